@@ -1,9 +1,18 @@
 #!/usr/bin/env python
 """bench.py -- merged Mpixels/s of the HIP pixel merger on synthetic 1024x2048 maps.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, and the
+roofline and phase figures that the timed steps' own HIP events give).  `--full` adds every side
+measurement described below (`pipelined`, `id_match`, `scoring_pass_general_path`, `exact_engine`,
+`default_mode` / `value_proven_path`, `cpu_baseline`); each of them runs outside the timed steps.
+`--dump-outputs DIR` writes what the last timed step returned to its caller -- the instance mask, the
+class of each instance and the log-likelihood, as DIR/<name>.npy in float32 / float64 (rank r of
+N > 1 prefixes `rank<r>_`) -- so that two builds can be compared output for output: the inputs are
+seeded, and the image of the last step depends only on --steps and --warmup.
 
 One "step" = one pass of the hot path over one batch of synthetic input: every rank merges ONE
 1024x2048 Cityscapes-shape image (C=9 classes, O=10 log-spiral offsets, options 0/1/0.03 of
@@ -14,7 +23,7 @@ the merges of the following steps, all of them complete inside the timed region)
 through POOL different images (636 MB of maps, more than the 256 MiB Infinity Cache), so a step
 reads its maps from HBM and not from a cache warmed by the previous step.
 
-Rank 0 prints ONE JSON line with BOTH paths on the same images:
+Rank 0 prints ONE JSON line; with --full it holds BOTH paths on the same images:
 
 * `value` = pixels merged by all ranks / wall time of the K timed steps (max over ranks), in Mpixel/s, on the
   library's SPECULATIVE fast path (mode AUTO with require_proof = -1: the component contraction when the maps are
@@ -249,6 +258,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements outside the timed steps (pipelined rate, id match against "
+                         "the reference's outputs, general path, exact engine, default mode, CPU baseline); the "
+                         "--no-* options below drop single ones of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (mask, object classes, log-likelihood) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-general-path", action="store_true")
     ap.add_argument("--no-pipelined", action="store_true")
@@ -445,9 +460,21 @@ def main():
     elapsed = time.perf_counter() - t0
     exchange_wait_ms = ex.wait_ms if ex is not None else 0.0
 
+    if args.dump_outputs:
+        # what a caller of the timed path received in the last step; the mask's ids and the class codes are small
+        # integers, exact in float32
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        prefix = "rank%d_" % rank if world > 1 else ""
+        k = st["num_instances"]
+        arrays = {"mask": mask.cpu().numpy().astype(np.float32),
+                  "object_class": table[:k].cpu().numpy().astype(np.float32),
+                  "total_logprob": np.array([st["total_logprob"]], dtype=np.float64)}
+        for name, a in arrays.items():
+            np.save(os.path.join(args.dump_outputs, prefix + name + ".npy"), a)
+
     # the same steps with PIPELINED_DEPTH images in flight (one GPU; outside the contract line)
     pipelined = None
-    if world == 1 and not args.no_pipelined and depth == 1:
+    if args.full and world == 1 and not args.no_pipelined and depth == 1:
         side_pool = seg.MergerPool(H, W, C, O, depth=PIPELINED_DEPTH, device=local_rank)
         run_steps(0, 2 * PIPELINED_DEPTH, side_pool)
         fence()
@@ -487,30 +514,32 @@ def main():
     # instance-id match of EVERY image of every rank's pool against the reference's own result for
     # that image (golden vectors tests/golden/cseg_synth_1024x2048_*.npz, produced by the
     # reference's segment.cc in 380-540 s per image); outside the timed region
-    from mergenet_amd import labels as ck      # plain numpy label-map comparison
-    checked, equal = 0, 0
-    for j, sd in enumerate(seeds):
-        gname = "cseg_synth_1024x2048_cfg2.npz" if sd == 1000 else "cseg_synth_1024x2048_s%d.npz" % sd
-        golden = os.path.join(ROOT, "tests", "golden", gname)
-        if not os.path.exists(golden):
-            continue
-        z = np.load(golden)
-        m_j, t_j, _, st_j = merger.segment(pool_images[j][0], pool_images[j][1], offs, opts)
-        got_cls = [int(c) for c in t_j.cpu().numpy()[: st_j["num_instances"]]]
-        checked += 1
-        equal += int(ck.masks_equivalent(m_j.cpu().numpy(), got_cls, z["mask"],
-                                         [int(c) for c in z["object_class"]]))
-    if world > 1:
-        t = torch.tensor([checked, equal], dtype=torch.int64, device=dev)
-        dist.all_reduce(t)
-        checked, equal = int(t[0].item()), int(t[1].item())
-    id_match = {"vs": "reference segment.cc (golden vectors, seeds 1000..1007)",
-                "images_checked": checked, "images_equal": equal, "equal": bool(checked and checked == equal)}
+    id_match = None
+    if args.full:
+        from mergenet_amd import labels as ck      # plain numpy label-map comparison
+        checked, equal = 0, 0
+        for j, sd in enumerate(seeds):
+            gname = "cseg_synth_1024x2048_cfg2.npz" if sd == 1000 else "cseg_synth_1024x2048_s%d.npz" % sd
+            golden = os.path.join(ROOT, "tests", "golden", gname)
+            if not os.path.exists(golden):
+                continue
+            z = np.load(golden)
+            m_j, t_j, _, st_j = merger.segment(pool_images[j][0], pool_images[j][1], offs, opts)
+            got_cls = [int(c) for c in t_j.cpu().numpy()[: st_j["num_instances"]]]
+            checked += 1
+            equal += int(ck.masks_equivalent(m_j.cpu().numpy(), got_cls, z["mask"],
+                                             [int(c) for c in z["object_class"]]))
+        if world > 1:
+            t = torch.tensor([checked, equal], dtype=torch.int64, device=dev)
+            dist.all_reduce(t)
+            checked, equal = int(t[0].item()), int(t[1].item())
+        id_match = {"vs": "reference segment.cc (golden vectors, seeds 1000..1007)",
+                    "images_checked": checked, "images_equal": equal, "equal": bool(checked and checked == equal)}
 
     # the general path (rounds) on the same images, outside the timed region: its affinity-scoring
     # pass (class pass + edge pass) is the kernel the north star names
     general = None
-    if rank == 0 and not args.no_general_path:
+    if args.full and rank == 0 and not args.no_general_path:
         ropts = seg.default_options(same_different_bias=OPTS[0], object_merge_factor=OPTS[1],
                                     merge_logprob_bias=OPTS[2], mode=seg.MN_MODE_ROUNDS)
         g = {"ms_class_pass": 0.0, "ms_edge_pass": 0.0, "ms_total": 0.0}
@@ -525,13 +554,13 @@ def main():
     # outside the timed region: what the library's default AUTO falls back to when the fast path's
     # answer is not certified
     exact = None
-    if rank == 0 and world == 1 and not args.no_exact:
+    if args.full and rank == 0 and world == 1 and not args.no_exact:
         exact = exact_engine_sample(seg, synth, offs, local_rank)
 
     # the proven path (library defaults) on this rank's own pool, outside the timed region; the ring's
     # contexts are released first (the batch takes what memory there is)
     default_mode = None
-    if not args.no_default_mode:
+    if args.full and not args.no_default_mode:
         for mg in mergers_ring[1:]:
             mg.close()
         default_mode = default_mode_block(seg, pool_images, seeds, offs, local_rank, args.default_batch)
@@ -630,7 +659,7 @@ def main():
                        "mode": {0: "auto", 1: "exact", 2: "rounds", 3: "components"}.get(args.mode),
                        "proof": "speculative fast path (require_proof = -1): on these images its answer is not "
                                 "certified -- equality with the reference's own outputs is measured on every image "
-                                "of the pool in this run (id_match); the library's default AUTO redoes an "
+                                "of the pool by a --full run (id_match); the library's default AUTO redoes an "
                                 "uncertified image in the exact engine (exact_engine)",
                        "mode_used": sorted({1: "exact", 2: "rounds", 3: "components"}.get(m, m) for m in modes),
                        "exchange": ("one all_gather per step of the masks (%s wire) + class tables + "
@@ -653,8 +682,9 @@ def main():
             "merge_stats": {"rounds": st["rounds"], "finisher_steps": st["finisher_steps"],
                             "merges": st["merges"], "certified": st["certified"],
                             "instances": st["num_instances"]},
-            "id_match": id_match,
         }
+        if id_match is not None:
+            out["id_match"] = id_match
         if pipelined is not None:
             out["pipelined"] = pipelined
         if general is not None:
@@ -680,7 +710,7 @@ def main():
                                "default_mode / value_proven_path")
         if exact is not None:
             out["exact_engine"] = exact
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -6,8 +6,9 @@ TAG=${1:-r02}
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$ROOT"
 mkdir -p gpurun_out/$TAG
-python bench.py > gpurun_out/$TAG/bench_line.json 2> gpurun_out/$TAG/bench.err
-python bench.py --mode 2 --steps 6 --warmup 1 --no-cpu-baseline --no-pipelined > gpurun_out/$TAG/bench_line_rounds_mode.json 2>> gpurun_out/$TAG/bench.err
+O=$_                    # the directory just made
+python bench.py --full > $O/bench_line.json 2> $O/bench.err
+python bench.py --full --mode 2 --steps 6 --warmup 1 --no-cpu-baseline --no-pipelined > $O/bench_line_rounds_mode.json 2>> $O/bench.err
 MN_PROF_BENCH=1 bash tools/prof_kernels.sh ${TAG}_bench 200 > gpurun_out/$TAG/kernel_stats.txt 2>&1
 cp gpurun_out/${TAG}_bench_kernel_stats.csv gpurun_out/$TAG/bench_kernel_stats.csv
 MN_PROF_BENCH=1 MN_PROF_ARGS="--mode 2" bash tools/prof_kernels.sh ${TAG}_rounds 6 > gpurun_out/$TAG/kernel_stats_rounds.txt 2>&1

@@ -8,9 +8,9 @@ mkdir -p gpurun_out/$TAG
 O=gpurun_out/$TAG
 step() { echo "[collect $(date +%H:%M:%S)] $*"; }
 step "bench, driver's command line"
-python bench.py --steps 20 --warmup 5 > $O/bench_line_driver_cmd.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_line_driver_cmd.json 2> $O/bench.err
 step "bench, default command (2000 steps)"
-python bench.py > $O/bench_line.json 2>> $O/bench.err
+python bench.py --full > $O/bench_line.json 2>> $O/bench.err
 step "kernel stats of the bench loop (fast path), 200 steps"
 MN_PROF_BENCH=1 MN_PROF_ARGS="--no-default-mode" bash tools/prof_kernels.sh ${TAG}_bench 200 > $O/bench_kernel_stats_per_image.txt 2>&1
 cp gpurun_out/${TAG}_bench_kernel_stats.csv $O/bench_kernel_stats.csv

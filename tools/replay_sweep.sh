@@ -2,7 +2,7 @@
 # hipGraph replay of the launches behind the sweep (bench --replay) against plain launches, 20 and 2000 steps (GPU box)
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 LOG="$ROOT/gpurun_out/replay_sweep.log"; : > "$LOG"
-FLAGS="--no-cpu-baseline --no-exact --no-default-mode --no-pipelined --no-general-path"
+FLAGS="--full --no-cpu-baseline --no-exact --no-default-mode --no-pipelined --no-general-path"
 for rep in 1 2 3; do
 for r in "" "--replay"; do
   for k in 20 2000; do

@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 mkdir -p "$ROOT/gpurun_out"
 LOG="$ROOT/gpurun_out/variant_ab.log"
 : > "$LOG"
-FLAGS="--no-cpu-baseline --no-exact --no-default-mode --no-pipelined --no-general-path"
+FLAGS="--full --no-cpu-baseline --no-exact --no-default-mode --no-pipelined --no-general-path"
 for lib in "$@"; do
   for rep in 1 2; do
     MN_LIB="$ROOT/$lib" python3 "$ROOT/bench.py" --steps 2000 --warmup 20 $FLAGS 2>/dev/null | python3 -c "
