@@ -41,8 +41,9 @@ enum mn_status {
   MN_ERR_CAPACITY = -4,     /* image larger than the context was created for                  */
   MN_ERR_NO_BACKGROUND = -10, /* pysegmenter prune: no class-0 object (reference: NameError)  */
   MN_ERR_INTERNAL = -20,
-  MN_ERR_UNPROVEN = -30     /* a proven result was asked for, the fast path could not certify its own and
-                               the exact engine found no room for its workspace                   */
+  MN_ERR_UNPROVEN = -30     /* a proven result was asked for (require_proof) and could not be had: no room for
+                               the exact engine's or the reference-order loop's workspace, or a Python-variant
+                               result whose tied choices conflict (the output then holds that proof 3 result) */
 };
 
 enum mn_variant {
@@ -72,9 +73,11 @@ enum mn_proof {
   MN_PROOF_NONE = 0,             /* measured only: an approximation of the sequential order on order-dependent inputs */
   MN_PROOF_CERTIFICATE = 1,      /* ANY order of the lazy greedy ends in this partition          */
   MN_PROOF_SEQUENTIAL = 2,       /* the reference's sequential order was run and no choice among bit-equal priorities
-                                    was left to the engine: every pop was forced (tied_steps == 0) or the reference's
+                                    was left to the engine: every pop was forced (tied_steps == 0), or the reference's
                                     own heap / hash-map order among equals was reproduced (tie_order_used ==
-                                    MN_TIES_REFERENCE)                                                               */
+                                    MN_TIES_REFERENCE), or there were tied pops whose choices provably commute
+                                    (tied_steps > 0, tied_conflicts == 0: no tied choice wrote what another read or
+                                    wrote, so every order among equals ends in this state; mn_kernels_exact.h "ties") */
   MN_PROOF_SEQUENTIAL_TIES = 3   /* the sequential order was run, but some pops chose among bit-equal priorities by
                                     the engine's rule (lowest record id) where the reference's std::priority_queue
                                     chooses by heap position: equal to the reference on most vectors held at the
@@ -126,7 +129,8 @@ typedef struct mn_options {
                                   whatever mode was asked for, and -- if that run chose among bit-equal
                                   priorities by its own rule (proof 3) -- once more in the reference's order
                                   among equals (tie_order MN_TIES_REFERENCE; MN_ERR_UNPROVEN for the Python
-                                  variant, whose heapq order is not restated); -1 = it is handed back as it is (the
+                                  variant, whose heapq order is not restated, with the proof 3 output left in
+                                  place; mn_segment_exact_batch applies the same per image); -1 = it is handed back as it is (the
                                   speculative fast path: an approximation on order-dependent inputs,
                                   stats.proof tells); 0 (default) = by mode: AUTO redoes it, an explicit
                                   MN_MODE_ROUNDS / MN_MODE_COMPONENTS request is taken as a request for
@@ -254,7 +258,14 @@ int mn_sweep_time_device(mn_context* ctx, const float* const* d_class_pred, cons
  * returns when all images are done.  Results are those of `count` separate MN_MODE_EXACT calls; the images the
  * tie policy sends to the reference-order loop (opts->tie_order; stats.tied_conflicts > 0) are redone TOGETHER,
  * one workgroup per image in one launch of that loop, and up to MN_TIE_LIMIT_BATCH_RECORDS initial records
- * instead of MN_TIE_LIMIT_RECORDS (the loop is sequential: images in flight are its throughput). */
+ * instead of MN_TIE_LIMIT_RECORDS (the loop is sequential: images in flight are its throughput).  With
+ * opts->tie_order == MN_TIES_REFERENCE the exact engine is not run at all.
+ * opts->require_proof = 1 holds per image as in a single call: after the hand-over, every image that is still
+ * proof 3 (no certificate, tied choices that conflict, not redone by the tie policy) is redone in the reference's
+ * order, together and whatever its size; stats keep the tied pops the exact engine met.  Where that is not possible
+ * (Python variant; MN_ERR_CAPACITY from the loop's workspace) the image's output stays the exact engine's (proof 3),
+ * its stats[i].status is MN_ERR_UNPROVEN, the other images are unaffected, and the call returns the first non-OK
+ * status. */
 int mn_segment_exact_batch(mn_context** ctxs, int count, const float* const* d_class_pred, int class_dim,
                            const float* const* d_adj_pred, int offset_dim, int img_width, int img_height,
                            int num_classes, const int* offset_list, int* const* d_mask,

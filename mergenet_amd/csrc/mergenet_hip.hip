@@ -2100,7 +2100,10 @@ extern "C" int mn_segment_exact_batch(mn_context** ctxs, int count, const float*
     (void)hipGetLastError();
     for (int i = 0; i < count; i++) ctxs[i]->xw.max_blocks = count > ncu ? 6144 : 0;
   }
-  rc = exact_run(ctxs, count, Ps, st);
+  const bool ref_possible = o.variant == MN_VARIANT_CSEGMENT;
+  // (MN_TIES_REFERENCE: straight to the reference-order loop, as a single call goes)
+  const bool ref_only = ref_possible && o.tie_order == MN_TIES_REFERENCE;
+  if (!ref_only) rc = exact_run(ctxs, count, Ps, st);
   for (int i = 0; i < count; i++) ctxs[i]->xw.max_blocks = 0;
   if (rc != MN_OK) { free(Ps); g_last_status = rc; return rc; }
   // The tie policy, as a single call applies it: images whose tied choices conflict (or all, with
@@ -2109,44 +2112,86 @@ extern "C" int mn_segment_exact_batch(mn_context** ctxs, int count, const float*
   // call (MN_TIE_LIMIT_BATCH_RECORDS).
   long long tie_limit = MN_TIE_LIMIT_BATCH_RECORDS;
   if (const char* e = getenv("MN_TIE_LIMIT")) tie_limit = atoll(e);
-  const bool ref_possible = o.variant == MN_VARIANT_CSEGMENT;
   int n_redo = 0;
   mn_context** rc_ctx = static_cast<mn_context**>(malloc((size_t)count * sizeof(mn_context*)));
   ImgParams* rc_P = static_cast<ImgParams*>(malloc((size_t)count * sizeof(ImgParams)));
   struct Saved { long long ts, tm, tc; int tt; };
   Saved* saved = static_cast<Saved*>(malloc((size_t)count * sizeof(Saved)));
   unsigned char* redo = static_cast<unsigned char*>(calloc((size_t)count, 1));
-  if (!rc_ctx || !rc_P || !saved || !redo) rc = MN_ERR_INTERNAL;
+  int* rc_idx = static_cast<int*>(malloc((size_t)count * sizeof(int)));
+  // (require_proof reads every image's verdict after the hand-over: statistics are kept also when the caller wants none)
+  mn_stats* own_stats = (!stats && o.require_proof > 0) ? static_cast<mn_stats*>(calloc((size_t)count, sizeof(mn_stats))) : nullptr;
+  mn_stats* out = stats ? stats : own_stats;
+  auto release = [&]() { free(Ps); free(rc_ctx); free(rc_P); free(saved); free(redo); free(rc_idx); free(own_stats); };
+  if (!rc_ctx || !rc_P || !saved || !redo || !rc_idx || (o.require_proof > 0 && !out)) rc = MN_ERR_INTERNAL;
   for (int i = 0; i < count && rc == MN_OK; i++) {
-    const XCtl* h = ctxs[i]->xw.h_ctl;
-    redo[i] = ref_possible && (o.tie_order == MN_TIES_REFERENCE ||
-                               (o.tie_order == MN_TIES_DEFAULT && x_ties_unresolved(h) &&
-                                (long long)W * H * offset_dim <= tie_limit));
+    redo[i] = ref_only || (ref_possible && o.tie_order == MN_TIES_DEFAULT && x_ties_unresolved(ctxs[i]->xw.h_ctl) &&
+                           (long long)W * H * offset_dim <= tie_limit);
     if (!redo[i]) continue;
-    saved[n_redo] = Saved{h->tied_steps, h->tied_merges, h->tied_conflicts, h->ttrack};
+    if (!ref_only) {
+      const XCtl* h = ctxs[i]->xw.h_ctl;
+      saved[n_redo] = Saved{h->tied_steps, h->tied_merges, h->tied_conflicts, h->ttrack};
+    }
     rc_ctx[n_redo] = ctxs[i]; rc_P[n_redo] = Ps[i]; n_redo++;
   }
   if (rc == MN_OK && n_redo > 0) {
     rc = run_reforder_batch(rc_ctx, n_redo, rc_P, st);
-    for (int j = 0; j < n_redo && rc == MN_OK; j++) {
-      XCtl* h = rc_ctx[j]->xw.h_ctl;
-      if (o.tie_order != MN_TIES_REFERENCE) {          // (what the exact engine met)
-        h->tied_steps = saved[j].ts; h->tied_merges = saved[j].tm; h->tied_conflicts = saved[j].tc; h->ttrack = saved[j].tt;
-      }
+    for (int j = 0; j < n_redo && rc == MN_OK && !ref_only; j++) {
+      XCtl* h = rc_ctx[j]->xw.h_ctl;                   // (what the exact engine met)
+      h->tied_steps = saved[j].ts; h->tied_merges = saved[j].tm; h->tied_conflicts = saved[j].tc; h->ttrack = saved[j].tt;
     }
   }
-  free(Ps); free(rc_ctx); free(rc_P); free(saved);
-  if (rc != MN_OK) { free(redo); g_last_status = rc; return rc; }
+  if (rc != MN_OK) { release(); g_last_status = rc; return rc; }
   // hand-over and output stage of every image (labels, mask, class table, certificate, log-likelihood)
   for (int i = 0; i < count; i++) {
     ctxs[i]->xw.prerun = redo[i] ? 2 : 1;
     const int r = segment_attempt(ctxs[i], d_class_pred[i], class_dim, d_adj_pred[i], offset_dim, W, H, num_classes,
                                   offset_list, d_mask[i], d_object_class[i], d_partition ? d_partition[i] : nullptr,
-                                  &o, stream, stats ? &stats[i] : nullptr, MN_MODE_EXACT, false);
+                                  &o, stream, out ? &out[i] : nullptr, MN_MODE_EXACT, false);
     ctxs[i]->xw.prerun = 0;
     if (r != MN_OK && rc == MN_OK) rc = r;
   }
-  free(redo);
+  // require_proof = 1, as mn_segment_finish applies it to a single call: a result that chose among bit-equal
+  // priorities by the engine's own rule (proof 3 -- known only now: a certificate may have proven it after all) is not
+  // taken for proven.  Those images are redone TOGETHER in the reference's order among equals, whatever their size
+  // (csegment variant), or marked MN_ERR_UNPROVEN (the Python variant, whose heapq / dict order is not restated; or no
+  // room for the loop's workspace) -- the exact engine's output then stays in place, and says proof 3.
+  if (o.require_proof > 0) {
+    int n2 = 0;
+    for (int i = 0; i < count; i++) {
+      if (out[i].status != MN_OK || out[i].proof != MN_PROOF_SEQUENTIAL_TIES) continue;
+      if (!ref_possible) {
+        out[i].status = MN_ERR_UNPROVEN;
+        if (rc == MN_OK) rc = MN_ERR_UNPROVEN;
+        continue;
+      }
+      const XCtl* h = ctxs[i]->xw.h_ctl;
+      saved[n2] = Saved{h->tied_steps, h->tied_merges, h->tied_conflicts, h->ttrack};
+      rc_ctx[n2] = ctxs[i]; rc_P[n2] = Ps[i]; rc_idx[n2] = i; n2++;
+    }
+    if (n2 > 0) {
+      const int r2 = run_reforder_batch(rc_ctx, n2, rc_P, st);
+      if (r2 == MN_ERR_CAPACITY) {
+        for (int j = 0; j < n2; j++) out[rc_idx[j]].status = MN_ERR_UNPROVEN;
+        if (rc == MN_OK) rc = MN_ERR_UNPROVEN;
+      } else if (r2 != MN_OK) {
+        release(); g_last_status = r2; return r2;
+      } else {
+        for (int j = 0; j < n2; j++) {
+          const int i = rc_idx[j];
+          XCtl* h = ctxs[i]->xw.h_ctl;                 // (what the exact engine met)
+          h->tied_steps = saved[j].ts; h->tied_merges = saved[j].tm; h->tied_conflicts = saved[j].tc; h->ttrack = saved[j].tt;
+          ctxs[i]->xw.prerun = 2;
+          const int r = segment_attempt(ctxs[i], d_class_pred[i], class_dim, d_adj_pred[i], offset_dim, W, H, num_classes,
+                                        offset_list, d_mask[i], d_object_class[i], d_partition ? d_partition[i] : nullptr,
+                                        &o, stream, &out[i], MN_MODE_EXACT, false);
+          ctxs[i]->xw.prerun = 0;
+          if (r != MN_OK && rc == MN_OK) rc = r;
+        }
+      }
+    }
+  }
+  release();
   g_last_status = rc;
   return rc;
 }

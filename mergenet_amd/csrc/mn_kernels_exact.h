@@ -698,6 +698,7 @@ __global__ __launch_bounds__(64) void mn_x_run(const ImgParams* __restrict__ Ps,
       MN_X_LOAD_OBJECTS(mn_key_u(k0), mn_key_v(k0));
     }
     if (lane == 0) X.leaf[rid] = 0u;               // (out of its block before the scan; see mn_x_scan_block)
+    MN_X_MEM_SYNC();   // (paranoid build: lane 0's store before the whole wave's loads of that block)
     u64 bm;
     if (ahead) bm = mn_x_scan_block<false>(X.leaf, blk << X.Blog, B, lane, nullptr, nullptr);
     else bm = mn_x_scan_block<true>(X.leaf, blk << X.Blog, B, lane, &X.rec[rid], &rraw);
@@ -825,6 +826,7 @@ __global__ __launch_bounds__(64) void mn_x_run(const ImgParams* __restrict__ Ps,
       mn_x_group_refresh(l1, l2, (int)(blk >> 6), lane);
       MN_X_LDS_SYNC();
       MN_X_STAMP(4);
+      MN_X_MEM_SYNC();   // (paranoid build: the fresh leaf and the stamps before the next step's loads)
       continue;
     }
 

@@ -719,7 +719,12 @@ class ExactBatch:
     """``count`` images of one shape through the exact engine in ONE launch of its loop
     (``mn_segment_exact_batch``): the engine is one wavefront per image, so images in flight are its
     throughput.  One context (workspace) per image; ``segment`` takes lists of [C,H,W] / [O,H,W] tensors
-    (at most ``count``) and returns a list of what :meth:`Merger.segment` returns."""
+    (at most ``count``) and returns a list of what :meth:`Merger.segment` returns.
+
+    ``require_proof = 1`` is applied per image as a single call applies it: results that are ``proof 3`` are redone
+    together in the reference's order among equals.  Where that cannot be done (the Python variant) the call raises
+    ``MergeNetError`` with status ``MN_ERR_UNPROVEN`` whose ``results`` attribute is the list ``segment`` would have
+    returned: every image's output is valid, and ``stats["status"] == MN_ERR_UNPROVEN`` marks the unproven ones."""
 
     def __init__(self, H: int, W: int, C: int, O: int, count: int, device: Optional[int] = None):
         if count < 1:
@@ -754,10 +759,15 @@ class ExactBatch:
             vp(*[t.data_ptr() for t in masks]), vp(*[t.data_ptr() for t in tables]),
             vp(*[t.data_ptr() for t in parts]) if parts is not None else None,
             ctypes.byref(opts), ctypes.c_void_p(stream), stats)
+        results = [(masks[i], tables[i], parts[i] if parts is not None else None, stats[i].as_dict())
+                   for i in range(n)]
+        if rc == MN_ERR_UNPROVEN:
+            err = MergeNetError(rc)
+            err.results = results
+            raise err
         if rc != 0:
             raise MergeNetError(rc)
-        return [(masks[i], tables[i], parts[i] if parts is not None else None, stats[i].as_dict())
-                for i in range(n)]
+        return results
 
     def close(self):
         for m in self.mergers:

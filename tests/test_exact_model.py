@@ -48,6 +48,54 @@ def test_a_tie_decided_vector_is_reported_as_conflicting():
     assert not labels.masks_equivalent(mask, classes, g["mask"], g["object_class"])
 
 
+# ---- fresh tied inputs: the verdict table that tests/test_gpu_proof.py holds the engine's proof claim to ----------
+# synth.blurred_v1(H, W, 9, generate_offsets(40, 10), seed, radius=2, noise=0.05) with options (0.0, 1.0, 0.03): every
+# one of these maps has tied pops (86-123 of ~26 k at 64x128, ~400 of ~52 k at 96x160, ~2 000 of ~117 k at 128x256).
+# The table is what the model said when it was written; the test below and the GPU module assert it per input, so
+# that neither can go vacuous if the generator or the model drifts.
+FRESH_OPTS = (0.0, 1.0, 0.03)
+EXPECTED_NO_CONFLICT = {(64, 128): (8102, 8103, 8106, 8107, 8111, 8112, 8113, 8114, 8115),
+                        (96, 160): (8504, 8507),
+                        (128, 256): (8701,)}
+EXPECTED_CONFLICT = {(64, 128): (8100, 8101, 8104, 8105, 8108, 8109, 8110),
+                     (96, 160): (8500,),
+                     (128, 256): (8700,)}
+# the lowest-id rule ends in a partition that is NOT the reference's on this one (on the other conflict seeds the two
+# rules happen to end in the same partition)
+WITNESS_SEED = 8100
+FRESH_TIED = sorted((H, W, seed) for table in (EXPECTED_NO_CONFLICT, EXPECTED_CONFLICT)
+                    for (H, W), seeds in table.items() for seed in seeds)
+
+
+def fresh_tied_input(H, W, seed):
+    from mergenet_amd import synth
+    offs = synth.generate_offsets(40, 10)
+    return synth.blurred_v1(H, W, 9, offs, seed, radius=2, noise=0.05), offs
+
+
+def expected_conflict(H, W, seed):
+    assert (seed in EXPECTED_CONFLICT[(H, W)]) != (seed in EXPECTED_NO_CONFLICT[(H, W)])
+    return seed in EXPECTED_CONFLICT[(H, W)]
+
+
+@pytest.mark.parametrize("H,W,seed", FRESH_TIED)
+def test_verdict_table_of_the_fresh_tied_inputs(oracle, H, W, seed):
+    """The model's yes / no on every fresh input equals the pinned table; no conflict => the model's partition (lowest
+    record id among equals) is the partition of the oracle's run of the reference's loop (its heap's order among
+    equals); and on seed 8100 -- a conflict -- it is not: there the verdict is not idle caution."""
+    s, offs = fresh_tied_input(H, W, seed)
+    sdb, omf, bias = FRESH_OPTS
+    ref = oracle.run_csegment(s.class_probs, s.sameness_probs, 9, offs, sdb, omf, bias)
+    part, ocls, st = exact_model.run(s.class_probs, s.sameness_probs, offs, omf, bias)
+    assert st["tied_steps"] > 0, st
+    assert (st["tied_conflicts"] > 0) == expected_conflict(H, W, seed), st
+    if st["tied_conflicts"] == 0:
+        assert oracle.same_partition(part, ref.partition), st
+        assert st["merges"] == ref.stats["n_merges"]
+    if seed == WITNESS_SEED:
+        assert st["tied_conflicts"] > 0 and not oracle.same_partition(part, ref.partition), st
+
+
 @pytest.mark.parametrize("window", [3, 16, 64])
 @pytest.mark.parametrize("name", ["cseg_adv_32x32_o0", "cseg_adv_48x48_o1", "cseg_synth_32x64_n60", "cseg_blur_64x128_r2",
                                   "cseg_checker_96x128_b015"])

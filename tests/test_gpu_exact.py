@@ -445,7 +445,8 @@ def test_paranoid_build_gives_the_same_masks_and_step_counts():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     paranoid = os.path.join(root, "mergenet_amd", "libmergenet_hip_paranoid.so")
     assert os.path.exists(paranoid), "make -C mergenet_amd/csrc builds it"
-    names = ["cseg_blur_64x128_r2", "cseg_crowd48_256x512_s6400"]
+    names = ["cseg_blur_64x128_r2", "cseg_crowd48_256x512_s6400", "cseg_blur_512x1024_r2_s4243",
+             "cseg_blur_64x128_r2_s8001"]
     outs = []
     for lib in (None, paranoid):
         env = dict(os.environ)

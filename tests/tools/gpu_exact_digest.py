@@ -21,5 +21,6 @@ for name in sys.argv[1:]:
     out[name] = {"mask": hashlib.sha256(np.ascontiguousarray(mask).tobytes()).hexdigest(),
                  "partition": hashlib.sha256(np.ascontiguousarray(part).tobytes()).hexdigest(),
                  "classes": classes, "steps": st["finisher_steps"], "merges": st["merges"],
-                 "tied_steps": st["tied_steps"], "tied_conflicts": st["tied_conflicts"]}
+                 "tied_steps": st["tied_steps"], "tied_merges": st["tied_merges"],
+                 "tied_conflicts": st["tied_conflicts"], "proof": st["proof"]}
 print(json.dumps(out))
