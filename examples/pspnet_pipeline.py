@@ -6,7 +6,8 @@ models/resnet.py:21-24), neither available offline, so this is our own definitio
 shape with random weights: a plumbing / throughput configuration, not a model-parity claim.
 The hand-off is device resident: sigmoid outputs (utils/inference_utils.py:44,96) -> Merger with
 the binding's clip fused into the loads; no .npy files (utils/inference_utils.py:122-126), no host
-copy.
+copy.  Under autocast (--dtype bfloat16 | float16, the default here) the network writes 16-bit maps and
+the merger reads them in that width: no float32 copy in between either.
 """
 
 from __future__ import annotations
@@ -80,19 +81,30 @@ class PSPNetResNet50(nn.Module):
 
 
 @torch.no_grad()
-def segment_image(model: PSPNetResNet50, image, offsets, merger, opts):
-    """image [1,3,H,W] on the GPU -> (mask, class_table, stats); everything stays on the device."""
-    logits = model(image)[0]
-    probs = torch.sigmoid(logits).float().contiguous()          # inference_utils.py:44,96
+def segment_image(model: PSPNetResNet50, image, offsets, merger, opts, dtype=None):
+    """image [1,3,H,W] on the GPU -> (mask, class_table, stats); everything stays on the device.
+    dtype: torch.bfloat16 / torch.float16 runs the model under autocast and hands its 16-bit sigmoid
+    outputs to the merger as they are; None: float32 throughout."""
+    if dtype is None or dtype == torch.float32:
+        probs = torch.sigmoid(model(image)[0]).float()           # inference_utils.py:44,96
+    else:
+        with torch.autocast("cuda", dtype=dtype):
+            probs = torch.sigmoid(model(image)[0])               # stays 16 bit: the merger widens on load
     C = model.num_classes
-    return merger.segment(probs[:C].contiguous(), probs[C:].contiguous(), offsets, opts)
+    # (slices along the first axis of a contiguous tensor are contiguous: views, not copies)
+    return merger.segment(probs[:C], probs[C:], offsets, opts)
 
 
 if __name__ == "__main__":
-    import sys, time
+    import argparse, sys, time
     sys.path.insert(0, ".")
     from mergenet_amd import synth, segmenter as seg
-    H, W = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (512, 1024)
+    ap = argparse.ArgumentParser()
+    ap.add_argument("size", nargs="*", type=int, default=[512, 1024], help="H W")
+    ap.add_argument("--dtype", choices=["bfloat16", "float16", "float32"], default="bfloat16")
+    args = ap.parse_args()
+    H, W = args.size[0], args.size[1]
+    dtype = getattr(torch, args.dtype)
     offs = synth.generate_offsets(40, 10)
     torch.manual_seed(0)
     model = PSPNetResNet50(9, len(offs)).cuda().eval()
@@ -101,7 +113,7 @@ if __name__ == "__main__":
     opts = seg.default_options(clip_inputs=1, mode=seg.MN_MODE_ROUNDS)
     for _ in range(2):
         torch.cuda.synchronize(); t = time.perf_counter()
-        mask, table, _, st = segment_image(model, img, offs, merger, opts)
+        mask, table, _, st = segment_image(model, img, offs, merger, opts, dtype=dtype)
         torch.cuda.synchronize(); dt = time.perf_counter() - t
-    print("PSPNet-ResNet50 forward + merge %dx%d: %.1f ms (merger %.1f ms), %d instances"
-          % (H, W, dt * 1e3, st["ms_total"], st["num_instances"]))
+    print("PSPNet-ResNet50 forward + merge %dx%d, maps in %s: %.1f ms (merger %.1f ms), %d instances"
+          % (H, W, args.dtype, dt * 1e3, st["ms_total"], st["num_instances"]))

@@ -67,6 +67,9 @@ enum mn_mode {
                             ROUNDS when the input is not sign-separable (mode_used tells)         */
 };
 
+/* Element type of the probability maps handed to the *_t entry points (both maps of a call share one). */
+enum mn_dtype { MN_DTYPE_F32 = 0, MN_DTYPE_F16 = 1, MN_DTYPE_BF16 = 2 };   /* IEEE binary32 / binary16 / bfloat16 */
+
 enum mn_tie_order { MN_TIES_DEFAULT = 0, MN_TIES_REFERENCE = 1, MN_TIES_LOWEST_ID = 2 };
 /* mn_stats.proof */
 enum mn_proof {
@@ -93,7 +96,10 @@ typedef struct mn_options {
   float merge_logprob_bias;    /* segment.h:248 */
   int variant;                 /* enum mn_variant */
   int mode;                    /* enum mn_mode */
-  int clip_inputs;             /* 1: clip to [2^-23, 1-2^-23] on load (c_segment.pyx:53-55 fused) */
+  int clip_inputs;             /* 1: clip to [2^-23, 1-2^-23] on load (c_segment.pyx:53-55 fused).  For 16-bit
+                                  maps (MN_DTYPE_F16 / MN_DTYPE_BF16) the clip on load is ALWAYS on, whatever
+                                  this says: neither format holds 1 - 2^-23, and a saturated sigmoid is exactly
+                                  1.0 in both (and 0.0 in binary16)                                  */
   int exact_limit;             /* AUTO: images with at most this many initial records go to EXACT right
                                   away (0 = default 32768)                                        */
   int finish_limit;            /* ROUNDS: hand over to the sequential finisher at <= this many
@@ -122,8 +128,10 @@ typedef struct mn_options {
                                   (from the third): a loop over images through fixed buffers; bit 7:
                                   time the sweep with an event packet before and behind it instead
                                   of start/stop events on its own dispatch (round 2's first form:
-                                  measures dispatch gap + kernel).  (Round 4 removed the opt-in engines
-                                  that were measured slower or known to deviate: bits 3, 8-13.)          */
+                                  measures dispatch gap + kernel); bit 8: a 16-bit map's sweep takes 4
+                                  pixels per lane (8-byte loads) where it would take 8 (16-byte loads) --
+                                  same results, for the measurement of the two forms.  (Round 4 removed the
+                                  opt-in engines that were measured slower or known to deviate: bits 3, 9-13.) */
   int require_proof;           /* what happens to a result that is not PROVEN equal to the reference's
                                   sequential order (stats.proof == 0): 1 = it is redone in MN_MODE_EXACT,
                                   whatever mode was asked for, and -- if that run chose among bit-equal
@@ -308,6 +316,57 @@ int mn_exact_phase_a_device(mn_context* ctx, const float* d_class_pred, int clas
                             const float* d_adj_pred, int offset_dim, int img_width, int img_height,
                             int num_classes, const int* offset_list, const mn_options* opts, void* stream,
                             unsigned char* d_cls_out, float* d_oml_out, float* d_prio_out);
+
+/* ---- 16-bit probability maps -------------------------------------------------------------------------
+ * The *_t entry points take the maps as untyped device pointers plus their element type, `int dtype` (enum
+ * mn_dtype): float32, IEEE binary16 or bfloat16, the width the network wrote them in -- no float32 copy is
+ * made anywhere.  ARGUMENT ORDER: that of the float entry point, with `int dtype` right after the group of the
+ * two map pointers (d_class_pred, class_dim, d_adj_pred, offset_dim, DTYPE, img_width, ...; where the two
+ * pointers are adjacent -- mn_sweep_time_device_t -- right after them); mn_prepare_device_t has one dtype
+ * behind each of its two pointers.  Both maps of a call share the dtype.  An unknown dtype is MN_ERR_ARGUMENT.
+ * Every kernel widens on load (exact) and computes in float32, so a call on 16-bit maps gives what the float
+ * entry point gives on the same values widened to float32 with clip_inputs = 1 (see mn_options.clip_inputs:
+ * a 16-bit map is always clipped on load; same_different_bias is applied after widening).  The sweep takes 8
+ * pixels per lane where N % 8 == 0, W % 8 == 0 and the planes are 16-byte aligned (info_out[0] of
+ * mn_sweep_device_t is then 8), which regroups the float products behind total_logprob / logsum_out: those
+ * agree to rounding (1e-5 relative), everything else bit for bit.  The float entry points are one-line calls
+ * of these with MN_DTYPE_F32; mn_segment_finish serves both.  c_run_segmentation and mn_segment_host stay
+ * float32 only. */
+int mn_segment_device_t(mn_context* ctx, const void* d_class_pred, int class_dim, const void* d_adj_pred,
+                        int offset_dim, int dtype, int img_width, int img_height, int num_classes,
+                        const int* offset_list, int* d_mask, int* d_object_class, int* d_partition,
+                        const mn_options* opts, void* stream, mn_stats* stats);
+int mn_segment_launch_t(mn_context* ctx, const void* d_class_pred, int class_dim, const void* d_adj_pred,
+                        int offset_dim, int dtype, int img_width, int img_height, int num_classes,
+                        const int* offset_list, int* d_mask, int* d_object_class, int* d_partition,
+                        const mn_options* opts, void* stream);
+int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void* const* d_class_pred, int class_dim,
+                             const void* const* d_adj_pred, int offset_dim, int dtype, int img_width,
+                             int img_height, int num_classes, const int* offset_list, int* const* d_mask,
+                             int* const* d_object_class, int* const* d_partition, const mn_options* opts,
+                             void* stream, mn_stats* stats);
+int mn_score_device_t(mn_context* ctx, const void* d_class_pred, int class_dim, const void* d_adj_pred,
+                      int offset_dim, int dtype, int img_width, int img_height, int num_classes,
+                      const int* offset_list, const mn_options* opts, void* stream, unsigned char* d_cls_out,
+                      unsigned long long* d_best_out, float* ms_class_pass, float* ms_edge_pass);
+int mn_sweep_device_t(mn_context* ctx, const void* d_class_pred, int class_dim, const void* d_adj_pred,
+                      int offset_dim, int dtype, int img_width, int img_height, int num_classes,
+                      const int* offset_list, const mn_options* opts, void* stream, unsigned* d_bits_out,
+                      float* d_neg_out, unsigned char* d_cls_out, int* d_gsum_out, double* logsum_out,
+                      int* info_out);   /* info_out[0]: pixels per lane, 8 | 4 | 1 */
+int mn_sweep_time_device_t(mn_context* ctx, const void* const* d_class_pred, const void* const* d_adj_pred,
+                           int dtype, int n_inputs, int class_dim, int offset_dim, int img_width, int img_height,
+                           int num_classes, const int* offset_list, const mn_options* opts, void* stream,
+                           int reps, float* us_per_launch);
+int mn_exact_phase_a_device_t(mn_context* ctx, const void* d_class_pred, int class_dim, const void* d_adj_pred,
+                              int offset_dim, int dtype, int img_width, int img_height, int num_classes,
+                              const int* offset_list, const mn_options* opts, void* stream,
+                              unsigned char* d_cls_out, float* d_oml_out, float* d_prio_out);
+/* mn_prepare_device with typed ends: d_in holds in_dtype elements, d_out out_dtype elements; the arithmetic is
+ * float32 and a 16-bit output is that float32 value rounded to nearest even. */
+int mn_prepare_device_t(mn_context* ctx, const void* d_in, int in_dtype, int channels, int in_height,
+                        int in_width, void* d_out, int out_dtype, int out_height, int out_width,
+                        int apply_sigmoid, int clip, void* stream);
 
 /* Host-pointer convenience: copies in, runs mn_segment_device, copies out. */
 int mn_segment_host(mn_context* ctx, const float* class_pred, int class_dim, const float* adj_pred,

@@ -55,6 +55,7 @@ struct mn_context {
   size_t gen_bytes;
   size_t cc_cap;          // table capacity used by the last component contraction
   int debug_flags;        // mn_options.debug_flags of the call in progress
+  int dtype;              // enum mn_dtype of the maps of the call in progress (set by every *_t entry point)
   size_t bytes;
   // objects
   unsigned char *ocls, *cls0, *lpvalid, *matched, *pruned;
@@ -107,7 +108,7 @@ struct mn_context {
     int mode, rounds, finish_limit, N;
     long long R0;
     bool speculate, want_cert;
-    const float *d_class, *d_adj;
+    const void *d_class, *d_adj;   // elements of mn_context::dtype
     int class_dim, offset_dim, W, H, num_classes;
     int offs[2 * MN_MAX_OFFSETS];
     int *d_mask, *d_objcls, *d_part;
@@ -557,12 +558,18 @@ static int check_args(const mn_context* c, int class_dim, int offset_dim, int W,
   return MN_OK;
 }
 
-static void fill_params(ImgParams* P, const float* d_class, const float* d_same, int offset_dim,
+static inline bool dtype_ok(int dtype) {
+  return dtype == MN_DTYPE_F32 || dtype == MN_DTYPE_F16 || dtype == MN_DTYPE_BF16;
+}
+
+static void fill_params(ImgParams* P, const void* d_class, const void* d_same, int dtype, int offset_dim,
                         int W, int H, int num_classes, const int* offs, const mn_options* o) {
   memset(P, 0, sizeof(*P));
   P->H = H; P->W = W; P->N = W * H; P->C = num_classes; P->O = offset_dim;
   P->sdb = o->same_different_bias; P->omf = o->object_merge_factor; P->bias = o->merge_logprob_bias;
-  P->variant = o->variant; P->clip = o->clip_inputs ? 1 : 0;
+  // a 16-bit map cannot hold 1 - 2^-23 and a saturated sigmoid is exactly 1.0 in it: always clipped on load
+  P->variant = o->variant; P->clip = (o->clip_inputs || dtype != MN_DTYPE_F32) ? 1 : 0;
+  P->dtype = dtype;
   P->cls = d_class; P->same = d_same;
   P->djmin = 0; P->djmax = 0;
   for (int k = 0; k < offset_dim; k++) {
@@ -755,50 +762,83 @@ static size_t gsum_stride(int N) {
 #endif
 }
 
+// The sweep (mn_cc_sign) in the form for PX pixels per lane and maps of element type DT.
+template <int PX, int DT>
+static void launch_sign(mn_context* c, const ImgParams& P, hipStream_t st, bool cls, bool lean_cls) {
+  const int N = P.N, ngroups = (N + PX - 1) / PX;
+  const dim3 g(grid_for(ngroups, MN_CC_SIGN_THREADS)), b(MN_CC_SIGN_THREADS);
+  ClsOut CO;
+  CO.ocls = lean_cls ? nullptr : c->ocls; CO.cls0 = c->cls0; CO.lpvalid = lean_cls ? nullptr : c->lpvalid;
+  CO.gsum = reinterpret_cast<int*>(c->lpsum);     // (the summed class log-probs are written later, at roots only)
+  CO.gstride = gsum_stride(P.N);
+  // (a 16-bit map is always clipped on load; its plain form is the clip alone: mn_cc_value)
+  const bool plain = (DT != MN_DTYPE_F32 || !P.clip) && P.sdb == 0.0f;
+  // Timed: the dispatch itself carries the two events (hipExtLaunchKernel: start and stop time of THIS
+  // kernel), instead of an event packet in front of it and one behind -- each of those cost a ~6 us
+  // dispatch gap on the stream, and the pair measured gap + kernel (54 us where rocprofv3 saw 46).
+#define MN_LAUNCH_SIGN(PLAINV, CLSV)                                                                    \
+  do {                                                                                                \
+    if (c->ext_events)                                                                                \
+      hipExtLaunchKernelGGL((mn_cc_sign<PX, PLAINV, (CLSV) && PX >= 4, DT>), g, b, 0, st, c->ev[0], c->ev[10], 0, \
+                            P, c->cc_bits, c->cc_negbits, c->scalars + 6, c->partial, CO); \
+    else                                                                                              \
+      hipLaunchKernelGGL((mn_cc_sign<PX, PLAINV, (CLSV) && PX >= 4, DT>), g, b, 0, st, P, c->cc_bits, c->cc_negbits, \
+                         c->scalars + 6, c->partial, CO);                                             \
+  } while (0)
+  if (plain && cls) MN_LAUNCH_SIGN(true, true);
+  else if (plain) MN_LAUNCH_SIGN(true, false);
+  else if (cls) MN_LAUNCH_SIGN(false, true);
+  else MN_LAUNCH_SIGN(false, false);
+#undef MN_LAUNCH_SIGN
+}
+
+// Pixels per lane of the sweep.  4 whenever the planes stay aligned for a lane's one load per plane (N % 4 == 0):
+// with W % 4 != 0 one lane per row runs over the row's end (mn_cc_sign: `straddle`; W >= 4: its four pixels then
+// span at most two rows, which is what mn_cc_sign assumes), else 1.  A 16-bit map takes 8 -- one 16-byte load per
+// plane, as the float32 map's 4 -- where N % 8 == 0, W % 8 == 0 (no lane runs over a row's end) and the planes
+// are 16-byte aligned; debug_flags bit 8 keeps it at 4 (8-byte loads), for the measurement of the two forms.
+static int sweep_px(const mn_context* c, const ImgParams& P) {
+  if (!((P.N & 3) == 0 && P.W >= 4)) return 1;
+  if (P.dtype != MN_DTYPE_F32 && !(c->debug_flags & 256) && (P.N & 7) == 0 && (P.W & 7) == 0 &&
+      ((reinterpret_cast<uintptr_t>(P.cls) | reinterpret_cast<uintptr_t>(P.same)) & 15) == 0)
+    return 8;
+  return 4;
+}
+
+// The sweep in the form sweep_px chose (`cls`: it takes the class planes too; only with px >= 4).
+static void launch_sweep(mn_context* c, const ImgParams& P, hipStream_t st, int px, bool cls, bool lean_cls) {
+#define MN_SWEEP_DT(PXV)                                                                         \
+  do {                                                                                           \
+    if (P.dtype == MN_DTYPE_F16) launch_sign<PXV, MN_DTYPE_F16>(c, P, st, cls, lean_cls);        \
+    else launch_sign<PXV, MN_DTYPE_BF16>(c, P, st, cls, lean_cls);                               \
+  } while (0)
+  if (P.dtype == MN_DTYPE_F32) {
+    if (px == 4) launch_sign<4, MN_DTYPE_F32>(c, P, st, cls, lean_cls);
+    else launch_sign<1, MN_DTYPE_F32>(c, P, st, false, false);
+  } else if (px == 8) MN_SWEEP_DT(8);
+  else if (px == 4) MN_SWEEP_DT(4);
+  else { cls = false; lean_cls = false; MN_SWEEP_DT(1); }
+#undef MN_SWEEP_DT
+}
+
+// the sweep over the positive masks that hooks the offsets the tile stages did not take
+template <int PX>
+static void launch_cc_hook(mn_context* c, const ImgParams& P, hipStream_t st, unsigned kmask,
+                           const unsigned* hook_bits = nullptr, hipEvent_t hook_done = nullptr) {
+  const int N = P.N, ngroups = (N + PX - 1) / PX;
+  const dim3 gx(8 * ((grid_for(ngroups, 256) + 7) / 8));
+  if (hook_done)                 // (its completion is the fork point of the image: no event packet behind it)
+    hipExtLaunchKernelGGL(mn_cc_hook<PX>, gx, dim3(256), 0, st, nullptr, hook_done, 0, P,
+                          hook_bits ? hook_bits : (const unsigned*)c->cc_bits, c->parent, kmask);
+  else
+    hipLaunchKernelGGL(mn_cc_hook<PX>, gx, dim3(256), 0, st, P, hook_bits ? hook_bits : (const unsigned*)c->cc_bits,
+                       c->parent, kmask);
+}
+
 // Component contraction (mn_kernels_cc.h).  With `wait`: returns 0 when the input is
 // sign-separable (object state + list of records between components ready, count in h_cnt), 1
 // when it is not (caller falls back), < 0 on error.  Without: everything is queued, 0 is returned
 // and the verdict is read by the caller at the end.
-template <int PX>
-static void launch_cc_px(mn_context* c, const ImgParams& P, hipStream_t st, unsigned kmask, bool hook,
-                         bool cls = false, const unsigned* hook_bits = nullptr,
-                         hipEvent_t hook_done = nullptr, bool lean_cls = false) {
-  const int N = P.N, ngroups = (N + PX - 1) / PX;
-  if (!hook) {
-    const dim3 g(grid_for(ngroups, MN_CC_SIGN_THREADS)), b(MN_CC_SIGN_THREADS);
-    ClsOut CO;
-    CO.ocls = lean_cls ? nullptr : c->ocls; CO.cls0 = c->cls0; CO.lpvalid = lean_cls ? nullptr : c->lpvalid;
-    CO.gsum = reinterpret_cast<int*>(c->lpsum);     // (the summed class log-probs are written later, at roots only)
-    CO.gstride = gsum_stride(P.N);
-    const bool plain = !P.clip && P.sdb == 0.0f;
-    // Timed: the dispatch itself carries the two events (hipExtLaunchKernel: start and stop time of THIS
-    // kernel), instead of an event packet in front of it and one behind -- each of those cost a ~6 us
-    // dispatch gap on the stream, and the pair measured gap + kernel (54 us where rocprofv3 saw 46).
-#define MN_LAUNCH_SIGN(PLAINV, CLSV)                                                                    \
-    do {                                                                                                \
-      if (c->ext_events)                                                                                \
-        hipExtLaunchKernelGGL((mn_cc_sign<PX, PLAINV, (CLSV) && PX == 4>), g, b, 0, st, c->ev[0], c->ev[10], 0, \
-                              P, c->cc_bits, c->cc_negbits, c->scalars + 6, c->partial, CO); \
-      else                                                                                              \
-        hipLaunchKernelGGL((mn_cc_sign<PX, PLAINV, (CLSV) && PX == 4>), g, b, 0, st, P, c->cc_bits, c->cc_negbits, \
-                           c->scalars + 6, c->partial, CO);                                             \
-    } while (0)
-    if (plain && cls) MN_LAUNCH_SIGN(true, true);
-    else if (plain) MN_LAUNCH_SIGN(true, false);
-    else if (cls) MN_LAUNCH_SIGN(false, true);
-    else MN_LAUNCH_SIGN(false, false);
-#undef MN_LAUNCH_SIGN
-  } else {
-    const dim3 gx(8 * ((grid_for(ngroups, 256) + 7) / 8));
-    if (hook_done)                 // (its completion is the fork point of the image: no event packet behind it)
-      hipExtLaunchKernelGGL(mn_cc_hook<PX>, gx, dim3(256), 0, st, nullptr, hook_done, 0, P,
-                            hook_bits ? hook_bits : (const unsigned*)c->cc_bits, c->parent, kmask);
-    else
-      hipLaunchKernelGGL(mn_cc_hook<PX>, gx, dim3(256), 0, st, P, hook_bits ? hook_bits : (const unsigned*)c->cc_bits,
-                         c->parent, kmask);
-  }
-}
-
 static int run_components(mn_context* c, const ImgParams& P, hipStream_t& st, bool wait, bool with_ball,
                           bool with_compact, bool fork_before_sums, bool cores = false) {
   const int N = P.N;
@@ -821,8 +861,10 @@ static int run_components(mn_context* c, const ImgParams& P, hipStream_t& st, bo
   // the sweep takes 4 pixels per lane whenever the planes stay 16-byte aligned (N % 4 == 0): with
   // W % 4 != 0 one lane per row runs over the row's end (mn_cc_sign: `straddle`)
   // (W >= 4: a straddling lane's four pixels then span at most two rows, which is what mn_cc_sign assumes)
-  const bool sweep4 = (N & 3) == 0 && P.W >= 4;
-  const size_t sign_blocks = grid_for((size_t)(sweep4 ? N / 4 : N), MN_CC_SIGN_THREADS);
+  // (a 16-bit map: 8 where it can, sweep_px; what the sweep leaves is laid out per 4 pixels either way)
+  const int px = sweep_px(c, P);
+  const bool sweep4 = px >= 4;
+  const size_t sign_blocks = grid_for((size_t)(N / px), MN_CC_SIGN_THREADS);
   c->cc_sign_blocks = (int)(sign_blocks * (MN_CC_SIGN_THREADS / 64));       // (waves: one partial sum each)
   // class range of the components: `root` and `mapbuf` are free until the output stage
   int* clsmin = c->root;
@@ -833,8 +875,7 @@ static int run_components(mn_context* c, const ImgParams& P, hipStream_t& st, bo
   const bool fused_cls = sweep4;
   // (pure components mode: the roots' class and validity flag are set by mn_cc_finish)
   const bool lean_cls = fused_cls && !cores;
-  if (sweep4) launch_cc_px<4>(c, P, st, 0u, false, fused_cls, nullptr, nullptr, lean_cls);
-  else launch_cc_px<1>(c, P, st, 0u, false);
+  launch_sweep(c, P, st, px, fused_cls, lean_cls);
   if (!few_events && !c->ext_events) MN_HIP(hipEventRecord(c->ev[10], st));
   // cores (first step of the general rounds): the labelling runs on the edges between clean pixels
   const unsigned* lbits = c->cc_bits;
@@ -876,8 +917,8 @@ static int run_components(mn_context* c, const ImgParams& P, hipStream_t& st, bo
   // the last kernel on the caller's stream can carry the fork event itself (hipExtLaunchKernel stop event)
   fork_by_hook = fork_ext && kmask;
   if (kmask) {
-    if (four) launch_cc_px<4>(c, P, st, kmask, true, false, lbits, fork_by_hook ? c->ev_fork : nullptr);
-    else launch_cc_px<1>(c, P, st, kmask, true, false, lbits, fork_by_hook ? c->ev_fork : nullptr);
+    if (four) launch_cc_hook<4>(c, P, st, kmask, lbits, fork_by_hook ? c->ev_fork : nullptr);
+    else launch_cc_hook<1>(c, P, st, kmask, lbits, fork_by_hook ? c->ev_fork : nullptr);
   }
   if (c->replay.capturing) {
     MN_HIP(hipStreamEndCapture(c->replay.cap, &c->replay.gA));
@@ -1507,8 +1548,8 @@ static int segment_read_back(mn_context* c, const mn_options* opts, int mode, bo
 
 // `defer` (with a speculative attempt only): return MN_PENDING as soon as everything is queued;
 // the caller reads back later with segment_read_back after waiting for ev_done.
-static int segment_attempt(mn_context* c, const float* d_class_pred, int class_dim,
-                           const float* d_adj_pred, int offset_dim, int W, int H,
+static int segment_attempt(mn_context* c, const void* d_class_pred, int class_dim,
+                           const void* d_adj_pred, int offset_dim, int W, int H,
                            int num_classes, const int* offset_list, int* d_mask,
                            int* d_object_class, int* d_partition, const mn_options* opts,
                            void* stream, mn_stats* stats, int force_mode, bool speculate,
@@ -1523,7 +1564,7 @@ static int segment_attempt(mn_context* c, const float* d_class_pred, int class_d
   hipStream_t st = static_cast<hipStream_t>(stream);
 
   ImgParams P;
-  fill_params(&P, d_class_pred, d_adj_pred, offset_dim, W, H, num_classes, offset_list, opts);
+  fill_params(&P, d_class_pred, d_adj_pred, c->dtype, offset_dim, W, H, num_classes, offset_list, opts);
   // (development aid: MN_DEBUG_FLAGS_OR in the environment is OR-ed into debug_flags, so that a whole
   //  test run can be put through an opt-in code path)
   static const int env_flags = getenv("MN_DEBUG_FLAGS_OR") ? atoi(getenv("MN_DEBUG_FLAGS_OR")) : 0;
@@ -1891,12 +1932,13 @@ static int segment_attempt(mn_context* c, const float* d_class_pred, int class_d
 // First half: queue everything for one image and return.  In components mode (the default for
 // large images) nothing has been waited for when this returns; other modes run to completion here.
 // The context is busy until mn_segment_finish; inputs and outputs must stay alive until then.
-extern "C" int mn_segment_launch(mn_context* c, const float* d_class_pred, int class_dim,
-                                 const float* d_adj_pred, int offset_dim, int W, int H,
-                                 int num_classes, const int* offset_list, int* d_mask,
-                                 int* d_object_class, int* d_partition, const mn_options* opts,
-                                 void* stream) {
-  if (!c || c->pend.active) { g_last_status = MN_ERR_ARGUMENT; return MN_ERR_ARGUMENT; }
+extern "C" int mn_segment_launch_t(mn_context* c, const void* d_class_pred, int class_dim,
+                                   const void* d_adj_pred, int offset_dim, int dtype, int W, int H,
+                                   int num_classes, const int* offset_list, int* d_mask,
+                                   int* d_object_class, int* d_partition, const mn_options* opts,
+                                   void* stream) {
+  if (!c || c->pend.active || !dtype_ok(dtype)) { g_last_status = MN_ERR_ARGUMENT; return MN_ERR_ARGUMENT; }
+  c->dtype = dtype;
   HostLaunchTimer host_timer;
   mn_context::Pending& q = c->pend;
   if (opts) q.opts = *opts; else mn_default_options(&q.opts);
@@ -1914,7 +1956,7 @@ extern "C" int mn_segment_launch(mn_context* c, const float* d_class_pred, int c
   if (want_replay) {
     memset(key, 0, sizeof(key));
     const void* ptrs[6] = {d_class_pred, d_adj_pred, d_mask, d_object_class, d_partition, stream};
-    const int dims[5] = {class_dim, offset_dim, W, H, num_classes};
+    const int dims[6] = {class_dim, offset_dim, W, H, num_classes, dtype};
     memcpy(key + kb, ptrs, sizeof(ptrs)); kb += sizeof(ptrs);
     memcpy(key + kb, dims, sizeof(dims)); kb += sizeof(dims);
     memcpy(key + kb, &q.opts, sizeof(q.opts)); kb += sizeof(q.opts);
@@ -1929,13 +1971,13 @@ extern "C" int mn_segment_launch(mn_context* c, const float* d_class_pred, int c
     MN_HIP(hipSetDevice(c->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     ImgParams P;
-    fill_params(&P, d_class_pred, d_adj_pred, offset_dim, W, H, num_classes, offset_list, &q.opts);
+    fill_params(&P, d_class_pred, d_adj_pred, dtype, offset_dim, W, H, num_classes, offset_list, &q.opts);
     c->debug_flags = q.opts.debug_flags;
     c->ext_events = !(q.opts.debug_flags & 2) && !(q.opts.debug_flags & 128);
     c->cores_used = 0;
     const bool timed = !(q.opts.debug_flags & 2) && !c->ext_events;
     if (timed) MN_HIP(hipEventRecord(c->ev[0], st));
-    launch_cc_px<4>(c, P, st, 0u, false, true, nullptr, nullptr, true);
+    launch_sweep(c, P, st, sweep_px(c, P), true, true);      // (the key holds buffers and dtype: the recorded form)
     if (timed) MN_HIP(hipEventRecord(c->ev[10], st));
     MN_HIP(hipGraphLaunch(rp.eA, st));
     MN_HIP(hipEventRecord(c->ev_fork, st));
@@ -1981,6 +2023,15 @@ extern "C" int mn_segment_launch(mn_context* c, const float* d_class_pred, int c
   q.active = 2;                       // ran to completion on the ordinary path
   q.rc = rc;
   return MN_OK;
+}
+
+extern "C" int mn_segment_launch(mn_context* c, const float* d_class_pred, int class_dim,
+                                 const float* d_adj_pred, int offset_dim, int W, int H,
+                                 int num_classes, const int* offset_list, int* d_mask,
+                                 int* d_object_class, int* d_partition, const mn_options* opts,
+                                 void* stream) {
+  return mn_segment_launch_t(c, d_class_pred, class_dim, d_adj_pred, offset_dim, MN_DTYPE_F32, W, H, num_classes,
+                             offset_list, d_mask, d_object_class, d_partition, opts, stream);
 }
 
 // Second half: wait for the image queued by mn_segment_launch, read the verdict (a speculative
@@ -2046,15 +2097,15 @@ extern "C" int mn_segment_finish(mn_context* c, mn_stats* stats) {
   return rc;
 }
 
-extern "C" int mn_segment_device(mn_context* c, const float* d_class_pred, int class_dim,
-                                 const float* d_adj_pred, int offset_dim, int W, int H,
-                                 int num_classes, const int* offset_list, int* d_mask,
-                                 int* d_object_class, int* d_partition, const mn_options* opts,
-                                 void* stream, mn_stats* stats) {
+extern "C" int mn_segment_device_t(mn_context* c, const void* d_class_pred, int class_dim,
+                                   const void* d_adj_pred, int offset_dim, int dtype, int W, int H,
+                                   int num_classes, const int* offset_list, int* d_mask,
+                                   int* d_object_class, int* d_partition, const mn_options* opts,
+                                   void* stream, mn_stats* stats) {
   int rc = MN_ERR_ARGUMENT;
   if (!c || !c->pend.active)          // (a context with an unfinished launch is busy)
-    rc = mn_segment_launch(c, d_class_pred, class_dim, d_adj_pred, offset_dim, W, H, num_classes,
-                           offset_list, d_mask, d_object_class, d_partition, opts, stream);
+    rc = mn_segment_launch_t(c, d_class_pred, class_dim, d_adj_pred, offset_dim, dtype, W, H, num_classes,
+                             offset_list, d_mask, d_object_class, d_partition, opts, stream);
   if (rc != MN_OK) {                  // rejected, busy or failed: nothing was left pending
     if (stats) { memset(stats, 0, sizeof(*stats)); stats->status = rc; stats->total_logprob = NAN; }
     return rc;
@@ -2062,17 +2113,27 @@ extern "C" int mn_segment_device(mn_context* c, const float* d_class_pred, int c
   return mn_segment_finish(c, stats);
 }
 
+extern "C" int mn_segment_device(mn_context* c, const float* d_class_pred, int class_dim,
+                                 const float* d_adj_pred, int offset_dim, int W, int H,
+                                 int num_classes, const int* offset_list, int* d_mask,
+                                 int* d_object_class, int* d_partition, const mn_options* opts,
+                                 void* stream, mn_stats* stats) {
+  return mn_segment_device_t(c, d_class_pred, class_dim, d_adj_pred, offset_dim, MN_DTYPE_F32, W, H, num_classes,
+                             offset_list, d_mask, d_object_class, d_partition, opts, stream, stats);
+}
+
 // A batch of images of one shape through the exact engine in ONE launch of its loop (a workgroup per image);
 // see include/mergenet_hip.h.
-extern "C" int mn_segment_exact_batch(mn_context** ctxs, int count, const float* const* d_class_pred, int class_dim,
-                                      const float* const* d_adj_pred, int offset_dim, int W, int H, int num_classes,
-                                      const int* offset_list, int* const* d_mask, int* const* d_object_class,
-                                      int* const* d_partition, const mn_options* opts, void* stream,
-                                      mn_stats* stats) {
+extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void* const* d_class_pred, int class_dim,
+                                        const void* const* d_adj_pred, int offset_dim, int dtype, int W, int H,
+                                        int num_classes, const int* offset_list, int* const* d_mask,
+                                        int* const* d_object_class, int* const* d_partition, const mn_options* opts,
+                                        void* stream, mn_stats* stats) {
   mn_options o;
   if (opts) o = *opts; else mn_default_options(&o);
   o.mode = MN_MODE_EXACT;
-  if (!ctxs || count <= 0 || count > 4096 || !d_class_pred || !d_adj_pred || !d_mask || !d_object_class) {
+  if (!ctxs || count <= 0 || count > 4096 || !d_class_pred || !d_adj_pred || !d_mask || !d_object_class ||
+      !dtype_ok(dtype)) {
     g_last_status = MN_ERR_ARGUMENT;
     return MN_ERR_ARGUMENT;
   }
@@ -2090,8 +2151,10 @@ extern "C" int mn_segment_exact_batch(mn_context** ctxs, int count, const float*
   ImgParams* Ps = static_cast<ImgParams*>(malloc((size_t)count * sizeof(ImgParams)));
   if (!Ps) return MN_ERR_INTERNAL;
   int rc = MN_OK;
-  for (int i = 0; i < count; i++)
-    fill_params(&Ps[i], d_class_pred[i], d_adj_pred[i], offset_dim, W, H, num_classes, offset_list, &o);
+  for (int i = 0; i < count; i++) {
+    ctxs[i]->dtype = dtype;
+    fill_params(&Ps[i], d_class_pred[i], d_adj_pred[i], dtype, offset_dim, W, H, num_classes, offset_list, &o);
+  }
   {
     // more images than compute units: two workgroups per unit if each keeps its LDS under half of it
     int ncu = 256;
@@ -2196,21 +2259,32 @@ extern "C" int mn_segment_exact_batch(mn_context** ctxs, int count, const float*
   return rc;
 }
 
-extern "C" int mn_score_device(mn_context* c, const float* d_class_pred, int class_dim,
-                               const float* d_adj_pred, int offset_dim, int W, int H,
-                               int num_classes, const int* offset_list, const mn_options* opts,
-                               void* stream, unsigned char* d_cls_out,
-                               unsigned long long* d_best_out, float* ms_class_pass,
-                               float* ms_edge_pass) {
+extern "C" int mn_segment_exact_batch(mn_context** ctxs, int count, const float* const* d_class_pred, int class_dim,
+                                      const float* const* d_adj_pred, int offset_dim, int W, int H, int num_classes,
+                                      const int* offset_list, int* const* d_mask, int* const* d_object_class,
+                                      int* const* d_partition, const mn_options* opts, void* stream,
+                                      mn_stats* stats) {
+  return mn_segment_exact_batch_t(ctxs, count, reinterpret_cast<const void* const*>(d_class_pred), class_dim,
+                                  reinterpret_cast<const void* const*>(d_adj_pred), offset_dim, MN_DTYPE_F32, W, H,
+                                  num_classes, offset_list, d_mask, d_object_class, d_partition, opts, stream, stats);
+}
+
+extern "C" int mn_score_device_t(mn_context* c, const void* d_class_pred, int class_dim,
+                                 const void* d_adj_pred, int offset_dim, int dtype, int W, int H,
+                                 int num_classes, const int* offset_list, const mn_options* opts,
+                                 void* stream, unsigned char* d_cls_out,
+                                 unsigned long long* d_best_out, float* ms_class_pass,
+                                 float* ms_edge_pass) {
   mn_options defaults;
   if (!opts) { mn_default_options(&defaults); opts = &defaults; }
   int rc = check_args(c, class_dim, offset_dim, W, H, num_classes, offset_list, opts);
-  if (rc == MN_OK && (!d_class_pred || !d_adj_pred)) rc = MN_ERR_ARGUMENT;
+  if (rc == MN_OK && (!d_class_pred || !d_adj_pred || !dtype_ok(dtype))) rc = MN_ERR_ARGUMENT;
   if (rc != MN_OK) { g_last_status = rc; return rc; }
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
+  c->dtype = dtype;
   ImgParams P;
-  fill_params(&P, d_class_pred, d_adj_pred, offset_dim, W, H, num_classes, offset_list, opts);
+  fill_params(&P, d_class_pred, d_adj_pred, dtype, offset_dim, W, H, num_classes, offset_list, opts);
   c->debug_flags = opts->debug_flags;
   rc = ensure_fast(c);
   if (rc != MN_OK) return rc;
@@ -2229,34 +2303,45 @@ extern "C" int mn_score_device(mn_context* c, const float* d_class_pred, int cla
   return MN_OK;
 }
 
+extern "C" int mn_score_device(mn_context* c, const float* d_class_pred, int class_dim,
+                               const float* d_adj_pred, int offset_dim, int W, int H,
+                               int num_classes, const int* offset_list, const mn_options* opts,
+                               void* stream, unsigned char* d_cls_out,
+                               unsigned long long* d_best_out, float* ms_class_pass,
+                               float* ms_edge_pass) {
+  return mn_score_device_t(c, d_class_pred, class_dim, d_adj_pred, offset_dim, MN_DTYPE_F32, W, H, num_classes,
+                           offset_list, opts, stream, d_cls_out, d_best_out, ms_class_pass, ms_edge_pass);
+}
+
 // The affinity-scoring sweep of the default path alone (mn_cc_sign), and what it leaves, for the parity
 // test against the oracle's phase A (see include/mergenet_hip.h).
-extern "C" int mn_sweep_device(mn_context* c, const float* d_class_pred, int class_dim,
-                               const float* d_adj_pred, int offset_dim, int W, int H, int num_classes,
-                               const int* offset_list, const mn_options* opts, void* stream,
-                               unsigned* d_bits_out, float* d_neg_out, unsigned char* d_cls_out,
-                               int* d_gsum_out, double* logsum_out, int* info_out) {
+extern "C" int mn_sweep_device_t(mn_context* c, const void* d_class_pred, int class_dim,
+                                 const void* d_adj_pred, int offset_dim, int dtype, int W, int H, int num_classes,
+                                 const int* offset_list, const mn_options* opts, void* stream,
+                                 unsigned* d_bits_out, float* d_neg_out, unsigned char* d_cls_out,
+                                 int* d_gsum_out, double* logsum_out, int* info_out) {
   mn_options defaults;
   if (!opts) { mn_default_options(&defaults); opts = &defaults; }
   int rc = check_args(c, class_dim, offset_dim, W, H, num_classes, offset_list, opts);
-  if (rc == MN_OK && (!d_class_pred || !d_adj_pred || !d_bits_out || !d_neg_out)) rc = MN_ERR_ARGUMENT;
+  if (rc == MN_OK && (!d_class_pred || !d_adj_pred || !d_bits_out || !d_neg_out || !dtype_ok(dtype))) rc = MN_ERR_ARGUMENT;
   if (rc != MN_OK) { g_last_status = rc; return rc; }
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
+  c->dtype = dtype;
   ImgParams P;
-  fill_params(&P, d_class_pred, d_adj_pred, offset_dim, W, H, num_classes, offset_list, opts);
+  fill_params(&P, d_class_pred, d_adj_pred, dtype, offset_dim, W, H, num_classes, offset_list, opts);
   const int N = P.N;
   if (ensure_fast(c) != MN_OK) return MN_ERR_NO_DEVICE;
   c->debug_flags = opts->debug_flags | 2;          // (no events)
   c->ext_events = 0;
   c->cc_clean = 0;
-  const bool four = (N & 3) == 0 && P.W >= 4;   // (4 pixels per lane: also with W % 4 != 0, see run_components)
+  const int px = sweep_px(c, P);                // (4 pixels per lane: also with W % 4 != 0, see run_components)
+  const bool four = px >= 4;
   const bool fused_cls = four;
-  const size_t sign_blocks = grid_for((size_t)(four ? N / 4 : N), MN_CC_SIGN_THREADS);
+  const size_t sign_blocks = grid_for((size_t)(N / px), MN_CC_SIGN_THREADS);
   const size_t sign_waves = sign_blocks * (MN_CC_SIGN_THREADS / 64);
   MN_HIP(hipMemsetAsync(c->scalars, 0, MN_NSCALARS * sizeof(int), st));
-  if (four) launch_cc_px<4>(c, P, st, 0u, false, fused_cls);
-  else launch_cc_px<1>(c, P, st, 0u, false);
+  launch_sweep(c, P, st, px, fused_cls, false);
   MN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_neg_out), 0x7FC00000, (size_t)P.O * N, st));
   hipLaunchKernelGGL(mn_cc_export_neg, dim3((unsigned)grid_for((size_t)N, 256)), dim3(256), 0, st, P,
                      (const unsigned*)c->cc_negbits, d_neg_out);
@@ -2274,7 +2359,7 @@ extern "C" int mn_sweep_device(mn_context* c, const float* d_class_pred, int cla
   for (size_t b = 0; b < sign_waves; b++) t += hp[2 * b];
   free(hp);
   if (logsum_out) *logsum_out = t;
-  if (info_out) { info_out[0] = four ? 4 : 1; info_out[1] = fused_cls ? 1 : 0; info_out[2] = c->h_scalars[6]; }
+  if (info_out) { info_out[0] = px; info_out[1] = fused_cls ? 1 : 0; info_out[2] = c->h_scalars[6]; }
   MN_HIP(hipGetLastError());
   g_last_status = MN_OK;
   return MN_OK;
@@ -2283,14 +2368,24 @@ extern "C" int mn_sweep_device(mn_context* c, const float* d_class_pred, int cla
 // Timing of the sweep alone (tuning; see include/mergenet_hip.h): `reps` launches back to back on `stream`,
 // input set i % n_inputs for launch i, in the form the default path launches it.  Returns the average time per
 // launch by HIP events around the whole train (launch gaps of consecutive kernels included).
-extern "C" int mn_sweep_time_device(mn_context* c, const float* const* d_class_pred, const float* const* d_adj_pred,
-                                    int n_inputs, int class_dim, int offset_dim, int W, int H, int num_classes,
-                                    const int* offset_list, const mn_options* opts, void* stream, int reps,
-                                    float* us_per_launch) {
+extern "C" int mn_sweep_device(mn_context* c, const float* d_class_pred, int class_dim,
+                               const float* d_adj_pred, int offset_dim, int W, int H, int num_classes,
+                               const int* offset_list, const mn_options* opts, void* stream,
+                               unsigned* d_bits_out, float* d_neg_out, unsigned char* d_cls_out,
+                               int* d_gsum_out, double* logsum_out, int* info_out) {
+  return mn_sweep_device_t(c, d_class_pred, class_dim, d_adj_pred, offset_dim, MN_DTYPE_F32, W, H, num_classes,
+                           offset_list, opts, stream, d_bits_out, d_neg_out, d_cls_out, d_gsum_out, logsum_out, info_out);
+}
+
+extern "C" int mn_sweep_time_device_t(mn_context* c, const void* const* d_class_pred, const void* const* d_adj_pred,
+                                      int dtype, int n_inputs, int class_dim, int offset_dim, int W, int H,
+                                      int num_classes, const int* offset_list, const mn_options* opts, void* stream,
+                                      int reps, float* us_per_launch) {
   mn_options defaults;
   if (!opts) { mn_default_options(&defaults); opts = &defaults; }
   int rc = check_args(c, class_dim, offset_dim, W, H, num_classes, offset_list, opts);
-  if (rc == MN_OK && (!d_class_pred || !d_adj_pred || n_inputs < 1 || reps < 1 || !us_per_launch)) rc = MN_ERR_ARGUMENT;
+  if (rc == MN_OK && (!d_class_pred || !d_adj_pred || n_inputs < 1 || reps < 1 || !us_per_launch || !dtype_ok(dtype)))
+    rc = MN_ERR_ARGUMENT;
   if (rc != MN_OK) { g_last_status = rc; return rc; }
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2298,17 +2393,15 @@ extern "C" int mn_sweep_time_device(mn_context* c, const float* const* d_class_p
   c->debug_flags = opts->debug_flags | 2;          // (no events inside)
   c->ext_events = 0;
   c->cc_clean = 0;
-  const int N = W * H;
-  const bool four = (N & 3) == 0 && W >= 4;
+  c->dtype = dtype;
   MN_HIP(hipMemsetAsync(c->scalars, 0, MN_NSCALARS * sizeof(int), st));
   for (int phase = 0; phase < 2; phase++) {          // a tenth of the launches untimed first
     const int n = phase == 0 ? (reps + 9) / 10 : reps;
     if (phase == 1) MN_HIP(hipEventRecord(c->ev[0], st));
     for (int i = 0; i < n; i++) {
       ImgParams P;
-      fill_params(&P, d_class_pred[i % n_inputs], d_adj_pred[i % n_inputs], offset_dim, W, H, num_classes, offset_list, opts);
-      if (four) launch_cc_px<4>(c, P, st, 0u, false, true, nullptr, nullptr, true);
-      else launch_cc_px<1>(c, P, st, 0u, false);
+      fill_params(&P, d_class_pred[i % n_inputs], d_adj_pred[i % n_inputs], dtype, offset_dim, W, H, num_classes, offset_list, opts);
+      launch_sweep(c, P, st, sweep_px(c, P), true, true);
     }
     if (phase == 1) MN_HIP(hipEventRecord(c->ev[1], st));
   }
@@ -2323,20 +2416,30 @@ extern "C" int mn_sweep_time_device(mn_context* c, const float* const* d_class_p
 
 // Phase A of the exact engine (tests): log-odds and initial priority of every record in the layout
 // of the oracle's phase-A export ([offset][source pixel], NaN outside the image), arg-max classes.
-extern "C" int mn_exact_phase_a_device(mn_context* c, const float* d_class_pred, int class_dim,
-                                       const float* d_adj_pred, int offset_dim, int W, int H,
-                                       int num_classes, const int* offset_list, const mn_options* opts,
-                                       void* stream, unsigned char* d_cls_out, float* d_oml_out,
-                                       float* d_prio_out) {
+extern "C" int mn_sweep_time_device(mn_context* c, const float* const* d_class_pred, const float* const* d_adj_pred,
+                                    int n_inputs, int class_dim, int offset_dim, int W, int H, int num_classes,
+                                    const int* offset_list, const mn_options* opts, void* stream, int reps,
+                                    float* us_per_launch) {
+  return mn_sweep_time_device_t(c, reinterpret_cast<const void* const*>(d_class_pred),
+                                reinterpret_cast<const void* const*>(d_adj_pred), MN_DTYPE_F32, n_inputs, class_dim,
+                                offset_dim, W, H, num_classes, offset_list, opts, stream, reps, us_per_launch);
+}
+
+extern "C" int mn_exact_phase_a_device_t(mn_context* c, const void* d_class_pred, int class_dim,
+                                         const void* d_adj_pred, int offset_dim, int dtype, int W, int H,
+                                         int num_classes, const int* offset_list, const mn_options* opts,
+                                         void* stream, unsigned char* d_cls_out, float* d_oml_out,
+                                         float* d_prio_out) {
   mn_options defaults;
   if (!opts) { mn_default_options(&defaults); opts = &defaults; }
   int rc = check_args(c, class_dim, offset_dim, W, H, num_classes, offset_list, opts);
-  if (rc == MN_OK && (!d_class_pred || !d_adj_pred || !d_oml_out || !d_prio_out)) rc = MN_ERR_ARGUMENT;
+  if (rc == MN_OK && (!d_class_pred || !d_adj_pred || !d_oml_out || !d_prio_out || !dtype_ok(dtype))) rc = MN_ERR_ARGUMENT;
   if (rc != MN_OK) { g_last_status = rc; return rc; }
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
+  c->dtype = dtype;
   ImgParams P;
-  fill_params(&P, d_class_pred, d_adj_pred, offset_dim, W, H, num_classes, offset_list, opts);
+  fill_params(&P, d_class_pred, d_adj_pred, dtype, offset_dim, W, H, num_classes, offset_list, opts);
   rc = exact_setup(c, P, st);
   if (rc != MN_OK) { g_last_status = rc; return rc; }
   hipLaunchKernelGGL(mn_x_export_phase_a, dim3(grid_for((size_t)P.N * P.O, 256)), dim3(256), 0, st, P, c->xw.X,
@@ -2345,6 +2448,15 @@ extern "C" int mn_exact_phase_a_device(mn_context* c, const float* d_class_pred,
   MN_HIP(hipStreamSynchronize(st));
   g_last_status = MN_OK;
   return MN_OK;
+}
+
+extern "C" int mn_exact_phase_a_device(mn_context* c, const float* d_class_pred, int class_dim,
+                                       const float* d_adj_pred, int offset_dim, int W, int H,
+                                       int num_classes, const int* offset_list, const mn_options* opts,
+                                       void* stream, unsigned char* d_cls_out, float* d_oml_out,
+                                       float* d_prio_out) {
+  return mn_exact_phase_a_device_t(c, d_class_pred, class_dim, d_adj_pred, offset_dim, MN_DTYPE_F32, W, H, num_classes,
+                                   offset_list, opts, stream, d_cls_out, d_oml_out, d_prio_out);
 }
 
 static int ensure_staging(mn_context* c) {
@@ -2426,22 +2538,29 @@ extern "C" void c_run_segmentation(float* class_pred, int class_dim, float* adj_
 
 
 // ---- producer hand-off / mask post-processing -----------------
-extern "C" int mn_prepare_device(mn_context* c, const float* d_in, int channels, int in_height,
-                                 int in_width, float* d_out, int out_height, int out_width,
-                                 int apply_sigmoid, int clip, void* stream) {
+extern "C" int mn_prepare_device_t(mn_context* c, const void* d_in, int in_dtype, int channels, int in_height,
+                                   int in_width, void* d_out, int out_dtype, int out_height, int out_width,
+                                   int apply_sigmoid, int clip, void* stream) {
   if (!c || !d_in || !d_out || channels <= 0 || in_height <= 0 || in_width <= 0 || out_height <= 0 ||
-      out_width <= 0 || out_height > 65535 || channels > 65535) {
+      out_width <= 0 || out_height > 65535 || channels > 65535 || !dtype_ok(in_dtype) || !dtype_ok(out_dtype)) {
     g_last_status = MN_ERR_ARGUMENT;
     return MN_ERR_ARGUMENT;
   }
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(mn_prepare_maps, dim3(grid_for(out_width, 256), out_height, channels), dim3(256),
-                     0, st, d_in, channels, in_height, in_width, d_out, out_height, out_width,
+                     0, st, d_in, in_dtype, channels, in_height, in_width, d_out, out_dtype, out_height, out_width,
                      apply_sigmoid, clip);
   MN_HIP(hipGetLastError());
   g_last_status = MN_OK;
   return MN_OK;
+}
+
+extern "C" int mn_prepare_device(mn_context* c, const float* d_in, int channels, int in_height,
+                                 int in_width, float* d_out, int out_height, int out_width,
+                                 int apply_sigmoid, int clip, void* stream) {
+  return mn_prepare_device_t(c, d_in, MN_DTYPE_F32, channels, in_height, in_width, d_out, MN_DTYPE_F32, out_height,
+                             out_width, apply_sigmoid, clip, stream);
 }
 
 extern "C" int mn_upsample_mask_device(mn_context* c, const int* d_mask, int in_height, int in_width,

@@ -26,8 +26,9 @@ struct ImgParams {
   float vmin_first;    // pixel-level edges with a raw sameness value below this cannot reach priority >= 0
   float sep_hi, sep_lo; // components mode: an edge inside a component needs a sameness value >= sep_hi,
                         // one between components <= sep_lo (0.5 widened by the float32 rounding margin)
-  const float* cls;    // [C][N] class probabilities (borrowed)
-  const float* same;   // [O][N] sameness probabilities (borrowed)
+  int dtype;           // enum mn_dtype of BOTH maps; a 16-bit dtype always comes with clip == 1
+  const void* cls;     // [C][N] class probabilities (borrowed), elements of `dtype`
+  const void* same;    // [O][N] sameness probabilities (borrowed), elements of `dtype`
   int di[MN_MAX_OFFSETS];
   int dj[MN_MAX_OFFSETS];
 };
@@ -42,6 +43,44 @@ struct ObjState {
   float* lpsum;            // [C][N] summed class log-probs (Object::class_logprobs)
   unsigned char* lpvalid;  // [N]
 };
+
+// ---- typed loads of the probability maps ------------------------------------------------------------
+// Every read of a map goes through one of these.  Widening a 16-bit value to float32 is exact and written
+// out in plain C++: binary16 through the _Float16 -> float conversion (one v_cvt_f32_f16; the kernels are
+// built with denormals kept, so the binary16 subnormals -- live values here, most of them above the clip's
+// 2^-23 -- widen exactly), bfloat16 by placing its 16 bits in the high half of a float.
+typedef unsigned short mn_u16;
+__device__ __forceinline__ float mn_widen_f16(mn_u16 b) { return (float)__builtin_bit_cast(_Float16, b); }
+__device__ __forceinline__ float mn_widen_bf16(mn_u16 b) { return __uint_as_float((unsigned)b << 16); }
+template <int DT>
+__device__ __forceinline__ float mn_widen(mn_u16 b) {
+  return DT == MN_DTYPE_F16 ? mn_widen_f16(b) : mn_widen_bf16(b);
+}
+// two packed 16-bit values (element 0 in the low half, as they lie in memory)
+template <int DT>
+__device__ __forceinline__ float2 mn_widen2(unsigned w) {
+  if (DT == MN_DTYPE_F16) return make_float2(mn_widen_f16((mn_u16)(w & 0xFFFFu)), mn_widen_f16((mn_u16)(w >> 16)));
+  return make_float2(__uint_as_float(w << 16), __uint_as_float(w & 0xFFFF0000u));
+}
+
+// Element `i` of a map; the dtype is a run-time value, uniform over the launch (the cold sites: scalar loads of
+// the exact engine's set-up, the score kernels, the rounds, the output stage).
+__device__ __forceinline__ float mn_ld_map(const void* base, int dtype, size_t i) {
+  if (dtype == MN_DTYPE_F32) return static_cast<const float*>(base)[i];
+  const mn_u16 b = static_cast<const mn_u16*>(base)[i];
+  return dtype == MN_DTYPE_F16 ? mn_widen_f16(b) : mn_widen_bf16(b);
+}
+// Elements i .. i+3: one 16-byte or one 8-byte load.  (Planes of N % 4 != 0 elements start at any element: the
+// float32 form is then aligned to 4 bytes as it always was at these sites, the 16-bit form to 2, which the
+// packed type tells the compiler.)
+struct __attribute__((packed, aligned(2))) mn_uint2_h { unsigned x, y; };
+__device__ __forceinline__ float4 mn_ld_map4(const void* base, int dtype, size_t i) {
+  if (dtype == MN_DTYPE_F32) return *reinterpret_cast<const float4*>(static_cast<const float*>(base) + i);
+  const mn_uint2_h w = *reinterpret_cast<const mn_uint2_h*>(static_cast<const mn_u16*>(base) + i);
+  const float2 a = dtype == MN_DTYPE_F16 ? mn_widen2<MN_DTYPE_F16>(w.x) : mn_widen2<MN_DTYPE_BF16>(w.x);
+  const float2 b = dtype == MN_DTYPE_F16 ? mn_widen2<MN_DTYPE_F16>(w.y) : mn_widen2<MN_DTYPE_BF16>(w.y);
+  return make_float4(a.x, a.y, b.x, b.y);
+}
 
 __device__ __forceinline__ float mn_clip(float v) {
   return fminf(fmaxf(v, MN_EPS32), 1.0f - MN_EPS32);
@@ -66,8 +105,19 @@ __device__ __forceinline__ float mn_same_value(const ImgParams& P, float v) {
   return v;
 }
 
+// raw sameness value of offset k at pixel p (mn_same_value clips and applies the bias)
+__device__ __forceinline__ float mn_ld_same(const ImgParams& P, int k, int p) {
+  return mn_ld_map(P.same, P.dtype, (size_t)k * P.N + p);
+}
+__device__ __forceinline__ float4 mn_ld_same4(const ImgParams& P, int k, int p) {
+  return mn_ld_map4(P.same, P.dtype, (size_t)k * P.N + p);
+}
+__device__ __forceinline__ float4 mn_ld_class4(const ImgParams& P, int c, int p) {
+  return mn_ld_map4(P.cls, P.dtype, (size_t)c * P.N + p);
+}
+
 __device__ __forceinline__ float mn_ld_class(const ImgParams& P, int c, int p) {
-  float v = P.cls[(size_t)c * P.N + p];
+  float v = mn_ld_map(P.cls, P.dtype, (size_t)c * P.N + p);
   if (P.clip) v = mn_clip(v);
   return v;
 }

@@ -101,6 +101,41 @@ __device__ __forceinline__ float4 mn_ld_stream4(const float* p) {
   return *reinterpret_cast<const float4*>(p);
 #endif
 }
+// The 16-bit maps (DT = MN_DTYPE_F16 / MN_DTYPE_BF16): a lane's 4 values are one 8-byte load, its 8 values one
+// 16-byte load; DT = MN_DTYPE_F32 is the float load above, unchanged.
+typedef unsigned mn_u2v __attribute__((ext_vector_type(2)));
+template <int DT>
+__device__ __forceinline__ float4 mn_ld_stream4_t(const void* base, size_t i) {
+  if constexpr (DT == MN_DTYPE_F32) {
+    return mn_ld_stream4(static_cast<const float*>(base) + i);
+  } else {
+    const mn_u2v* q = reinterpret_cast<const mn_u2v*>(static_cast<const mn_u16*>(base) + i);
+#ifdef MN_NT_LOADS
+    const mn_u2v t = __builtin_nontemporal_load(q);
+#else
+    const mn_u2v t = *q;
+#endif
+    const float2 a = mn_widen2<DT>(t.x), b = mn_widen2<DT>(t.y);
+    return make_float4(a.x, a.y, b.x, b.y);
+  }
+}
+template <int DT>
+__device__ __forceinline__ void mn_ld_stream8_t(const void* base, size_t i, float* v) {
+  static_assert(DT != MN_DTYPE_F32, "8 values per load: 16-bit maps only");
+  const mn_u4v* q = reinterpret_cast<const mn_u4v*>(static_cast<const mn_u16*>(base) + i);
+#ifdef MN_NT_LOADS
+  const mn_u4v t = __builtin_nontemporal_load(q);
+#else
+  const mn_u4v t = *q;
+#endif
+  const float2 a = mn_widen2<DT>(t.x), b = mn_widen2<DT>(t.y), c = mn_widen2<DT>(t.z), d = mn_widen2<DT>(t.w);
+  v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y; v[4] = c.x; v[5] = c.y; v[6] = d.x; v[7] = d.y;
+}
+template <int DT>
+__device__ __forceinline__ float mn_ld_stream1_t(const void* base, size_t i) {
+  if constexpr (DT == MN_DTYPE_F32) return static_cast<const float*>(base)[i];
+  else return mn_widen<DT>(static_cast<const mn_u16*>(base)[i]);
+}
 __device__ __forceinline__ void mn_st_stream(int* p, int v) {
 #ifdef MN_NT_STORES
   __builtin_nontemporal_store(v, p);
@@ -117,9 +152,10 @@ __device__ __forceinline__ void mn_st_stream(uint4* p, uint4 v) {
 #endif
 }
 
-template <bool PLAIN>
+// (a 16-bit map is always clipped on load: its PLAIN form is the clip alone, no same_different_bias)
+template <bool PLAIN, int DT = MN_DTYPE_F32>
 __device__ __forceinline__ float mn_cc_value(const ImgParams& P, float v) {
-  return PLAIN ? v : mn_same_value(P, v);
+  return PLAIN ? (DT == MN_DTYPE_F32 ? v : mn_clip(v)) : mn_same_value(P, v);
 }
 
 // CLS (PX == 4, N % 4 == 0): the lane also streams the C class planes of its four pixels first -- the
@@ -143,6 +179,21 @@ __device__ __forceinline__ int mn_cc_argmax_logf(const ImgParams& P, int p) {
   return b;
 }
 
+// mn_cc_argmax_logf with the maps' element type known at compile time (the sweep's own instantiations)
+template <int DT>
+__device__ __forceinline__ int mn_cc_argmax_logf_t(const ImgParams& P, int p) {
+  float best = 0.0f;
+  int b = 0;
+  for (int c = 0; c < P.C; c++) {
+    float v = mn_ld_stream1_t<DT>(P.cls, (size_t)c * P.N + p);
+    if (P.clip) v = mn_clip(v);
+    const float l = logf(v);
+    if (c == 0 || l > best) { best = l; b = c; }
+  }
+  return b;
+}
+
+template <int DT>
 __device__ __forceinline__ void mn_cc_class_part(const ImgParams& P, const ClsOut& CO, int i) {
   // The arg-max is taken on the VALUES (logf is monotone); the reference's first-maximum rule on
   // logf values differs only if a class of LOWER index lies within rounding distance of the maximum
@@ -152,11 +203,11 @@ __device__ __forceinline__ void mn_cc_class_part(const ImgParams& P, const ClsOu
   // of the reference it stands for).
   float4 best, prev = make_float4(-1.0f, -1.0f, -1.0f, -1.0f);
   int b0 = 0, b1 = 0, b2 = 0, b3 = 0;
-  float4 nxt = mn_ld_stream4(P.cls + 4 * (size_t)i);
+  float4 nxt = mn_ld_stream4_t<DT>(P.cls, 4 * (size_t)i);
   for (int c = 0; c < P.C; c++) {
     float4 v = nxt;
     if (c + 1 < P.C)
-      nxt = mn_ld_stream4(P.cls + (size_t)(c + 1) * P.N + 4 * (size_t)i);
+      nxt = mn_ld_stream4_t<DT>(P.cls, (size_t)(c + 1) * P.N + 4 * (size_t)i);
     if (P.clip) { v.x = mn_clip(v.x); v.y = mn_clip(v.y); v.z = mn_clip(v.z); v.w = mn_clip(v.w); }
     if (c == 0) {
       best = v;
@@ -172,10 +223,10 @@ __device__ __forceinline__ void mn_cc_class_part(const ImgParams& P, const ClsOu
   // a lower class within 2^-18 of the maximum (logs of magnitude < 16 are 2^-20 apart at most, and
   // the GPU's logf is within an ulp of libm's): settle it the reference's way
   const float near = 1.0f - 3.814697265625e-06f;
-  if (prev.x >= best.x * near) b0 = mn_cc_argmax_logf(P, 4 * i);
-  if (prev.y >= best.y * near) b1 = mn_cc_argmax_logf(P, 4 * i + 1);
-  if (prev.z >= best.z * near) b2 = mn_cc_argmax_logf(P, 4 * i + 2);
-  if (prev.w >= best.w * near) b3 = mn_cc_argmax_logf(P, 4 * i + 3);
+  if (prev.x >= best.x * near) b0 = mn_cc_argmax_logf_t<DT>(P, 4 * i);
+  if (prev.y >= best.y * near) b1 = mn_cc_argmax_logf_t<DT>(P, 4 * i + 1);
+  if (prev.z >= best.z * near) b2 = mn_cc_argmax_logf_t<DT>(P, 4 * i + 2);
+  if (prev.w >= best.w * near) b3 = mn_cc_argmax_logf_t<DT>(P, 4 * i + 3);
   uchar4 o;
   o.x = (unsigned char)b0; o.y = (unsigned char)b1; o.z = (unsigned char)b2; o.w = (unsigned char)b3;
   // (pure components mode: only the component roots' class and validity flag are ever read, and
@@ -185,7 +236,49 @@ __device__ __forceinline__ void mn_cc_class_part(const ImgParams& P, const ClsOu
   if (CO.lpvalid) *reinterpret_cast<uchar4*>(CO.lpvalid + 4 * (size_t)i) = make_uchar4(0, 0, 0, 0);
 }
 
-template <int PX, bool PLAIN, bool CLS>
+// The same for a lane of EIGHT pixels of a 16-bit map (one 16-byte load per class plane): groups 2i and 2i + 1
+// of the layout above, so gsum, cls0 and everything behind the sweep are what the 4-pixel form leaves.  The
+// arithmetic per 4-pixel group is that of mn_cc_class_part on the widened values (a 16-bit map is always
+// clipped on load), so the outputs are bit-equal to the float32 sweep's on maps.float().
+template <int DT>
+__device__ __forceinline__ void mn_cc_class_part8(const ImgParams& P, const ClsOut& CO, int i) {
+  float best[8], prev[8];
+  int b[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) { best[j] = 0.0f; prev[j] = -1.0f; b[j] = 0; }
+  float nxt[8];
+  mn_ld_stream8_t<DT>(P.cls, 8 * (size_t)i, nxt);
+  for (int c = 0; c < P.C; c++) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) v[j] = mn_clip(nxt[j]);
+    if (c + 1 < P.C) mn_ld_stream8_t<DT>(P.cls, (size_t)(c + 1) * P.N + 8 * (size_t)i, nxt);
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      if (c == 0) best[j] = v[j];
+      else if (v[j] > best[j]) { prev[j] = best[j]; best[j] = v[j]; b[j] = c; }
+    }
+    int2 g;
+    g.x = __float2int_rn(logf((v[0] * v[1]) * (v[2] * v[3])) * 16777216.0f);
+    g.y = __float2int_rn(logf((v[4] * v[5]) * (v[6] * v[7])) * 16777216.0f);
+    *reinterpret_cast<int2*>(&CO.gsum[(size_t)c * CO.gstride + 2 * (size_t)i]) = g;
+  }
+  const float near = 1.0f - 3.814697265625e-06f;
+#pragma unroll
+  for (int j = 0; j < 8; j++)
+    if (prev[j] >= best[j] * near) b[j] = mn_cc_argmax_logf_t<DT>(P, 8 * i + j);
+  uint2 o;
+  o.x = (unsigned)b[0] | ((unsigned)b[1] << 8) | ((unsigned)b[2] << 16) | ((unsigned)b[3] << 24);
+  o.y = (unsigned)b[4] | ((unsigned)b[5] << 8) | ((unsigned)b[6] << 16) | ((unsigned)b[7] << 24);
+  if (CO.ocls) *reinterpret_cast<uint2*>(CO.ocls + 8 * (size_t)i) = o;
+  *reinterpret_cast<uint2*>(CO.cls0 + 8 * (size_t)i) = o;
+  if (CO.lpvalid) *reinterpret_cast<uint2*>(CO.lpvalid + 8 * (size_t)i) = make_uint2(0u, 0u);
+}
+
+// DT: element type of the maps.  MN_DTYPE_F32 takes PX = 4 | 1 as described above.  A 16-bit map takes PX = 8
+// (one 16-byte load of eight values per plane; N % 8 == 0, W % 8 == 0 -- no lane runs over a row's end -- and
+// 16-byte aligned planes), else PX = 4 with 8-byte loads, else PX = 1; its PLAIN form clips (mn_cc_value).
+template <int PX, bool PLAIN, bool CLS, int DT = MN_DTYPE_F32>
 __global__ __launch_bounds__(MN_CC_SIGN_THREADS) void mn_cc_sign(
     ImgParams P, unsigned* __restrict__ bits, unsigned* __restrict__ negbits, int* __restrict__ violations,
     double* __restrict__ partial, ClsOut CO) {
@@ -195,7 +288,12 @@ __global__ __launch_bounds__(MN_CC_SIGN_THREADS) void mn_cc_sign(
   const bool live = i < ngroups;
   const int p0 = live ? PX * i : 0;
   const int r = p0 / P.W, c0 = p0 - r * P.W;
-  if constexpr (CLS) { if (live) mn_cc_class_part(P, CO, i); }
+  if constexpr (CLS) {
+    if (live) {
+      if constexpr (PX == 8) mn_cc_class_part8<DT>(P, CO, i);
+      else mn_cc_class_part<DT>(P, CO, i);
+    }
+  }
   float f = 1.0f;
   double t_sum = 0.0;
   unsigned m[PX], ng[PX];                                // positive / negative out-edges per pixel
@@ -231,11 +329,13 @@ __global__ __launch_bounds__(MN_CC_SIGN_THREADS) void mn_cc_sign(
           first[g] = c0 + P.dj[k];
           rin[g] = (in1 ? 1 : 0) | (in2 ? 2 : 0);
           if (in1) rowmask |= 1u << k;
-          if (PX == 4) {
-            const float4 t = mn_ld_stream4(P.same + (size_t)k * P.N + p0);
+          if constexpr (PX == 8) {
+            mn_ld_stream8_t<DT>(P.same, (size_t)k * P.N + p0, v[g]);
+          } else if (PX == 4) {
+            const float4 t = mn_ld_stream4_t<DT>(P.same, (size_t)k * P.N + p0);
             v[g][0] = t.x; v[g][1 % PX] = t.y; v[g][2 % PX] = t.z; v[g][3 % PX] = t.w;
           } else {
-            v[g][0] = P.same[(size_t)k * P.N + p0];
+            v[g][0] = mn_ld_stream1_t<DT>(P.same, (size_t)k * P.N + p0);
           }
         }
       }
@@ -248,7 +348,7 @@ __global__ __launch_bounds__(MN_CC_SIGN_THREADS) void mn_cc_sign(
         const unsigned bit = (k0 + g < P.O) ? (1u << ((k0 + g) & 31)) : 0u;
 #pragma unroll
         for (int j = 0; j < PX; j++) {
-          const float x = (PLAIN || first[g] != INT_MIN) ? mn_cc_value<PLAIN>(P, v[g][j]) : 1.0f;
+          const float x = ((PLAIN && DT == MN_DTYPE_F32) || first[g] != INT_MIN) ? mn_cc_value<PLAIN, DT>(P, v[g][j]) : 1.0f;
           m[j] |= (x >= P.sep_hi) ? bit : 0u;
           ng[j] |= (x <= P.sep_lo) ? bit : 0u;
           f *= fmaxf(x, 1.0f - x);
@@ -267,7 +367,7 @@ __global__ __launch_bounds__(MN_CC_SIGN_THREADS) void mn_cc_sign(
           const bool second = straddle && c0 + j >= P.W;
           const bool inb = ((rin[g] >> (second ? 1 : 0)) & 1) &&
                            (unsigned)(first[g] + j - (second ? P.W : 0)) < (unsigned)P.W;
-          const float x = inb ? mn_cc_value<PLAIN>(P, v[g][j]) : 1.0f;
+          const float x = inb ? mn_cc_value<PLAIN, DT>(P, v[g][j]) : 1.0f;
           inmask[j] |= inb ? bit : 0u;
           m[j] |= (x >= P.sep_hi) ? bit : 0u;
           ng[j] |= (x <= P.sep_lo) ? bit : 0u;
@@ -275,7 +375,8 @@ __global__ __launch_bounds__(MN_CC_SIGN_THREADS) void mn_cc_sign(
         }
       }
     }
-    if (((k0 / G) & 3) == 3 || k0 + G >= P.O) {         // at most 4 * G * PX = 80 factors per product
+    constexpr int FOLD = PX == 8 ? 1 : 3;               // (8 pixels per lane: every 2 groups, the same 80 factors)
+    if (((k0 / G) & FOLD) == FOLD || k0 + G >= P.O) {   // at most 4 * G * PX = 80 factors per product
       t_sum += (double)logf(f);
       f = 1.0f;
     }
@@ -294,7 +395,12 @@ __global__ __launch_bounds__(MN_CC_SIGN_THREADS) void mn_cc_sign(
   // (edge, log-odds): two barriers and a dependent pass at the end of every block, 6.5 of 43.8 us (the sweep
   // without it: 37.3 us; a kernel that only moves the sweep's bytes: 34.3 us -- tools/stream_ceiling.hip).
   if (live) {
-    if (PX == 4) {
+    if (PX == 8) {
+      mn_st_stream(reinterpret_cast<uint4*>(bits + p0), make_uint4(m[0], m[1 % PX], m[2 % PX], m[3 % PX]));
+      mn_st_stream(reinterpret_cast<uint4*>(bits + p0) + 1, make_uint4(m[4 % PX], m[5 % PX], m[6 % PX], m[7 % PX]));
+      mn_st_stream(reinterpret_cast<uint4*>(negbits + p0), make_uint4(ng[0], ng[1 % PX], ng[2 % PX], ng[3 % PX]));
+      mn_st_stream(reinterpret_cast<uint4*>(negbits + p0) + 1, make_uint4(ng[4 % PX], ng[5 % PX], ng[6 % PX], ng[7 % PX]));
+    } else if (PX == 4) {
       mn_st_stream(reinterpret_cast<uint4*>(bits + p0), make_uint4(m[0], m[1 % PX], m[2 % PX], m[3 % PX]));
       mn_st_stream(reinterpret_cast<uint4*>(negbits + p0), make_uint4(ng[0], ng[1 % PX], ng[2 % PX], ng[3 % PX]));
     } else {
@@ -324,7 +430,7 @@ __global__ __launch_bounds__(256) void mn_cc_export_neg(ImgParams P, const unsig
   while (left) {
     const int k = __ffs((int)left) - 1;
     left &= left - 1u;
-    const float x = mn_same_value(P, P.same[(size_t)k * P.N + p]);
+    const float x = mn_same_value(P, mn_ld_same(P, k, p));
     out[(size_t)k * P.N + p] = logf(x) - mn_log1m(x);
   }
 }
@@ -789,7 +895,7 @@ __global__ __launch_bounds__(MN_CC_SUM_THREADS) void mn_cc_class_sums(
     float4 ring[MN_CC_SUM_AHEAD];
 #pragma unroll
     for (int a = 0; a < MN_CC_SUM_AHEAD; a++)
-      ring[a] = a < P.C ? *reinterpret_cast<const float4*>(P.cls + (size_t)a * P.N + 4 * (size_t)i)
+      ring[a] = a < P.C ? mn_ld_class4(P, a, 4 * i)
                         : make_float4(0.5f, 0.5f, 0.5f, 0.5f);
     for (int c0 = 0; c0 < P.C; c0 += MN_CC_SUM_AHEAD) {
 #pragma unroll
@@ -798,7 +904,7 @@ __global__ __launch_bounds__(MN_CC_SUM_THREADS) void mn_cc_class_sums(
       if (c >= P.C) break;
       float4 v = ring[a];
       if (c + MN_CC_SUM_AHEAD < P.C)
-        ring[a] = *reinterpret_cast<const float4*>(P.cls + (size_t)(c + MN_CC_SUM_AHEAD) * P.N + 4 * (size_t)i);
+        ring[a] = mn_ld_class4(P, (c + MN_CC_SUM_AHEAD), 4 * i);
       if (P.clip) { v.x = mn_clip(v.x); v.y = mn_clip(v.y); v.z = mn_clip(v.z); v.w = mn_clip(v.w); }
       if (c == 0) {
         best = v;
@@ -1069,7 +1175,7 @@ __global__ __launch_bounds__(MN_CC_SUM_THREADS) void mn_cc_sums(
       r.z = mn_cc_root_ro(S.parent, 4 * g + 2); r.w = mn_cc_root_ro(S.parent, 4 * g + 3);
       const int s0 = mn_lds_root_slot(s_root, r.x), s1 = mn_lds_root_slot(s_root, r.y);
       const int s2 = mn_lds_root_slot(s_root, r.z), s3 = mn_lds_root_slot(s_root, r.w);
-      const float4 v = *reinterpret_cast<const float4*>(P.cls + (size_t)c * P.N + 4 * (size_t)g);
+      const float4 v = mn_ld_class4(P, c, 4 * g);
       mn_cc_sums_pixelwise(P, S, s_root, s_val, lp_acc, r, c, s0, s1, s2, s3, v);
       if (c == 0) {
         const uchar4 b = *reinterpret_cast<const uchar4*>(cls0 + 4 * (size_t)g);
@@ -1214,7 +1320,7 @@ __global__ __launch_bounds__(MN_CC_CROSS_THREADS) void mn_cc_cross(
         const int k = (int)(it & 31u);
         const int p = blockIdx.x * (MN_CC_CROSS_THREADS * PX) + (int)(it >> 5);
         const int q = p + P.di[k] * P.W + P.dj[k];
-        const float x = mn_same_value(P, P.same[(size_t)k * P.N + p]);
+        const float x = mn_same_value(P, mn_ld_same(P, k, p));
         const int ru = parent[p], rv = parent[q];
         if (ru == rv) bad++;                                           // (a)
         else {

@@ -351,7 +351,7 @@ __global__ __launch_bounds__(256) void mn_x_init_records(ImgParams P, XState X) 
     return;
   }
   const int q = rr * P.W + cc;
-  const float v = mn_ref_same_value(P, P.same[(size_t)k * P.N + p]);
+  const float v = mn_ref_same_value(P, mn_ld_same(P, k, p));
   const float diff = mn_ref_log1m(v);
   const float same = mn_ref_logf(v);
   const float oml = same - diff;

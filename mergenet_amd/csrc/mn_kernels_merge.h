@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) void mn_build_from_pixels(ImgParams P, ObjStat
     const int q = rr * P.W + cc;
     const int v = S.parent[q];
     if (u == v) continue;
-    const float x = mn_same_value(P, P.same[(size_t)k * P.N + p]);
+    const float x = mn_same_value(P, mn_ld_same(P, k, p));
     const unsigned slot = mn_tab_insert(T, mn_key(u, v), mn_edge_fixed(x));
     T.touched[slot] = 1;
   }

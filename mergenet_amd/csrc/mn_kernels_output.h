@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256) void mn_verify_edges(ImgParams P, ObjState S,
           const int rr = r + P.di[k], cc = c + P.dj[k];
           if (rr >= 0 && rr < P.H && cc >= 0 && cc < P.W) {
             in[j] = true;
-            vv[j] = P.same[(size_t)k * P.N + p];
+            vv[j] = mn_ld_same(P, k, p);
             rq[j] = root[rr * P.W + cc];
           }
         }
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(MN_VERIFY4_THREADS) void mn_verify_edges4(ImgParams
           const int rr = r + P.di[k];
           if (rr >= 0 && rr < P.H) {
             first[j] = c + P.dj[k];
-            vv[j] = *reinterpret_cast<const float4*>(P.same + (size_t)k * P.N + p0);
+            vv[j] = mn_ld_same4(P, k, p0);
             const long long q0 = (long long)rr * P.W + first[j];
             if (q0 >= 0 && q0 + 3 < P.N) {
               const mn_int4_unaligned t = *reinterpret_cast<const mn_int4_unaligned*>(root + q0);

@@ -28,8 +28,19 @@ __device__ __forceinline__ void mn_lin_coord(int d, float scale, int ssize, int*
   *f = fx;
 }
 
-__global__ __launch_bounds__(256) void mn_prepare_maps(const float* __restrict__ in, int K, int Hin,
-                                                       int Win, float* __restrict__ out, int Hout,
+// float32 -> 16 bit, round to nearest even, in plain C++: binary16 by the language's conversion (one
+// v_cvt_f16_f32 in the default rounding mode, subnormal results kept), bfloat16 on the bits.
+__device__ __forceinline__ mn_u16 mn_narrow_f16(float v) { return __builtin_bit_cast(mn_u16, (_Float16)v); }
+__device__ __forceinline__ mn_u16 mn_narrow_bf16(float v) {
+  const unsigned u = __float_as_uint(v);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (mn_u16)((u >> 16) | 0x0040u);   // NaN stays NaN
+  return (mn_u16)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+
+// `in` holds elements of in_dtype, `out` of out_dtype (enum mn_dtype); the arithmetic in between is float32
+// whatever the two are.  The dtypes are uniform over the launch.
+__global__ __launch_bounds__(256) void mn_prepare_maps(const void* __restrict__ in, int in_dtype, int K, int Hin,
+                                                       int Win, void* __restrict__ out, int out_dtype, int Hout,
                                                        int Wout, int apply_sigmoid, int clip) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   const int y = blockIdx.y;
@@ -40,9 +51,9 @@ __global__ __launch_bounds__(256) void mn_prepare_maps(const float* __restrict__
   float fx, fy;
   mn_lin_coord(x, sx_scale, Win, &x0, &x1, &fx);
   mn_lin_coord(y, sy_scale, Hin, &y0, &y1, &fy);
-  const float* p = in + (size_t)k * Hin * Win;
-  float a = p[(size_t)y0 * Win + x0], b = p[(size_t)y0 * Win + x1];
-  float c = p[(size_t)y1 * Win + x0], d = p[(size_t)y1 * Win + x1];
+  const size_t p = (size_t)k * Hin * Win;
+  float a = mn_ld_map(in, in_dtype, p + (size_t)y0 * Win + x0), b = mn_ld_map(in, in_dtype, p + (size_t)y0 * Win + x1);
+  float c = mn_ld_map(in, in_dtype, p + (size_t)y1 * Win + x0), d = mn_ld_map(in, in_dtype, p + (size_t)y1 * Win + x1);
   if (apply_sigmoid) {
     a = 1.0f / (1.0f + expf(-a)); b = 1.0f / (1.0f + expf(-b));
     c = 1.0f / (1.0f + expf(-c)); d = 1.0f / (1.0f + expf(-d));
@@ -51,7 +62,9 @@ __global__ __launch_bounds__(256) void mn_prepare_maps(const float* __restrict__
   const float t1 = c * (1.0f - fx) + d * fx;
   float v = t0 * (1.0f - fy) + t1 * fy;
   if (clip) v = mn_clip(v);
-  out[((size_t)k * Hout + y) * Wout + x] = v;
+  const size_t o = ((size_t)k * Hout + y) * Wout + x;
+  if (out_dtype == MN_DTYPE_F32) static_cast<float*>(out)[o] = v;
+  else static_cast<mn_u16*>(out)[o] = out_dtype == MN_DTYPE_F16 ? mn_narrow_f16(v) : mn_narrow_bf16(v);
 }
 
 // cv2 INTER_NEAREST: source index = min(floor(dst * src/dst_size), src - 1)

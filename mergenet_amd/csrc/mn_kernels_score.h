@@ -21,7 +21,7 @@ __global__ __launch_bounds__(256) void mn_class_pass(ImgParams P, unsigned char*
     float4 best;
     int b0 = 0, b1 = 0, b2 = 0, b3 = 0;
     for (int c = 0; c < P.C; c++) {
-      float4 v = *reinterpret_cast<const float4*>(P.cls + (size_t)c * P.N + 4 * (size_t)i);
+      float4 v = mn_ld_class4(P, c, 4 * i);
       if (P.clip) { v.x = mn_clip(v.x); v.y = mn_clip(v.y); v.z = mn_clip(v.z); v.w = mn_clip(v.w); }
       float4 l;
       l.x = logf(v.x); l.y = logf(v.y); l.z = logf(v.z); l.w = logf(v.w);
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void mn_edge_pass_generic(ImgParams P, ObjStat
       const int q = rr * P.W + cc;
       if (!FIRST && matched[q]) continue;
       const int src = dir ? q : p;
-      const float v = mn_same_value(P, P.same[(size_t)k * P.N + src]);
+      const float v = mn_same_value(P, mn_ld_same(P, k, src));
       const float oml = mn_fixed_to_float(mn_edge_fixed(v));
       int mc;
       bool pos;
@@ -150,7 +150,6 @@ __global__ __launch_bounds__(256) void mn_edge_pass_fast(ImgParams P,
   const int cp = cls0[p];
 #pragma unroll
   for (int k = 0; k < OT; k++) {
-    const float* __restrict__ plane = P.same + (size_t)k * P.N;
     const int di = P.di[k], dj = P.dj[k];
 #pragma unroll
     for (int dir = 0; dir < 2; dir++) {
@@ -158,7 +157,7 @@ __global__ __launch_bounds__(256) void mn_edge_pass_fast(ImgParams P,
       const int cc = dir ? c - dj : c + dj;
       const bool ok = (unsigned)rr < (unsigned)P.H && (unsigned)cc < (unsigned)P.W;
       const unsigned q = ok ? (unsigned)(rr * P.W + cc) : (unsigned)p;
-      val[2 * k + dir] = plane[dir ? q : (unsigned)p];
+      val[2 * k + dir] = mn_ld_same(P, k, (int)(dir ? q : (unsigned)p));
       nbc[2 * k + dir] = cls0[q];
       bool live = ok;
       if (!FIRST) live = live && !matched[q];
@@ -199,7 +198,7 @@ __global__ __launch_bounds__(256) void mn_edge_pass_fast(ImgParams P,
       if (!FIRST && matched[q]) continue;
       const int cq = cls0[q];
       if (cq == cp) continue;
-      float v = P.same[(size_t)k * P.N + (dir ? q : p)];
+      float v = mn_ld_same(P, k, (dir ? q : p));
       if (CLIP) v = mn_clip(v);
       if (!(v >= vmin)) continue;
       bool pos;

@@ -34,6 +34,9 @@ MN_ERR_NO_BACKGROUND = -10
 MN_ERR_UNPROVEN = -30
 MN_DEBUG_GENERIC_EDGE_PASS, MN_DEBUG_NO_EVENTS, MN_DEBUG_NO_CORES = 1, 2, 4
 MN_DEBUG_LEAN_EVENTS, MN_DEBUG_REPLAY = 16, 32
+MN_DEBUG_SWEEP16_4PX = 256    # a 16-bit map's sweep takes 4 pixels per lane (8-byte loads) where it would take 8
+MN_DTYPE_F32, MN_DTYPE_F16, MN_DTYPE_BF16 = 0, 1, 2   # enum mn_dtype: element type of the maps (*_t entry points)
+MN_ERR_ARGUMENT = -1
 MN_PROVE_ALWAYS, MN_PROVE_BY_MODE, MN_PROVE_NEVER = 1, 0, -1   # mn_options.require_proof
 MN_TIES_DEFAULT, MN_TIES_REFERENCE, MN_TIES_LOWEST_ID = 0, 1, 2   # mn_options.tie_order
 MN_PROOF_NONE, MN_PROOF_CERTIFICATE, MN_PROOF_SEQUENTIAL, MN_PROOF_SEQUENTIAL_TIES = 0, 1, 2, 3   # mn_stats.proof
@@ -83,6 +86,8 @@ EXPORTS = ["mn_default_options", "mn_create", "mn_destroy", "mn_workspace_bytes"
            "mn_prepare_device", "mn_upsample_mask_device", "mn_rle_points_device", "mn_rle_encode_host", "mn_sameness_targets_device", "mn_instance_scores_device",
            "mn_pack_wire_device", "mn_runs_wire_words", "mn_pack_runs_device", "mn_unpack_runs_device",
            "mn_unpack_runs_batch_device",
+           "mn_segment_device_t", "mn_segment_launch_t", "mn_segment_exact_batch_t", "mn_score_device_t",
+           "mn_exact_phase_a_device_t", "mn_sweep_device_t", "mn_sweep_time_device_t", "mn_prepare_device_t",
            "mn_last_status", "mn_status_string", "mn_version"]
 
 
@@ -157,6 +162,24 @@ def load_library() -> ctypes.CDLL:
                                       ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     lib.mn_prepare_device.restype = ctypes.c_int
+    if hasattr(lib, "mn_segment_device_t"):              # (absent from older variant builds: MN_LIB)
+        # the typed forms: `int dtype` right after the group of the two map pointers
+        def typed(argtypes, at=5):
+            return list(argtypes[:at]) + [ctypes.c_int] + list(argtypes[at:])
+        lib.mn_segment_device_t.argtypes = typed(lib.mn_segment_device.argtypes)
+        lib.mn_segment_launch_t.argtypes = typed(lib.mn_segment_launch.argtypes)
+        lib.mn_segment_exact_batch_t.argtypes = typed(lib.mn_segment_exact_batch.argtypes, 6)
+        lib.mn_score_device_t.argtypes = typed(lib.mn_score_device.argtypes)
+        lib.mn_exact_phase_a_device_t.argtypes = typed(lib.mn_exact_phase_a_device.argtypes)
+        lib.mn_sweep_device_t.argtypes = typed(lib.mn_sweep_device.argtypes)
+        lib.mn_sweep_time_device_t.argtypes = typed(lib.mn_sweep_time_device.argtypes, 3)
+        lib.mn_prepare_device_t.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+        for name in ("mn_segment_device_t", "mn_segment_launch_t", "mn_segment_exact_batch_t", "mn_score_device_t",
+                     "mn_exact_phase_a_device_t", "mn_sweep_device_t", "mn_sweep_time_device_t",
+                     "mn_prepare_device_t"):
+            getattr(lib, name).restype = ctypes.c_int
     lib.mn_upsample_mask_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                             ctypes.c_void_p]
@@ -396,7 +419,13 @@ class Merger:
     ``class_probs`` [C,H,W] and ``same_probs`` [O,H,W] are float32 CUDA(HIP) tensors, e.g. the
     sigmoid outputs of the network (``utils/inference_utils.py:44,96``); ``clip_inputs=1`` fuses
     the binding's clip (c_segment.pyx:53-55) into the loads.
+
+    Both may also be ``float16`` or ``bfloat16`` (the same dtype for the two), as a network under autocast
+    writes them: the kernels read them in that width -- no float32 copy is made -- and the result is what
+    the float32 call gives on ``maps.float()`` with ``clip_inputs=1`` (16-bit maps are always clipped on load).
     """
+
+    DTYPE_NAMES = "float32, float16 or bfloat16"
 
     def __init__(self, H: int, W: int, C: int, O: int, device: Optional[int] = None):
         import torch
@@ -424,11 +453,32 @@ class Merger:
     def workspace_bytes(self) -> int:
         return int(self.lib.mn_workspace_bytes(self.handle))
 
-    def _check(self, class_probs, same_probs, offsets):
+    def _dtype(self, t) -> int:
+        """enum mn_dtype of a map tensor; ValueError for anything but the three accepted dtypes."""
         torch = self.torch
+        code = {torch.float32: MN_DTYPE_F32, torch.float16: MN_DTYPE_F16, torch.bfloat16: MN_DTYPE_BF16}.get(t.dtype)
+        if code is None:
+            raise ValueError("expected %s tensors, got %s" % (self.DTYPE_NAMES, t.dtype))
+        return code
+
+    def _typed(self, name: str, dtype: int):
+        """The entry point that takes `dtype` and the arguments that carry it: (function, (dtype,)) of the *_t
+        form, or -- float32 maps on a variant build without the typed forms (MN_LIB) -- (float function, ())."""
+        fn = getattr(self.lib, name + "_t", None)
+        if fn is not None:
+            return fn, (dtype,)
+        if dtype != MN_DTYPE_F32:
+            raise RuntimeError("%s has no %s_t: 16-bit maps need the current library" % (LIB_PATH, name))
+        return getattr(self.lib, name), ()
+
+    def _check(self, class_probs, same_probs, offsets):
         for t in (class_probs, same_probs):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 3):
-                raise ValueError("expected contiguous float32 [K,H,W] tensors on the GPU")
+            if not (t.is_cuda and t.is_contiguous() and t.dim() == 3):
+                raise ValueError("expected contiguous %s [K,H,W] tensors on the GPU" % self.DTYPE_NAMES)
+            self._dtype(t)
+            if t.dtype != class_probs.dtype:
+                raise ValueError("class and sameness maps must share one dtype (%s), got %s and %s"
+                                 % (self.DTYPE_NAMES, class_probs.dtype, same_probs.dtype))
             if t.device.index != self.device:
                 raise ValueError("tensor lives on another device than the Merger")
         C, H, W = class_probs.shape
@@ -450,13 +500,11 @@ class Merger:
         part = torch.empty((H, W), dtype=torch.int32, device=dev) if want_partition else None
         stats = MnStats()
         stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.mn_segment_device(self.handle, class_probs.data_ptr(), C,
-                                        same_probs.data_ptr(), O, W, H, C,
-                                        off.ctypes.data_as(_i32p), mask.data_ptr(),
-                                        table.data_ptr(),
-                                        part.data_ptr() if part is not None else None,
-                                        ctypes.byref(opts), ctypes.c_void_p(stream),
-                                        ctypes.byref(stats))
+        fn, dt = self._typed("mn_segment_device", self._dtype(class_probs))
+        rc = fn(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(), O, *dt, W, H, C,
+                off.ctypes.data_as(_i32p), mask.data_ptr(), table.data_ptr(),
+                part.data_ptr() if part is not None else None,
+                ctypes.byref(opts), ctypes.c_void_p(stream), ctypes.byref(stats))
         if rc != 0:
             raise MergeNetError(rc)
         return mask, table, part, stats.as_dict()
@@ -487,12 +535,11 @@ class Merger:
             table = torch.empty((H * W,), dtype=torch.int32, device=dev)
         part = torch.empty((H, W), dtype=torch.int32, device=dev) if want_partition else None
         stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.mn_segment_launch(self.handle, class_probs.data_ptr(), C,
-                                        same_probs.data_ptr(), O, W, H, C,
-                                        off.ctypes.data_as(_i32p), mask.data_ptr(),
-                                        table.data_ptr(),
-                                        part.data_ptr() if part is not None else None,
-                                        ctypes.byref(opts), ctypes.c_void_p(stream))
+        fn, dt = self._typed("mn_segment_launch", self._dtype(class_probs))
+        rc = fn(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(), O, *dt, W, H, C,
+                off.ctypes.data_as(_i32p), mask.data_ptr(), table.data_ptr(),
+                part.data_ptr() if part is not None else None,
+                ctypes.byref(opts), ctypes.c_void_p(stream))
         if rc != 0:
             raise MergeNetError(rc)
         return PendingSegment(self, mask, table, part, (class_probs, same_probs, opts))
@@ -508,12 +555,13 @@ class Merger:
         best = torch.empty((H, W), dtype=torch.int64, device=dev) if want_arrays else None
         a, b = ctypes.c_float(0), ctypes.c_float(0)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.mn_score_device(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(),
-                                      O, W, H, C, off.ctypes.data_as(_i32p), ctypes.byref(opts),
-                                      ctypes.c_void_p(stream),
-                                      cls.data_ptr() if cls is not None else None,
-                                      best.data_ptr() if best is not None else None,
-                                      ctypes.byref(a), ctypes.byref(b))
+        fn, dt = self._typed("mn_score_device", self._dtype(class_probs))
+        rc = fn(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(),
+                O, *dt, W, H, C, off.ctypes.data_as(_i32p), ctypes.byref(opts),
+                ctypes.c_void_p(stream),
+                cls.data_ptr() if cls is not None else None,
+                best.data_ptr() if best is not None else None,
+                ctypes.byref(a), ctypes.byref(b))
         if rc != 0:
             raise MergeNetError(rc)
         if want_arrays:
@@ -536,10 +584,11 @@ class Merger:
         logsum = ctypes.c_double(0.0)
         info = (ctypes.c_int * 3)()
         stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.mn_sweep_device(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(), O, W, H, C,
-                                      off.ctypes.data_as(_i32p), ctypes.byref(opts), ctypes.c_void_p(stream),
-                                      bits.data_ptr(), neg.data_ptr(), cls.data_ptr(), gsum.data_ptr(),
-                                      ctypes.byref(logsum), info)
+        fn, dt = self._typed("mn_sweep_device", self._dtype(class_probs))
+        rc = fn(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(), O, *dt, W, H, C,
+                off.ctypes.data_as(_i32p), ctypes.byref(opts), ctypes.c_void_p(stream),
+                bits.data_ptr(), neg.data_ptr(), cls.data_ptr(), gsum.data_ptr(),
+                ctypes.byref(logsum), info)
         if rc != 0:
             raise MergeNetError(rc)
         fused = bool(info[1])
@@ -549,16 +598,20 @@ class Merger:
     def sweep_time(self, inputs: Sequence, offsets, opts: Optional[MnOptions] = None, reps: int = 400) -> float:
         """Tuning aid (``mn_sweep_time_device``): microseconds per launch of the sweep alone, back to back over
         the (class_probs, same_probs) pairs of ``inputs`` in rotation."""
-        C, H, W, O, off = self._check(inputs[0][0], inputs[0][1], offsets)
+        for a, b in inputs:
+            C, H, W, O, off = self._check(a, b, offsets)
+            if a.dtype != inputs[0][0].dtype or a.shape != inputs[0][0].shape:
+                raise ValueError("the input sets of a sweep timing share one dtype and shape")
         opts = opts if opts is not None else default_options()
         n = len(inputs)
         vp = ctypes.c_void_p * n
         out = ctypes.c_float(0)
         stream = self.torch.cuda.current_stream(inputs[0][0].device).cuda_stream
-        rc = self.lib.mn_sweep_time_device(self.handle, vp(*[a.data_ptr() for a, _ in inputs]),
-                                           vp(*[b.data_ptr() for _, b in inputs]), n, C, O, W, H, C,
-                                           off.ctypes.data_as(_i32p), ctypes.byref(opts), ctypes.c_void_p(stream),
-                                           int(reps), ctypes.byref(out))
+        fn, dt = self._typed("mn_sweep_time_device", self._dtype(inputs[0][0]))
+        rc = fn(self.handle, vp(*[a.data_ptr() for a, _ in inputs]),
+                vp(*[b.data_ptr() for _, b in inputs]), *dt, n, C, O, W, H, C,
+                off.ctypes.data_as(_i32p), ctypes.byref(opts), ctypes.c_void_p(stream),
+                int(reps), ctypes.byref(out))
         if rc != 0:
             raise MergeNetError(rc)
         return out.value
@@ -574,28 +627,41 @@ class Merger:
         oml = torch.empty((O, H, W), dtype=torch.float32, device=dev)
         prio = torch.empty((O, H, W), dtype=torch.float32, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.mn_exact_phase_a_device(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(),
-                                              O, W, H, C, off.ctypes.data_as(_i32p), ctypes.byref(opts),
-                                              ctypes.c_void_p(stream), cls.data_ptr(), oml.data_ptr(),
-                                              prio.data_ptr())
+        fn, dt = self._typed("mn_exact_phase_a_device", self._dtype(class_probs))
+        rc = fn(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(),
+                O, *dt, W, H, C, off.ctypes.data_as(_i32p), ctypes.byref(opts),
+                ctypes.c_void_p(stream), cls.data_ptr(), oml.data_ptr(),
+                prio.data_ptr())
         if rc != 0:
             raise MergeNetError(rc)
         return cls, oml, prio
 
     def prepare(self, maps, out_height: int, out_width: int, apply_sigmoid: bool = False,
-                clip: bool = True):
+                clip: bool = True, out_dtype=None):
         """Network output -> merger input on the device: optional sigmoid, bilinear resize with
         cv2.resize coordinates (egs/cityscape/local/segment.py:115-123) and clip, one pass.
-        maps: float32 [K, Hin, Win] tensor on this GPU.  Returns float32 [K, out_height, out_width]."""
+        maps: float32, float16 or bfloat16 [K, Hin, Win] tensor on this GPU.  Returns [K, out_height, out_width]
+        in float32, or in ``out_dtype`` (torch.float16 / torch.bfloat16): the float32 value the kernel computed,
+        rounded to nearest even."""
         torch = self.torch
-        if not (maps.is_cuda and maps.dtype == torch.float32 and maps.is_contiguous() and maps.dim() == 3):
-            raise ValueError("expected a contiguous float32 [K,H,W] tensor on the GPU")
+        if not (maps.is_cuda and maps.is_contiguous() and maps.dim() == 3):
+            raise ValueError("expected a contiguous %s [K,H,W] tensor on the GPU" % self.DTYPE_NAMES)
+        in_code = self._dtype(maps)
+        out_dtype = torch.float32 if out_dtype is None else out_dtype
+        out_code = {torch.float32: MN_DTYPE_F32, torch.float16: MN_DTYPE_F16, torch.bfloat16: MN_DTYPE_BF16}.get(out_dtype)
+        if out_code is None:
+            raise ValueError("out_dtype: %s, got %s" % (self.DTYPE_NAMES, out_dtype))
         K, Hin, Win = maps.shape
-        out = torch.empty((K, out_height, out_width), dtype=torch.float32, device=maps.device)
+        out = torch.empty((K, out_height, out_width), dtype=out_dtype, device=maps.device)
         stream = torch.cuda.current_stream(maps.device).cuda_stream
-        rc = self.lib.mn_prepare_device(self.handle, maps.data_ptr(), K, Hin, Win, out.data_ptr(),
-                                        out_height, out_width, int(apply_sigmoid), int(clip),
-                                        ctypes.c_void_p(stream))
+        if in_code == MN_DTYPE_F32 and out_code == MN_DTYPE_F32 and not hasattr(self.lib, "mn_prepare_device_t"):
+            rc = self.lib.mn_prepare_device(self.handle, maps.data_ptr(), K, Hin, Win, out.data_ptr(),
+                                            out_height, out_width, int(apply_sigmoid), int(clip),
+                                            ctypes.c_void_p(stream))      # (a variant build without the typed forms)
+        else:
+            rc = self.lib.mn_prepare_device_t(self.handle, maps.data_ptr(), in_code, K, Hin, Win, out.data_ptr(),
+                                              out_code, out_height, out_width, int(apply_sigmoid), int(clip),
+                                              ctypes.c_void_p(stream))
         if rc != 0:
             raise MergeNetError(rc)
         return out
@@ -742,9 +808,9 @@ class ExactBatch:
         shape = None
         for cp, sp in zip(class_probs, same_probs):
             C, H, W, O, off = self.mergers[0]._check(cp, sp, offsets)
-            if shape is not None and shape != (C, H, W, O):
-                raise ValueError("the images of a batch have one shape")
-            shape = (C, H, W, O)
+            if shape is not None and shape != (C, H, W, O, cp.dtype):
+                raise ValueError("the images of a batch have one shape and one dtype")
+            shape = (C, H, W, O, cp.dtype)
         opts = opts if opts is not None else default_options()
         dev = class_probs[0].device
         masks = [torch.empty((H, W), dtype=torch.int32, device=dev) for _ in range(n)]
@@ -753,9 +819,10 @@ class ExactBatch:
         vp = ctypes.c_void_p * n
         stats = (MnStats * n)()
         stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.mn_segment_exact_batch(
+        fn, dt = self.mergers[0]._typed("mn_segment_exact_batch", self.mergers[0]._dtype(class_probs[0]))
+        rc = fn(
             vp(*[m.handle for m in self.mergers[:n]]), n, vp(*[t.data_ptr() for t in class_probs]), C,
-            vp(*[t.data_ptr() for t in same_probs]), O, W, H, C, off.ctypes.data_as(_i32p),
+            vp(*[t.data_ptr() for t in same_probs]), O, *dt, W, H, C, off.ctypes.data_as(_i32p),
             vp(*[t.data_ptr() for t in masks]), vp(*[t.data_ptr() for t in tables]),
             vp(*[t.data_ptr() for t in parts]) if parts is not None else None,
             ctypes.byref(opts), ctypes.c_void_p(stream), stats)
