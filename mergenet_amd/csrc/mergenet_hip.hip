@@ -46,6 +46,31 @@ static thread_local int g_last_status = MN_OK;
     }                                                                                     \
   } while (0)
 
+// Host scratch of n zeroed plain elements that every return path frees; !ok(): no memory (MN_ERR_INTERNAL to the caller).
+template <typename T>
+struct HostBuf {
+  T* p;
+  explicit HostBuf(size_t n) : p(static_cast<T*>(calloc(n ? n : 1, sizeof(T)))) {}
+  ~HostBuf() { free(p); }
+  HostBuf(const HostBuf&) = delete;
+  bool ok() const { return p != nullptr; }
+  operator T*() const { return p; }
+};
+
+// One image call as an entry point received it.  The entry sets the maps, the shape and the outputs; image_call the rest.
+struct ImageCall {
+  const void *d_class, *d_adj;   // maps, elements of `dtype`
+  int dtype;                     // enum mn_dtype
+  int class_dim, offset_dim, W, H, num_classes;
+  int *d_mask, *d_objcls, *d_part;
+  hipStream_t stream;
+  bool has_offsets;              // the caller gave an offset list (copied only when offset_dim is in range)
+  int offs[2 * MN_MAX_OFFSETS];
+  mn_options opts;               // resolved: the defaults when the caller gave none
+};
+
+struct Queued { int mode, rounds, finish_limit, N; long long R0; bool speculate, want_cert; };
+
 struct mn_context {
   int device;
   int maxH, maxW, maxC, maxO;
@@ -55,7 +80,6 @@ struct mn_context {
   size_t gen_bytes;
   size_t cc_cap;          // table capacity used by the last component contraction
   int debug_flags;        // mn_options.debug_flags of the call in progress
-  int dtype;              // enum mn_dtype of the maps of the call in progress (set by every *_t entry point)
   size_t bytes;
   // objects
   unsigned char *ocls, *cls0, *lpvalid, *matched, *pruned;
@@ -105,15 +129,8 @@ struct mn_context {
   struct Pending {
     int active;            // 0 none, 1 kernels queued and verdict unread, 2 finished in launch
     int rc;
-    int mode, rounds, finish_limit, N;
-    long long R0;
-    bool speculate, want_cert;
-    const void *d_class, *d_adj;   // elements of mn_context::dtype
-    int class_dim, offset_dim, W, H, num_classes;
-    int offs[2 * MN_MAX_OFFSETS];
-    int *d_mask, *d_objcls, *d_part;
-    mn_options opts;
-    void* stream;
+    Queued queued;         // what the queued attempt leaves for segment_read_back
+    ImageCall call;
     mn_stats stats;
   } pend;
   hipEvent_t ev_done;
@@ -130,9 +147,7 @@ struct mn_context {
     hipGraph_t gA, gB;
     hipGraphExec_t eA, eB;
     hipStream_t cap;       // capture happens here (the caller's stream may be the null stream, which cannot capture)
-    int finish_limit;
-    long long R0;
-    bool want_cert;
+    Queued queued;         // of the attempt that recorded the graphs
   } replay;
   hipStream_t side;       // the single-workgroup tail of an image runs here, beside the next image's sweeps
   hipEvent_t ev_fork;
@@ -520,6 +535,14 @@ static int ensure_fast(mn_context* c) {
   return MN_OK;
 }
 
+static void drop_replay_graphs(mn_context::Replay& rp) {
+  if (rp.eA) { (void)hipGraphExecDestroy(rp.eA); rp.eA = nullptr; }
+  if (rp.eB) { (void)hipGraphExecDestroy(rp.eB); rp.eB = nullptr; }
+  if (rp.gA) { (void)hipGraphDestroy(rp.gA); rp.gA = nullptr; }
+  if (rp.gB) { (void)hipGraphDestroy(rp.gB); rp.gB = nullptr; }
+  rp.state = 0;
+}
+
 // The general rounds (and the small-list exact mode) hold a record per pixel edge: their lists and table
 // are allocated when first needed.  Recorded replay graphs hold the old pointers and are dropped.
 static int ensure_general(mn_context* c) {
@@ -530,24 +553,20 @@ static int ensure_general(mn_context* c) {
   c->cap = c->cap_full;
   c->gen_ready = 1;
   c->cc_clean = 0;
-  mn_context::Replay& rp = c->replay;
-  if (rp.eA) { (void)hipGraphExecDestroy(rp.eA); rp.eA = nullptr; }
-  if (rp.eB) { (void)hipGraphExecDestroy(rp.eB); rp.eB = nullptr; }
-  if (rp.gA) { (void)hipGraphDestroy(rp.gA); rp.gA = nullptr; }
-  if (rp.gB) { (void)hipGraphDestroy(rp.gB); rp.gB = nullptr; }
-  rp.state = 0;
+  drop_replay_graphs(c->replay);
   return MN_OK;
 }
 
 // ---- argument checking shared by the entry points ---------------------------------------------
-static int check_args(const mn_context* c, int class_dim, int offset_dim, int W, int H,
-                      int num_classes, const int* offs, const mn_options* o) {
-  if (!c || !offs || !o) return MN_ERR_ARGUMENT;
-  if (W <= 0 || H <= 0 || num_classes <= 0 || offset_dim <= 0 || class_dim < num_classes)
+static int check_args(const mn_context* c, const ImageCall& call) {
+  const int W = call.W, H = call.H, num_classes = call.num_classes, offset_dim = call.offset_dim;
+  const int* offs = call.offs;
+  if (!c || !call.has_offsets) return MN_ERR_ARGUMENT;
+  if (W <= 0 || H <= 0 || num_classes <= 0 || offset_dim <= 0 || call.class_dim < num_classes)
     return MN_ERR_ARGUMENT;
   if (num_classes > MN_MAX_CLASSES || offset_dim > MN_MAX_OFFSETS) return MN_ERR_ARGUMENT;
   if ((size_t)W * H > c->N || num_classes > c->maxC || offset_dim > c->maxO) return MN_ERR_CAPACITY;
-  if (o->variant != MN_VARIANT_CSEGMENT && o->variant != MN_VARIANT_PYSEGMENTER)
+  if (call.opts.variant != MN_VARIANT_CSEGMENT && call.opts.variant != MN_VARIANT_PYSEGMENTER)
     return MN_ERR_ARGUMENT;
   for (int a = 0; a < offset_dim; a++)
     for (int b = 0; b < offset_dim; b++) {
@@ -558,22 +577,30 @@ static int check_args(const mn_context* c, int class_dim, int offset_dim, int W,
   return MN_OK;
 }
 
-static inline bool dtype_ok(int dtype) {
-  return dtype == MN_DTYPE_F32 || dtype == MN_DTYPE_F16 || dtype == MN_DTYPE_BF16;
+static inline bool dtype_ok(int dtype) { return dtype == MN_DTYPE_F32 || dtype == MN_DTYPE_F16 || dtype == MN_DTYPE_BF16; }
+
+// A null offset list is only noted (check_args rejects the call before `offs` is read), as is an offset_dim out of range.
+static void image_call(ImageCall* call, const int* offset_list, const mn_options* opts, void* stream) {
+  call->has_offsets = offset_list != nullptr;
+  if (offset_list && call->offset_dim > 0 && call->offset_dim <= MN_MAX_OFFSETS)
+    memcpy(call->offs, offset_list, sizeof(int) * 2 * (size_t)call->offset_dim);
+  call->stream = static_cast<hipStream_t>(stream);
+  if (opts) call->opts = *opts; else mn_default_options(&call->opts);
 }
 
-static void fill_params(ImgParams* P, const void* d_class, const void* d_same, int dtype, int offset_dim,
-                        int W, int H, int num_classes, const int* offs, const mn_options* o) {
+static void fill_params(ImgParams* P, const ImageCall& call) {
+  const int dtype = call.dtype, offset_dim = call.offset_dim, W = call.W, H = call.H;
+  const mn_options* o = &call.opts;
   memset(P, 0, sizeof(*P));
-  P->H = H; P->W = W; P->N = W * H; P->C = num_classes; P->O = offset_dim;
+  P->H = H; P->W = W; P->N = W * H; P->C = call.num_classes; P->O = offset_dim;
   P->sdb = o->same_different_bias; P->omf = o->object_merge_factor; P->bias = o->merge_logprob_bias;
   // a 16-bit map cannot hold 1 - 2^-23 and a saturated sigmoid is exactly 1.0 in it: always clipped on load
   P->variant = o->variant; P->clip = (o->clip_inputs || dtype != MN_DTYPE_F32) ? 1 : 0;
   P->dtype = dtype;
-  P->cls = d_class; P->same = d_same;
+  P->cls = call.d_class; P->same = call.d_adj;
   P->djmin = 0; P->djmax = 0;
   for (int k = 0; k < offset_dim; k++) {
-    P->di[k] = offs[2 * k]; P->dj[k] = offs[2 * k + 1];
+    P->di[k] = call.offs[2 * k]; P->dj[k] = call.offs[2 * k + 1];
     if (P->dj[k] < P->djmin) P->djmin = P->dj[k];
     if (P->dj[k] > P->djmax) P->djmax = P->dj[k];
   }
@@ -606,10 +633,24 @@ static void fill_params(ImgParams* P, const void* d_class, const void* d_same, i
   }
 }
 
-static long long count_records(int W, int H, int offset_dim, const int* offs) {
+// What the six entry points that take an image begin with: the call is checked (`entry_ok`: what the entry checks
+// of its own arguments, reported after the shared checks as MN_ERR_ARGUMENT), the device selected and the kernel
+// parameters filled.  `stats`, where the entry has some, is reset once the verdict of the checks is known.  (New for
+// segment_attempt and the replay branch: the checks of the maps and the element type; their callers make them first.)
+static int begin_call(mn_context* c, const ImageCall& call, bool entry_ok, mn_stats* stats, ImgParams* P) {
+  int rc = check_args(c, call);
+  if (rc == MN_OK && (!call.d_class || !call.d_adj || !dtype_ok(call.dtype) || !entry_ok)) rc = MN_ERR_ARGUMENT;
+  if (stats) { memset(stats, 0, sizeof(*stats)); stats->status = rc; stats->total_logprob = NAN; }
+  if (rc != MN_OK) { g_last_status = rc; return rc; }
+  MN_HIP(hipSetDevice(c->device));
+  fill_params(P, call);
+  return MN_OK;
+}
+
+static long long count_records(const ImageCall& call) {
   long long r = 0;
-  for (int k = 0; k < offset_dim; k++) {
-    const long long hh = H - abs(offs[2 * k]), ww = W - abs(offs[2 * k + 1]);
+  for (int k = 0; k < call.offset_dim; k++) {
+    const long long hh = call.H - abs(call.offs[2 * k]), ww = call.W - abs(call.offs[2 * k + 1]);
     if (hh > 0 && ww > 0) r += hh * ww;
   }
   return r;
@@ -718,8 +759,9 @@ static int read_counters(mn_context* c, hipStream_t st) {
   return MN_OK;
 }
 
+// `src`: the list of the round before (Rsrc records); null: the records come from the pixel graph
 static int build_list(mn_context* c, const ImgParams& P, hipStream_t st, size_t cap, RecList L,
-                      bool from_pixels, RecList src, int Rsrc, int* Rout, bool fresh_all = false) {
+                      const RecList* src, int Rsrc, int* Rout) {
   ObjState S = obj_state(c);
   HashTab T = c->T;
   T.mask = (unsigned)(cap - 1);
@@ -734,11 +776,11 @@ static int build_list(mn_context* c, const ImgParams& P, hipStream_t st, size_t 
   f.add(c->ball, (size_t)P.N * sizeof(u64), 0);
   f.add(c->gmax, 64 * sizeof(unsigned), 0);
   f.launch(st);
-  if (from_pixels)
+  if (!src)
     hipLaunchKernelGGL(mn_build_from_pixels, dim3(grid_for(P.N, 256)), dim3(256), 0, st, P, S, T);
   else
-    hipLaunchKernelGGL(mn_rebuild, dim3(grid_for(Rsrc, MN_REBUILD_ITEMS)), dim3(256), 0, st, S, src,
-                       Rsrc, (const unsigned char*)c->matched, T, L, c->ball, c->gmax, c->cnt, fresh_all ? 1 : 0);
+    hipLaunchKernelGGL(mn_rebuild, dim3(grid_for(Rsrc, MN_REBUILD_ITEMS)), dim3(256), 0, st, S, *src,
+                       Rsrc, (const unsigned char*)c->matched, T, L, c->ball, c->gmax, c->cnt, /* fresh_all */ 0);
   if (cap <= (1u << 16))
     hipLaunchKernelGGL(mn_compact<1>, dim3(grid_for(cap, 256)), dim3(256), 0, st, P, S, T, L,
                        c->ball, c->gmax, c->cnt, (const int*)nullptr, (int*)nullptr);
@@ -835,12 +877,21 @@ static void launch_cc_hook(mn_context* c, const ImgParams& P, hipStream_t st, un
                        c->parent, kmask);
 }
 
-// Component contraction (mn_kernels_cc.h).  With `wait`: returns 0 when the input is
+enum CcUse {          // the four uses of the component contraction
+  CC_WAITED,          // ordinary components attempt: compacted with the best-record slots, verdict waited for
+  CC_QUEUED_COMPACT,  // speculative attempt that ends in the LDS finisher: compacted, nothing waited for
+  CC_QUEUED_TAIL,     // speculative attempt that ends in mn_cc_tail: forks to the side stream before the sums
+  CC_CORES            // first step of the general rounds, on the edges between clean pixels
+};
+
+// Component contraction (mn_kernels_cc.h).  CC_WAITED: returns 0 when the input is
 // sign-separable (object state + list of records between components ready, count in h_cnt), 1
-// when it is not (caller falls back), < 0 on error.  Without: everything is queued, 0 is returned
+// when it is not (caller falls back), < 0 on error.  The others: everything is queued, 0 is returned
 // and the verdict is read by the caller at the end.
-static int run_components(mn_context* c, const ImgParams& P, hipStream_t& st, bool wait, bool with_ball,
-                          bool with_compact, bool fork_before_sums, bool cores = false) {
+static int run_components(mn_context* c, const ImgParams& P, hipStream_t& st, CcUse use) {
+  const bool wait = use == CC_WAITED, with_ball = use == CC_WAITED;
+  const bool with_compact = use == CC_WAITED || use == CC_QUEUED_COMPACT;
+  const bool fork_before_sums = use == CC_QUEUED_TAIL, cores = use == CC_CORES;
   const int N = P.N;
   ObjState S = obj_state(c);
   const dim3 b(256);
@@ -1051,8 +1102,8 @@ static int exact_loop(mn_context** cs, int n, const ImgParams* Ps, hipStream_t s
   size_t lds = 0;
   long long max_total = 0;
   {
-    XState* hx = static_cast<XState*>(malloc((size_t)n * sizeof(XState)));
-    if (!hx) return MN_ERR_INTERNAL;
+    HostBuf<XState> hx((size_t)n);
+    if (!hx.ok()) return MN_ERR_INTERNAL;
     for (int i = 0; i < n; i++) {
       const XState& X = cs[i]->xw.X;
       hx[i] = X;
@@ -1065,8 +1116,7 @@ static int exact_loop(mn_context** cs, int n, const ImgParams* Ps, hipStream_t s
     }
     hipError_t e1 = hipMemcpyAsync(w0.d_P, Ps, (size_t)n * sizeof(ImgParams), hipMemcpyHostToDevice, st);
     hipError_t e2 = hipMemcpyAsync(w0.d_X, hx, (size_t)n * sizeof(XState), hipMemcpyHostToDevice, st);
-    hipError_t e3 = hipStreamSynchronize(st);
-    free(hx);
+    hipError_t e3 = hipStreamSynchronize(st);     // (before any return: a copy queued ahead of a failed call still reads host scratch)
     MN_HIP(e1); MN_HIP(e2); MN_HIP(e3);
   }
   if (!w0.lds_ready) {
@@ -1124,11 +1174,8 @@ static int exact_loop(mn_context** cs, int n, const ImgParams* Ps, hipStream_t s
 
 // Set-up and loop of a batch; an image whose workspace was too small is repeated with a larger one.
 static int exact_run(mn_context** cs, int n, const ImgParams* Ps, hipStream_t st) {
-  mn_context** sub = static_cast<mn_context**>(malloc((size_t)n * sizeof(mn_context*)));
-  ImgParams* subP = static_cast<ImgParams*>(malloc((size_t)n * sizeof(ImgParams)));
-  unsigned char* full = static_cast<unsigned char*>(malloc((size_t)n));
-  int rc = (sub && subP && full) ? MN_OK : MN_ERR_INTERNAL;
-  int m = n;
+  HostBuf<mn_context*> sub((size_t)n); HostBuf<ImgParams> subP((size_t)n); HostBuf<unsigned char> full((size_t)n);
+  int rc = (sub.ok() && subP.ok() && full.ok()) ? MN_OK : MN_ERR_INTERNAL, m = n;
   for (int i = 0; i < n && rc == MN_OK; i++) { sub[i] = cs[i]; subP[i] = Ps[i]; }
   for (int attempt = 0; rc == MN_OK && m > 0; attempt++) {
     if (attempt == 8) { rc = MN_ERR_CAPACITY; break; }
@@ -1148,7 +1195,6 @@ static int exact_run(mn_context** cs, int n, const ImgParams* Ps, hipStream_t st
     }
     m = k;
   }
-  free(sub); free(subP); free(full);
   return rc;
 }
 
@@ -1289,8 +1335,8 @@ static int ro_loop(mn_context** cs, int n, const ImgParams* Ps, hipStream_t st, 
     MN_HIP(hipMalloc(reinterpret_cast<void**>(&w0.d_S), (size_t)n * sizeof(RoState)));
     w0.batch_cap = n;
   }
-  RoState* hs = static_cast<RoState*>(malloc((size_t)n * sizeof(RoState)));
-  if (!hs) return MN_ERR_INTERNAL;
+  HostBuf<RoState> hs((size_t)n);
+  if (!hs.ok()) return MN_ERR_INTERNAL;
   long long max_pops = 0;
   for (int i = 0; i < n; i++) {
     hs[i] = cs[i]->rw.S;
@@ -1299,10 +1345,8 @@ static int ro_loop(mn_context** cs, int n, const ImgParams* Ps, hipStream_t st, 
     const long long mp = 64LL * hs[i].NL + 65536;
     if (mp > max_pops) max_pops = mp;
   }
-  hipError_t e1 = hipMemcpyAsync(w0.d_S, hs, (size_t)n * sizeof(RoState), hipMemcpyHostToDevice, st);
-  hipError_t e2 = hipStreamSynchronize(st);
-  free(hs);
-  MN_HIP(e1); MN_HIP(e2);
+  MN_HIP(hipMemcpyAsync(w0.d_S, hs, (size_t)n * sizeof(RoState), hipMemcpyHostToDevice, st));
+  MN_HIP(hipStreamSynchronize(st));
   long long per_launch = 1LL << 20;                  // pops per launch (MN_X_BUDGET: tests of the relaunch)
   if (const char* e = getenv("MN_X_BUDGET")) { const long long v = atoll(e); if (v > 0) per_launch = v; }
   for (long long it = 0; it < (1 << 20); it++) {
@@ -1358,11 +1402,9 @@ static int ro_finish(mn_context* c, const ImgParams& P, hipStream_t st) {
 
 // set-up, loop and hand-over of a batch; an image whose workspace was too small is repeated with a larger one
 static int run_reforder_batch(mn_context** cs, int n, const ImgParams* Ps, hipStream_t st) {
-  mn_context** sub = static_cast<mn_context**>(malloc((size_t)n * sizeof(mn_context*)));
-  ImgParams* subP = static_cast<ImgParams*>(malloc((size_t)n * sizeof(ImgParams)));
-  unsigned char* full = static_cast<unsigned char*>(malloc((size_t)n));
-  int rc = (sub && subP && full) ? MN_OK : MN_ERR_INTERNAL;
-  int m = n;
+  HostBuf<mn_context*> sub((size_t)n), run((size_t)n); HostBuf<ImgParams> subP((size_t)n), runP((size_t)n);
+  HostBuf<unsigned char> full((size_t)n), f2((size_t)n); HostBuf<int> idx((size_t)n);
+  int rc = (sub.ok() && subP.ok() && full.ok() && run.ok() && runP.ok() && f2.ok() && idx.ok()) ? MN_OK : MN_ERR_INTERNAL, m = n;
   for (int i = 0; i < n && rc == MN_OK; i++) { sub[i] = cs[i]; subP[i] = Ps[i]; }
   for (int attempt = 0; rc == MN_OK && m > 0; attempt++) {
     if (attempt == 8) { rc = MN_ERR_CAPACITY; break; }
@@ -1371,24 +1413,18 @@ static int run_reforder_batch(mn_context** cs, int n, const ImgParams* Ps, hipSt
     MN_HIP(hipStreamSynchronize(st));
     memset(full, 0, (size_t)m);
     int ready = 0;                 // images whose maps were built: they go through the loop now
-    mn_context** run = static_cast<mn_context**>(malloc((size_t)m * sizeof(mn_context*)));
-    ImgParams* runP = static_cast<ImgParams*>(malloc((size_t)m * sizeof(ImgParams)));
-    int* idx = static_cast<int*>(malloc((size_t)m * sizeof(int)));
-    if (!run || !runP || !idx) { free(run); free(runP); free(idx); rc = MN_ERR_INTERNAL; break; }
     for (int i = 0; i < m; i++) {
       if (sub[i]->rw.h_ctl[7] != 0) { full[i] = MN_RO_ARENA_FULL; continue; }
       run[ready] = sub[i]; runP[ready] = subP[i]; idx[ready] = i; ready++;
     }
     if (ready > 0) {
-      unsigned char* f2 = static_cast<unsigned char*>(calloc((size_t)ready, 1));
-      rc = f2 ? ro_loop(run, ready, runP, st, f2) : MN_ERR_INTERNAL;
+      memset(f2, 0, (size_t)ready);
+      rc = ro_loop(run, ready, runP, st, f2);
       for (int j = 0; j < ready && rc == MN_OK; j++) {
         if (f2[j]) full[idx[j]] = f2[j];
         else rc = ro_finish(run[j], runP[j], st);
       }
-      free(f2);
     }
-    free(run); free(runP); free(idx);
     if (rc != MN_OK) break;
     int k = 0;
     for (int i = 0; i < m; i++) {
@@ -1399,13 +1435,7 @@ static int run_reforder_batch(mn_context** cs, int n, const ImgParams* Ps, hipSt
     }
     m = k;
   }
-  free(sub); free(subP); free(full);
   return rc;
-}
-
-static int run_reforder(mn_context* c, const ImgParams& P, hipStream_t st) {
-  mn_context* one[1] = {c};
-  return run_reforder_batch(one, 1, &P, st);
 }
 
 // Did the run leave anything to the engine's own rule among bit-equal priorities?  Tied pops whose choices touched
@@ -1415,36 +1445,44 @@ static bool x_ties_unresolved(const XCtl* h) {
   return h->tied_steps > 0 && (h->ttrack == 0 || h->tied_conflicts > 0);
 }
 
+// Images redone in the reference's order among equals.  `keep_ties`: they have been through the exact engine, and on
+// success its tie counters -- what the exact engine met -- are put back over the zeros that ro_finish leaves.
+static int redo_in_reference_order(mn_context** cs, int n, const ImgParams* Ps, hipStream_t st, bool keep_ties) {
+  HostBuf<XCtl> saved((size_t)n);
+  if (!saved.ok()) return MN_ERR_INTERNAL;
+  for (int i = 0; i < n && keep_ties; i++) saved[i] = *cs[i]->xw.h_ctl;
+  const int rc = run_reforder_batch(cs, n, Ps, st);
+  for (int i = 0; i < n && keep_ties && rc == MN_OK; i++) {
+    XCtl* h = cs[i]->xw.h_ctl;
+    h->tied_steps = saved[i].tied_steps; h->tied_merges = saved[i].tied_merges;
+    h->tied_conflicts = saved[i].tied_conflicts; h->ttrack = saved[i].ttrack;
+  }
+  return rc;
+}
+
 // set-up, loop and hand-over of ONE image; in a batch (mn_segment_exact_batch) set-up and loop have run for
 // all images together and only the hand-over is left (xw.prerun)
 static int run_exact_engine(mn_context* c, const ImgParams& P, hipStream_t st) {
   int rc = MN_OK;
+  mn_context* one[1] = {c};
   c->tie_used = MN_TIES_LOWEST_ID;
   const bool ref_possible = P.variant == MN_VARIANT_CSEGMENT;       // (the Python variant's heapq / dict order is not restated)
   if (c->tie_ref == MN_TIES_REFERENCE && !c->xw.prerun) {
     if (!ref_possible) return MN_ERR_ARGUMENT;
-    rc = run_reforder(c, P, st);
-    if (rc != MN_OK) return rc;
+    if ((rc = redo_in_reference_order(one, 1, &P, st, false)) != MN_OK) return rc;
     c->tie_used = MN_TIES_REFERENCE;
     MN_HIP(hipEventRecord(c->ev[1], st));
     MN_HIP(hipEventRecord(c->ev[2], st));
   } else if (!c->xw.prerun) {
-    mn_context* one[1] = {c};
-    rc = exact_run(one, 1, &P, st);
-    if (rc != MN_OK) return rc;
+    if ((rc = exact_run(one, 1, &P, st)) != MN_OK) return rc;
     // MN_TIES_DEFAULT: tied pops are the only place where the engine's order and the reference's can part; a
     // small image that had some is redone the reference's way
     long long limit = MN_TIE_LIMIT_RECORDS;
     if (const char* e = getenv("MN_TIE_LIMIT")) limit = atoll(e);
     if (c->tie_ref == MN_TIES_DEFAULT && ref_possible && x_ties_unresolved(c->xw.h_ctl) &&
         (long long)P.N * P.O <= limit) {
-      const long long ts = c->xw.h_ctl->tied_steps, tm = c->xw.h_ctl->tied_merges, tc = c->xw.h_ctl->tied_conflicts;
-      const int tt = c->xw.h_ctl->ttrack;
-      rc = run_reforder(c, P, st);
-      if (rc != MN_OK) return rc;
+      if ((rc = redo_in_reference_order(one, 1, &P, st, true)) != MN_OK) return rc;
       c->tie_used = MN_TIES_REFERENCE;
-      c->xw.h_ctl->tied_steps = ts; c->xw.h_ctl->tied_merges = tm;     // (what the exact engine met)
-      c->xw.h_ctl->tied_conflicts = tc; c->xw.h_ctl->ttrack = tt;
     }
   } else {
     // (set-up and loop have run as part of a batch; prerun == 2: the reference-order loop too)
@@ -1460,20 +1498,24 @@ static int run_exact_engine(mn_context* c, const ImgParams& P, hipStream_t st) {
 #define MN_RETRY_WAIT 1002     /* more records than the finisher takes: redo, waiting for the count */
 #define MN_PENDING 1003        /* deferred: everything queued, mn_segment_finish reads the verdict   */
 
-// One attempt.  `speculate`: in components mode the host does not wait for the record count and
-// the separability verdict in the middle of the image; finisher and output are queued behind the
-// contraction and everything is read at the one synchronisation at the end.  Sign-separable maps
-// with few components -- the case the mode exists for -- are done then; otherwise a verdict above
-// is returned and mn_segment_device runs the attempt again on the ordinary path.
+// The options under which "a record inside a component scores > bias, one between components < bias" can hold:
+// gain = omf * log-odds with omf at least `min_omf`; bias >= 0 (csegment) so that intra-component records
+// (> bias) are always visible and ahead of cross records (< bias); pysegmenter divides (gain + bias) by n1*n2,
+// which only separates the two kinds when bias == 0.  The contraction (components mode, cores) asks for omf >= 1e-20,
+// the certificate for any omf > 0 (it passes 0 and adds the strict test).  Why the two differ is not recorded: carry-over.
+static bool separable_options(const mn_options& o, float min_omf) {
+  return o.object_merge_factor >= min_omf &&
+         (o.variant == MN_VARIANT_CSEGMENT ? o.merge_logprob_bias >= 0.0f : o.merge_logprob_bias == 0.0f);
+}
+
 // After the stream has drained: verdict of a speculative attempt, then the statistics.
-static int segment_read_back(mn_context* c, const mn_options* opts, int mode, bool speculate,
-                             int finish_limit, int N, long long R0, int rounds, bool want_cert,
-                             mn_stats* stats) {
-  if (speculate) {
+static int segment_read_back(mn_context* c, const mn_options* opts, const Queued& q, mn_stats* stats) {
+  const int mode = q.mode;
+  if (q.speculate) {
     if (c->h_scalars[6] != 0) return MN_RETRY_ROUNDS;
-    if (c->h_scalars[7] != 0 || c->h_cnt->n_records > finish_limit) return MN_RETRY_WAIT;
+    if (c->h_scalars[7] != 0 || c->h_cnt->n_records > q.finish_limit) return MN_RETRY_WAIT;
   }
-  const long long merges = (long long)N - (long long)c->h_scalars[2];     // every merge removes one object
+  const long long merges = (long long)q.N - (long long)c->h_scalars[2];     // every merge removes one object
   if (getenv("MN_TRACE_LABEL"))
     fprintf(stderr, "labelling: unions asked for -- vertical borders %d, horizontal borders %d, other offsets %d\n",
             c->h_scalars[10], c->h_scalars[11], c->h_scalars[12]);
@@ -1481,13 +1523,11 @@ static int segment_read_back(mn_context* c, const mn_options* opts, int mode, bo
   if (stats) {
     stats->status = rc;
     stats->mode_used = mode;
-    const bool cert_opts = opts->object_merge_factor > 0.0f &&
-                           (opts->variant == MN_VARIANT_CSEGMENT ? opts->merge_logprob_bias >= 0.0f
-                                                                 : opts->merge_logprob_bias == 0.0f);
+    const bool cert_opts = opts->object_merge_factor > 0.0f && separable_options(*opts, 0.0f);
     stats->cert_edge_violations = c->h_scalars[0];
     stats->cert_class_violations = c->h_scalars[3];
     stats->cert_record_violations = c->h_scalars[4];
-    stats->certified = (want_cert && c->h_scalars[0] == 0 && c->h_scalars[3] == 0 && c->h_scalars[4] == 0 && cert_opts) ? 1 : 0;
+    stats->certified = (q.want_cert && c->h_scalars[0] == 0 && c->h_scalars[3] == 0 && c->h_scalars[4] == 0 && cert_opts) ? 1 : 0;
     // 2 only where the pop order was forced or the reference's own order among equals was run; an exact-engine
     // result that met tied pops under its own lowest-id rule says 3 (advisor r3 / verdict r3: a held vector
     // shows the two rules can part)
@@ -1499,7 +1539,7 @@ static int segment_read_back(mn_context* c, const mn_options* opts, int mode, bo
                                                                                        : MN_PROOF_SEQUENTIAL_TIES;
     stats->num_instances = c->h_scalars[1];
     stats->num_objects = c->h_scalars[2];
-    stats->rounds = rounds;
+    stats->rounds = q.rounds;
     stats->cores_condemned = c->cores_used ? (c->h_scalars[9] != 0) : 0;
     stats->finisher_steps = c->h_cnt->finisher_steps;
     stats->tied_steps = stats->tied_merges = stats->tied_conflicts = 0;
@@ -1513,9 +1553,9 @@ static int segment_read_back(mn_context* c, const mn_options* opts, int mode, bo
       const long long tc = c->xw.h_ctl->tied_conflicts;
       stats->tied_conflicts = (c->xw.h_ctl->ttrack == 0 && tc == 0 && ts > 0) ? 1 : (int)(tc > 0x7FFFFFFF ? 0x7FFFFFFF : tc);
     }
-    stats->initial_records = R0;
+    stats->initial_records = q.R0;
     stats->merges = merges;
-    stats->total_logprob = want_cert ? c->h_lp[0] : NAN;
+    stats->total_logprob = q.want_cert ? c->h_lp[0] : NAN;
     float ms = 0;
     const bool cmode = mode == MN_MODE_COMPONENTS || c->cores_used;   // (no separate scoring phase: ev[1], ev[2] not recorded)
     if (c->cores_used && !(opts->debug_flags & 2)) {
@@ -1526,7 +1566,7 @@ static int segment_read_back(mn_context* c, const mn_options* opts, int mode, bo
       (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]); stats->ms_edge_pass = ms;
     }
     stats->ms_score = stats->ms_class_pass + stats->ms_edge_pass;
-    const bool lean = (opts->debug_flags & 16) != 0 && speculate && mode == MN_MODE_COMPONENTS &&
+    const bool lean = (opts->debug_flags & 16) != 0 && q.speculate && mode == MN_MODE_COMPONENTS &&
                       opts->variant == MN_VARIANT_CSEGMENT;      // (only ev[0], ev[10] were recorded)
     if (!lean) {
       (void)hipEventElapsedTime(&ms, c->ev[cmode ? 0 : 2], c->ev[3]); stats->ms_merge = ms;
@@ -1546,252 +1586,239 @@ static int segment_read_back(mn_context* c, const mn_options* opts, int mode, bo
   return rc;
 }
 
-// `defer` (with a speculative attempt only): return MN_PENDING as soon as everything is queued;
-// the caller reads back later with segment_read_back after waiting for ev_done.
-static int segment_attempt(mn_context* c, const void* d_class_pred, int class_dim,
-                           const void* d_adj_pred, int offset_dim, int W, int H,
-                           int num_classes, const int* offset_list, int* d_mask,
-                           int* d_object_class, int* d_partition, const mn_options* opts,
-                           void* stream, mn_stats* stats, int force_mode, bool speculate,
-                           bool defer = false) {
-  mn_options defaults;
-  if (!opts) { mn_default_options(&defaults); opts = &defaults; }
-  int rc = check_args(c, class_dim, offset_dim, W, H, num_classes, offset_list, opts);
-  if (rc == MN_OK && (!d_class_pred || !d_adj_pred || !d_mask || !d_object_class)) rc = MN_ERR_ARGUMENT;
-  if (stats) { memset(stats, 0, sizeof(*stats)); stats->status = rc; stats->total_logprob = NAN; }
-  if (rc != MN_OK) { g_last_status = rc; return rc; }
-  MN_HIP(hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+struct Plan {              // everything an attempt decides before its first launch
+  int mode;                // MN_MODE_EXACT / ROUNDS / COMPONENTS, resolved (a waited contraction can still fall back)
+  bool xengine;            // the sequential order at any size: the exact engine
+  bool speculate;          // nothing is waited for before the one synchronisation at the end
+  bool fused_tail;         // the speculative attempt of the C++ variant ends in mn_cc_tail
+  bool cores_ok;           // the general rounds may start from the cores (mn_core_clean) instead of from single pixels
+  bool want_cert, lean;    // lean: only the sweep is timed
+  int finish_limit, rounds_limit, exact_limit, subrounds;
+  float band_gamma; long long R0;     // R0: records of the pixel graph
+};
 
-  ImgParams P;
-  fill_params(&P, d_class_pred, d_adj_pred, c->dtype, offset_dim, W, H, num_classes, offset_list, opts);
-  // (development aid: MN_DEBUG_FLAGS_OR in the environment is OR-ed into debug_flags, so that a whole
-  //  test run can be put through an opt-in code path)
-  static const int env_flags = getenv("MN_DEBUG_FLAGS_OR") ? atoi(getenv("MN_DEBUG_FLAGS_OR")) : 0;
-  c->debug_flags = opts->debug_flags | env_flags;
-  c->ext_events = !(opts->debug_flags & 2) && !(opts->debug_flags & 128);
-  c->core_radius = opts->core_radius != 0 ? opts->core_radius : MN_DEFAULT_CORE_RADIUS;
-  const int N = P.N;
-  const long long R0 = count_records(W, H, offset_dim, offset_list);
-  const int exact_limit = opts->exact_limit > 0 ? opts->exact_limit : 32768;
-  const int finish_limit = opts->finish_limit > 0 ? opts->finish_limit : 4096;
+static Plan make_plan(const ImageCall& call, int force_mode, bool speculate) {
+  const mn_options* opts = &call.opts;
+  Plan pl;
+  pl.R0 = count_records(call);
+  pl.exact_limit = opts->exact_limit > 0 ? opts->exact_limit : 32768;
+  pl.finish_limit = opts->finish_limit > 0 ? opts->finish_limit : 4096;
   // hand-over of the general rounds: since the rounds start from the cores a late round is cheap, and
   // 2048 records beat 4096 (10.0 against 11.6 ms on a blurred 1024x2048 map; 1536: 9.7 ms)
-  const int rounds_limit = opts->finish_limit > 0 ? opts->finish_limit : 2048;
-  int subrounds = opts->subrounds > 0 ? opts->subrounds : 32;
-  if (subrounds > MN_MAX_SUBROUNDS) subrounds = MN_MAX_SUBROUNDS;
-  const float band_gamma = opts->band_permille > 0 ? opts->band_permille * 1e-3f
-                                                   : (opts->band_permille < 0 ? 0.0f : 0.05f);
-  int mode = force_mode > 0 ? force_mode : opts->mode;
-  if (mode != MN_MODE_EXACT && mode != MN_MODE_ROUNDS && mode != MN_MODE_COMPONENTS)
-    mode = (R0 <= exact_limit) ? MN_MODE_EXACT : MN_MODE_COMPONENTS;
-  // the component contraction needs: gain = omf * log-odds with omf > 0; bias >= 0 (csegment) so
-  // that intra-component records (> bias) are always visible and ahead of cross records (< bias);
-  // pysegmenter divides (gain + bias) by n1*n2, which only separates the two kinds when bias == 0
+  pl.rounds_limit = opts->finish_limit > 0 ? opts->finish_limit : 2048;
+  pl.subrounds = opts->subrounds > 0 ? opts->subrounds : 32;
+  if (pl.subrounds > MN_MAX_SUBROUNDS) pl.subrounds = MN_MAX_SUBROUNDS;
+  pl.band_gamma = opts->band_permille > 0 ? opts->band_permille * 1e-3f
+                                          : (opts->band_permille < 0 ? 0.0f : 0.05f);
+  pl.mode = force_mode > 0 ? force_mode : opts->mode;
+  if (pl.mode != MN_MODE_EXACT && pl.mode != MN_MODE_ROUNDS && pl.mode != MN_MODE_COMPONENTS)
+    pl.mode = (pl.R0 <= pl.exact_limit) ? MN_MODE_EXACT : MN_MODE_COMPONENTS;
+  // the component contraction needs separable_options
   // (and N <= 2^26: a component's class sums are 2^-32 fixed point in 64 bits, |log p| <= 16)
-  if (mode == MN_MODE_COMPONENTS &&
-      !(N <= (1 << 26) && opts->object_merge_factor >= 1e-20f &&
-        (opts->variant == MN_VARIANT_CSEGMENT ? opts->merge_logprob_bias >= 0.0f
-                                              : opts->merge_logprob_bias == 0.0f)))
-    mode = MN_MODE_ROUNDS;
-  // the sequential order at any size: the exact engine
-  const bool xengine = mode == MN_MODE_EXACT;
-  c->tie_ref = xengine ? opts->tie_order : MN_TIES_LOWEST_ID;
-  c->tie_used = 0;
-  ObjState S = obj_state(c);
+  const bool contractible = call.W * call.H <= (1 << 26) && separable_options(*opts, 1e-20f);
+  if (pl.mode == MN_MODE_COMPONENTS && !contractible) pl.mode = MN_MODE_ROUNDS;
+  pl.xengine = pl.mode == MN_MODE_EXACT;
   // the same conditions let the general rounds start from the cores (mn_core_clean) instead of from
   // single pixels; debug_flags bit 2 keeps the round on the implicit pixel graph
-  const bool cores_ok = N <= (1 << 26) && opts->object_merge_factor >= 1e-20f &&
-                        (opts->variant == MN_VARIANT_CSEGMENT ? opts->merge_logprob_bias >= 0.0f
-                                                              : opts->merge_logprob_bias == 0.0f) &&
-                        !(opts->debug_flags & 4);
-  c->cores_used = 0;
+  pl.cores_ok = contractible && !(opts->debug_flags & 4);
+  pl.speculate = speculate && pl.mode == MN_MODE_COMPONENTS && pl.finish_limit <= MN_FIN2_MAXR;
+  pl.fused_tail = pl.speculate && opts->variant == MN_VARIANT_CSEGMENT;
+  pl.want_cert = opts->compute_logprob != 0;
+  pl.lean = (opts->debug_flags & 16) != 0 && pl.fused_tail;
+  return pl;
+}
 
-  bool fused_tail = false;         // the speculative attempt of the C++ variant ends in mn_cc_tail
-  FillList fills;
+struct Attempt {           // what an attempt carries from one stage to the next
+  hipStream_t st;          // where the next launch goes (run_components moves it to the side / capture stream)
+  int mode;                // Plan::mode, or the rounds after a contraction that did not hold
+  bool cores;              // the rounds start from the cores
+  RecList cur, nxt;        // record list in use / the one the next round builds
+  int rounds, R;           // R: records in `cur` (speculating: the most the finisher takes)
+  FillList fills, post;    // what is cleared in ONE launch before the first kernel; the same again, for the end of a fused attempt
+  // (mn_cc_certificate: from what the contraction and the LDS finisher left, not from a sweep)
+  bool cc_certificate() const { return mode == MN_MODE_COMPONENTS && rounds == 0 && R <= MN_FIN2_MAXR; }
+};
+
+// What the attempt expects cleared before its first kernel, as ONE fill launch (A.fills).
+static void build_clear_list(mn_context* c, const ImgParams& P, const Plan& pl, Attempt& A) {
+  FillList& fills = A.fills;
   fills.add(c->cnt, sizeof(Counters), 0);
   fills.add(c->scalars, MN_NSCALARS * sizeof(int), 0);
-  speculate = speculate && mode == MN_MODE_COMPONENTS && finish_limit <= MN_FIN2_MAXR;
-  if (!xengine) {
-    rc = ensure_fast(c);
-    if (rc != MN_OK) return rc;
-  }
-  // everything but the speculative components attempt and the exact engine works on full-size record lists
-  if (!speculate && !xengine) {
-    rc = ensure_general(c);
-    if (rc != MN_OK) return rc;
-  }
-  if (mode != MN_MODE_COMPONENTS)
-    fills.add(c->mapbuf, (size_t)N * sizeof(int), 0xFF);    // (object -> record) map of mn_finisher
-  if (mode == MN_MODE_COMPONENTS) {
+  if (pl.mode != MN_MODE_COMPONENTS)
+    fills.add(c->mapbuf, (size_t)P.N * sizeof(int), 0xFF);    // (object -> record) map of mn_finisher
+  if (pl.mode == MN_MODE_COMPONENTS) {
     // everything the contraction and the compaction after it expect cleared, in the same launch.
     // Records between components are few: the speculative attempt, which only stands with at
     // most finish_limit of them, takes a table of 8x that many slots (less to clear, less for
     // mn_compact to scan); the ordinary attempt one of N/8.  A table that fills up fails the
     // bounded insert, counted apart from the separability violations (scalars[7]).
     // (the speculative attempt ends in mn_cc_tail, whose lanes hold MN_TAIL_TABLE_CAP / 1024 slots each)
-    fused_tail = speculate && opts->variant == MN_VARIANT_CSEGMENT;
-    size_t cap = fused_tail ? (size_t)MN_TAIL_TABLE_CAP
-                            : (speculate ? next_pow2((size_t)finish_limit * 8) : next_pow2((size_t)N / 8 + 8192));
+    size_t cap = pl.fused_tail ? (size_t)MN_TAIL_TABLE_CAP
+                               : (pl.speculate ? next_pow2((size_t)pl.finish_limit * 8) : next_pow2((size_t)P.N / 8 + 8192));
     if (cap > c->cc_cap_max) cap = c->cc_cap_max;
     c->cc_cap = cap;
     fills.add(c->T.key, cap * sizeof(u64), 0xFF);
     fills.add(c->T.S, cap * sizeof(i64), 0);
     fills.add(c->T.touched, cap, 0);
     fills.add(c->cc_tcount, cap * sizeof(int), 0);
-    if (!speculate) {
+    if (!pl.speculate) {
       // best-record slots: only if more records may be left than the finisher takes, so that the
       // rounds go on from this list and look at all N slots (the speculative attempt never does:
       // it is redone on this path instead)
-      fills.add(c->ball, (size_t)N * sizeof(u64), 0);
+      fills.add(c->ball, (size_t)P.N * sizeof(u64), 0);
       fills.add(c->gmax, 64 * sizeof(unsigned), 0);
     }
   }
   // A fused speculative attempt clears the same few kilobytes again at its END, on the side stream
   // (after the statistics have been copied out): the next one starts with its sweep over the
   // sameness planes instead of a fill kernel and the dispatch gap behind it.
-  FillList post = fills;
-  if (fused_tail && c->cc_clean) fills.j.count = 0;
+  A.post = fills;
+  if (pl.fused_tail && c->cc_clean) fills.j.count = 0;
   c->cc_clean = 0;                 // (set again only when this attempt has queued its own clean-up)
+}
 
-  // ---------------- phase A ----------------
-  bool cores = mode == MN_MODE_ROUNDS && cores_ok;
-  if (cores) fills.add(c->touch, 64 * sizeof(unsigned), 0);        // (edges outside the cores: mn_core_bits)
-  if (xengine) {
-    fills.launch(st);
-    MN_HIP(hipEventRecord(c->ev[0], st));
-    rc = run_exact_engine(c, P, st);
+// Phase A: the exact engine from start to end, or the scoring passes / the contraction (with its fall-back to the rounds).
+static int run_first_phase(mn_context* c, const ImgParams& P, const Plan& pl, Attempt& A) {
+  FillList& fills = A.fills;
+  int rc;
+  if (A.cores) fills.add(c->touch, 64 * sizeof(unsigned), 0);        // (edges outside the cores: mn_core_bits)
+  if (pl.xengine) {
+    fills.launch(A.st);
+    MN_HIP(hipEventRecord(c->ev[0], A.st));
+    rc = run_exact_engine(c, P, A.st);
   } else {
-    rc = run_phase_a(c, P, st, mode == MN_MODE_ROUNDS && !cores, &fills, mode == MN_MODE_COMPONENTS || cores);
+    rc = run_phase_a(c, P, A.st, A.mode == MN_MODE_ROUNDS && !A.cores, &fills, A.mode == MN_MODE_COMPONENTS || A.cores);
   }
   if (rc != MN_OK) return rc;
-  if (mode == MN_MODE_COMPONENTS) {
-    rc = run_components(c, P, st, !speculate, !speculate, !fused_tail, fused_tail);
+  if (A.mode == MN_MODE_COMPONENTS) {
+    rc = run_components(c, P, A.st, !pl.speculate ? CC_WAITED : (pl.fused_tail ? CC_QUEUED_TAIL : CC_QUEUED_COMPACT));
     if (rc < 0) return rc;
     if (rc == 1) {                 // not sign-separable: start over with the general rounds
-      mode = MN_MODE_ROUNDS;
-      cores = cores_ok;
+      A.mode = MN_MODE_ROUNDS;
+      A.cores = pl.cores_ok;
       FillList none;
-      if (cores) none.add(c->touch, 64 * sizeof(unsigned), 0);
-      rc = run_phase_a(c, P, st, !cores, &none, cores);
-      if (rc != MN_OK) return rc;
+      if (A.cores) none.add(c->touch, 64 * sizeof(unsigned), 0);
+      if ((rc = run_phase_a(c, P, A.st, !A.cores, &none, A.cores)) != MN_OK) return rc;
     }
   }
-  if (cores) {
+  if (A.cores) {
     // sweep + labelling of the cores + their class sums and object state; nothing is waited for
-    rc = run_components(c, P, st, false, false, false, false, true);
-    if (rc < 0) return rc;
+    if ((rc = run_components(c, P, A.st, CC_CORES)) < 0) return rc;
     c->cores_used = 1;
   }
+  return MN_OK;
+}
 
-  // ---------------- phase B ----------------
-  long long merges = 0;
-  int rounds = 0;
-  RecList cur = c->LA, nxt = c->LB;
-  int R = 0;
-  if (mode == MN_MODE_ROUNDS && cores) {
-    rounds = 1;                    // (the contraction stands for round 0)
-  } else if (mode == MN_MODE_ROUNDS) {
+// Round 0 of the general rounds (the contraction of the cores stands for it where they are used).
+static int run_round0(mn_context* c, const ImgParams& P, const Plan& pl, Attempt& A) {
+  if (A.mode != MN_MODE_ROUNDS) return MN_OK;
+  const int N = P.N;
+  if (!A.cores) {
     // round 0 on the implicit pixel graph: matching sub-rounds, then one apply
-    MN_HIP(hipMemsetAsync(c->progress, 0, MN_MAX_SUBROUNDS * sizeof(int), st));
-    hipLaunchKernelGGL(mn_pix_match, dim3(grid_for(N, 256)), dim3(256), 0, st, N,
+    MN_HIP(hipMemsetAsync(c->progress, 0, MN_MAX_SUBROUNDS * sizeof(int), A.st));
+    hipLaunchKernelGGL(mn_pix_match, dim3(grid_for(N, 256)), dim3(256), 0, A.st, N,
                        (const u64*)c->ball, c->matched, c->mate, c->progress, 0, c->cnt);
-    for (int s = 1; s < subrounds; s++) {
-      launch_edge_pass<false>(c, P, st, c->bsub, s);
-      hipLaunchKernelGGL(mn_pix_match, dim3(grid_for(N, 256)), dim3(256), 0, st, N,
+    for (int s = 1; s < pl.subrounds; s++) {
+      launch_edge_pass<false>(c, P, A.st, c->bsub, s);
+      hipLaunchKernelGGL(mn_pix_match, dim3(grid_for(N, 256)), dim3(256), 0, A.st, N,
                          (const u64*)c->bsub, c->matched, c->mate, c->progress, s, c->cnt);
     }
-    hipLaunchKernelGGL(mn_pix_apply, dim3(grid_for(N, 256)), dim3(256), 0, st, P, S,
-                       (const int*)c->mate, c->cnt);
-    rounds = 1;
+    hipLaunchKernelGGL(mn_pix_apply, dim3(grid_for(N, 256)), dim3(256), 0, A.st, P, obj_state(c), (const int*)c->mate, c->cnt);
   }
-  if (xengine) {
-    R = 0;
-  } else if (mode == MN_MODE_COMPONENTS) {
+  A.rounds = 1;
+  return MN_OK;
+}
+
+// The first record list, then rounds until the finisher can take what is left: A.cur, A.R, A.rounds.
+static int run_rounds(mn_context* c, const ImgParams& P, const Plan& pl, Attempt& A) {
+  if (pl.xengine) return MN_OK;      // (the engine has no list: R stays 0)
+  const int N = P.N;
+  const hipStream_t st = A.st;
+  int &R = A.R, rc;
+  if (A.mode == MN_MODE_COMPONENTS) {
     // run_components already compacted the table into the list; speculating, the count is still
     // on the device: launches below are sized for the most the finisher takes
-    R = speculate ? finish_limit : c->h_cnt->n_records;
+    R = pl.speculate ? pl.finish_limit : c->h_cnt->n_records;
   } else {
-    size_t cap0 = next_pow2((size_t)R0 + (size_t)R0 / 4 + 1024);
-    if (cores && R0 > (1 << 18)) {   // only the edges outside the cores become records: worth a round trip
+    size_t cap0 = next_pow2((size_t)pl.R0 + (size_t)pl.R0 / 4 + 1024);
+    if (A.cores && pl.R0 > (1 << 18)) {   // only the edges outside the cores become records: worth a round trip
       MN_HIP(hipMemcpyAsync(c->h_touch, c->touch, 64 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
       MN_HIP(hipStreamSynchronize(st));
       size_t need = 0;
       for (int w = 0; w < 64; w++) need += c->h_touch[w];
       cap0 = next_pow2(need + need / 2 + 1024);
     }
-    rc = build_list(c, P, st, cap0 < c->cap ? cap0 : c->cap, cur, true, cur, 0, &R);
-    if (rc != MN_OK) return rc;
+    if ((rc = build_list(c, P, st, cap0 < c->cap ? cap0 : c->cap, A.cur, nullptr, 0, &R)) != MN_OK) return rc;
   }
-  if (mode == MN_MODE_ROUNDS || mode == MN_MODE_COMPONENTS) {
-    bool first_round = true;
-    int productive = subrounds;    // matching sub-rounds of the previous round that paired anything, + 1
-    // (a list the finisher can take whole goes to it at once: the sequential order itself; the lower
-    //  hand-over only applies once the rounds are running)
-    int loop_limit = finish_limit;
-    while (!speculate && R > loop_limit && rounds < 5000) {
-      if (mode != MN_MODE_COMPONENTS || rounds > 0) loop_limit = rounds_limit;
-      {
-        FillList f;                // one launch instead of five memsets
-        f.add(c->matched, N, 0);
-        f.add(c->mate, (size_t)N * sizeof(int), 0xFF);
-        f.add(c->cnt, 4 * sizeof(int), 0);                       // n_records, any_selected, ...
-        f.add(c->progress, MN_MAX_SUBROUNDS * sizeof(int), 0);
-        f.add(c->touch, 64 * sizeof(unsigned), 0);
-        if (first_round) f.add(c->bsub, (size_t)N * sizeof(u64), 0);   // (accept leaves it clean for the next round)
-        f.launch(st);
-        first_round = false;
-      }
-      const dim3 g(grid_for(R, 256)), b(256), go(grid_for(N, 256));
-      hipLaunchKernelGGL(mn_band_threshold, dim3(1), dim3(64), 0, st, (const unsigned*)c->gmax,
-                         P.bias, P.variant, band_gamma, c->theta);
-      hipLaunchKernelGGL(mn_obj_match_mutual, go, b, 0, st, N, (const u64*)c->ball,
-                         (const float*)c->theta, c->matched, c->mate, c->progress, c->cnt);
-      // late rounds are launch-bound: fewer matching sub-rounds once the list is small
-      // ... and a sub-round is two launches that return at once when the one before paired nothing:
-      // how far the previous round got (read back with its counters) bounds this one, plus a margin
-      int sub_r = R > (1 << 20) ? subrounds : (subrounds > 8 ? subrounds / 4 : subrounds);
-      if (sub_r > productive + 3) sub_r = productive + 3;
-      for (int s = 1; s < sub_r; s++) {
-        hipLaunchKernelGGL(mn_obj_propose, go, b, 0, st, N, (const u64*)c->ball,
-                           (const float*)c->theta, (const unsigned char*)c->matched, c->bsub,
-                           (const int*)c->progress, s, c->cnt);
-        hipLaunchKernelGGL(mn_obj_accept, go, b, 0, st, N, c->bsub, c->matched, c->mate,
-                           c->progress, s, c->cnt);
-      }
-      hipLaunchKernelGGL(mn_rec_apply, g, b, 0, st, P, S, cur, R, (const int*)c->mate, c->cnt, c->touch);
-      // the table only takes the records with a matched object at an end (the others go straight to
-      // the next list): for a big list it is worth a host round trip to size it for those
-      size_t need = (size_t)R;
-      if (R > (1 << 18)) {
-        MN_HIP(hipMemcpyAsync(c->h_touch, c->touch, 64 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-        MN_HIP(hipStreamSynchronize(st));
-        need = 0;
-        for (int w = 0; w < 64; w++) need += c->h_touch[w];
-      }
-      size_t cap = next_pow2(need + need / 2 + 1024);   // load <= 2/3
-      if (cap > c->cap) cap = c->cap;
-      int Rn = 0;
-      MN_HIP(hipMemcpyAsync(c->h_touch + 64, c->progress, MN_MAX_SUBROUNDS * sizeof(int), hipMemcpyDeviceToHost, st));
-      rc = build_list(c, P, st, cap, nxt, false, cur, R, &Rn);
-      if (rc != MN_OK) return rc;
-      productive = 1;
-      for (int w = 1; w < sub_r; w++)
-        if (c->h_touch[64 + w]) productive = w + 1;
-      if (getenv("MN_TRACE_ROUNDS"))
-        fprintf(stderr, "round %d: R %d -> %d, sub-rounds used %d of %d\n", rounds, R, Rn, productive, sub_r);
-      rounds++;
-      const int selected = c->h_cnt->any_selected;
-      RecList t = cur; cur = nxt; nxt = t;
-      R = Rn;
-      if (selected == 0) break;     // nothing visible any more: the queue is empty
+  bool first_round = true;
+  int productive = pl.subrounds;    // matching sub-rounds of the previous round that paired anything, + 1
+  // (a list the finisher can take whole goes to it at once: the sequential order itself; the lower
+  //  hand-over only applies once the rounds are running)
+  int loop_limit = pl.finish_limit;
+  while (!pl.speculate && R > loop_limit && A.rounds < 5000) {
+    if (A.mode != MN_MODE_COMPONENTS || A.rounds > 0) loop_limit = pl.rounds_limit;
+    {
+      FillList f;                // one launch instead of five memsets
+      f.add(c->matched, N, 0);
+      f.add(c->mate, (size_t)N * sizeof(int), 0xFF);
+      f.add(c->cnt, 4 * sizeof(int), 0);                       // n_records, any_selected, ...
+      f.add(c->progress, MN_MAX_SUBROUNDS * sizeof(int), 0);
+      f.add(c->touch, 64 * sizeof(unsigned), 0);
+      if (first_round) f.add(c->bsub, (size_t)N * sizeof(u64), 0);   // (accept leaves it clean for the next round)
+      f.launch(st);
+      first_round = false;
     }
+    const dim3 g(grid_for(R, 256)), b(256), go(grid_for(N, 256));
+    hipLaunchKernelGGL(mn_band_threshold, dim3(1), dim3(64), 0, st, (const unsigned*)c->gmax,
+                       P.bias, P.variant, pl.band_gamma, c->theta);
+    hipLaunchKernelGGL(mn_obj_match_mutual, go, b, 0, st, N, (const u64*)c->ball,
+                       (const float*)c->theta, c->matched, c->mate, c->progress, c->cnt);
+    // late rounds are launch-bound: fewer matching sub-rounds once the list is small
+    // ... and a sub-round is two launches that return at once when the one before paired nothing:
+    // how far the previous round got (read back with its counters) bounds this one, plus a margin
+    int sub_r = R > (1 << 20) ? pl.subrounds : (pl.subrounds > 8 ? pl.subrounds / 4 : pl.subrounds);
+    if (sub_r > productive + 3) sub_r = productive + 3;
+    for (int s = 1; s < sub_r; s++) {
+      hipLaunchKernelGGL(mn_obj_propose, go, b, 0, st, N, (const u64*)c->ball, (const float*)c->theta,
+                         (const unsigned char*)c->matched, c->bsub, (const int*)c->progress, s, c->cnt);
+      hipLaunchKernelGGL(mn_obj_accept, go, b, 0, st, N, c->bsub, c->matched, c->mate, c->progress, s, c->cnt);
+    }
+    hipLaunchKernelGGL(mn_rec_apply, g, b, 0, st, P, obj_state(c), A.cur, R, (const int*)c->mate, c->cnt, c->touch);
+    // the table only takes the records with a matched object at an end (the others go straight to
+    // the next list): for a big list it is worth a host round trip to size it for those
+    size_t need = (size_t)R;
+    if (R > (1 << 18)) {
+      MN_HIP(hipMemcpyAsync(c->h_touch, c->touch, 64 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+      MN_HIP(hipStreamSynchronize(st));
+      need = 0;
+      for (int w = 0; w < 64; w++) need += c->h_touch[w];
+    }
+    size_t cap = next_pow2(need + need / 2 + 1024);   // load <= 2/3
+    if (cap > c->cap) cap = c->cap;
+    int Rn = 0;
+    MN_HIP(hipMemcpyAsync(c->h_touch + 64, c->progress, MN_MAX_SUBROUNDS * sizeof(int), hipMemcpyDeviceToHost, st));
+    if ((rc = build_list(c, P, st, cap, A.nxt, &A.cur, R, &Rn)) != MN_OK) return rc;
+    productive = 1;
+    for (int w = 1; w < sub_r; w++)
+      if (c->h_touch[64 + w]) productive = w + 1;
+    if (getenv("MN_TRACE_ROUNDS"))
+      fprintf(stderr, "round %d: R %d -> %d, sub-rounds used %d of %d\n", A.rounds, R, Rn, productive, sub_r);
+    A.rounds++;
+    const int selected = c->h_cnt->any_selected;
+    RecList t = A.cur; A.cur = A.nxt; A.nxt = t;
+    R = Rn;
+    if (selected == 0) break;     // nothing visible any more: the queue is empty
   }
-  const bool want_cert = opts->compute_logprob != 0;
-  // sequential lazy-greedy on what is left (the whole problem in exact mode)
-  if (xengine) {
+  return MN_OK;
+}
+
+// Sequential lazy-greedy on what is left: mn_cc_tail, mn_finisher_lds or mn_finisher by the attempt and its list's length.
+static int launch_finisher(mn_context* c, const ImgParams& P, const Plan& pl, const Attempt& A, const ImageCall& call) {
+  const ObjState S = obj_state(c);
+  const long long max_steps = 64LL * (pl.R0 > 0 ? pl.R0 : 1) + 4096;
+  if (pl.xengine) {
     // (the engine has run to the end of the queue)
-  } else if (fused_tail) {
+  } else if (pl.fused_tail) {
     if (!c->tail_lds_ready) {
       MN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mn_cc_tail),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, MN_FIN2_MAXR * 12));
@@ -1799,114 +1826,115 @@ static int segment_attempt(mn_context* c, const void* d_class_pred, int class_di
     }
     HashTab T = c->T;
     T.mask = (unsigned)(c->cc_cap - 1);
-    const long long max_steps = 64LL * (R0 > 0 ? R0 : 1) + 4096;
     const int nbe = c->cc_sign_blocks;
-    hipLaunchKernelGGL(mn_cc_tail, dim3(1), dim3(MN_FIN2_THREADS), MN_FIN2_MAXR * 12, st, P, S, T,
-                       (const int*)c->cc_tcount, cur, c->cc_lcount, c->label, c->fin_lists, c->cnt, max_steps,
-                       c->scalars, finish_limit, (const unsigned char*)c->cls0, (const int*)c->mate,
-                       (const int*)c->cc_roots, nbe, (const double*)c->partial, c->lp_out, want_cert ? 1 : 0,
-                       c->label, d_object_class);
+    hipLaunchKernelGGL(mn_cc_tail, dim3(1), dim3(MN_FIN2_THREADS), MN_FIN2_MAXR * 12, A.st, P, S, T, (const int*)c->cc_tcount,
+                       A.cur, c->cc_lcount, c->label, c->fin_lists, c->cnt, max_steps, c->scalars, pl.finish_limit,
+                       (const unsigned char*)c->cls0, (const int*)c->mate, (const int*)c->cc_roots, nbe,
+                       (const double*)c->partial, c->lp_out, pl.want_cert ? 1 : 0, c->label, call.d_objcls);
   } else {
-    const long long max_steps = 64LL * (R0 > 0 ? R0 : 1) + 4096;
     // (records that come straight from the component contraction were scored a moment ago)
-    if (mode != MN_MODE_EXACT && R > 0 && !opts->no_handover_refresh &&
-        !(mode == MN_MODE_COMPONENTS && rounds == 0))
-      hipLaunchKernelGGL(mn_rec_refresh, dim3(grid_for(R, 256)), dim3(256), 0, st, P, S, cur, R);
-    if (R <= MN_FIN2_MAXR) {
+    if (A.mode != MN_MODE_EXACT && A.R > 0 && !call.opts.no_handover_refresh &&
+        !(A.mode == MN_MODE_COMPONENTS && A.rounds == 0))
+      hipLaunchKernelGGL(mn_rec_refresh, dim3(grid_for(A.R, 256)), dim3(256), 0, A.st, P, S, A.cur, A.R);
+    if (A.R <= MN_FIN2_MAXR) {
       // record list resident in LDS (96 KiB dynamic); the (object -> record) map lives in `label`
       if (!c->fin_lds_ready) {
         MN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mn_finisher_lds),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, MN_FIN2_MAXR * 12));
         c->fin_lds_ready = 1;
       }
-      hipLaunchKernelGGL(mn_finisher_lds, dim3(1), dim3(MN_FIN2_THREADS), MN_FIN2_MAXR * 12, st, P, S,
-                         cur, R, c->label, c->fin_lists, c->cnt, max_steps,
-                         speculate ? (const int*)&c->cnt->n_records : (const int*)nullptr,
-                         (const int*)(c->scalars + 6), finish_limit,
-                         (mode == MN_MODE_COMPONENTS && rounds == 0) ? c->cc_lcount : (int*)nullptr);
+      hipLaunchKernelGGL(mn_finisher_lds, dim3(1), dim3(MN_FIN2_THREADS), MN_FIN2_MAXR * 12, A.st, P, S, A.cur, A.R, c->label,
+                         c->fin_lists, c->cnt, max_steps, pl.speculate ? (const int*)&c->cnt->n_records : (const int*)nullptr,
+                         (const int*)(c->scalars + 6), pl.finish_limit,
+                         (A.mode == MN_MODE_COMPONENTS && A.rounds == 0) ? c->cc_lcount : (int*)nullptr);
     } else {
-      if (mode == MN_MODE_COMPONENTS || cores)   // (the class range of the contraction lived there)
-        MN_HIP(hipMemsetAsync(c->mapbuf, 0xFF, (size_t)N * sizeof(int), st));
-      hipLaunchKernelGGL(mn_finisher, dim3(1), dim3(MN_FIN_THREADS), 0, st, P, S, cur, R, c->mapbuf,
+      if (A.mode == MN_MODE_COMPONENTS || A.cores)   // (the class range of the contraction lived there)
+        MN_HIP(hipMemsetAsync(c->mapbuf, 0xFF, (size_t)P.N * sizeof(int), A.st));
+      hipLaunchKernelGGL(mn_finisher, dim3(1), dim3(MN_FIN_THREADS), 0, A.st, P, S, A.cur, A.R, c->mapbuf,
                          c->touched_list, c->cnt, max_steps);
     }
   }
-  const bool lean = (opts->debug_flags & 16) != 0 && fused_tail;   // (only the sweep is timed)
-  if (!lean) MN_HIP(hipEventRecord(c->ev[3], st));
+  if (!pl.lean) MN_HIP(hipEventRecord(c->ev[3], A.st));
+  return MN_OK;
+}
 
-  // ---------------- output ----------------
+// Output stage: pruning (pysegmenter), instance ranks, mask / class table / partition.
+static int launch_output(mn_context* c, const ImgParams& P, const Plan& pl, const Attempt& A, const ImageCall& call) {
+  const int N = P.N;
+  const ObjState S = obj_state(c);
   const unsigned char* pruned = NULL;
-  if (opts->variant == MN_VARIANT_PYSEGMENTER) {
-    MN_HIP(hipMemsetAsync(c->bg_key, 0, sizeof(u64), st));
-    hipLaunchKernelGGL(mn_prune_find_background, dim3(grid_for(N, 256)), dim3(256), 0, st, P, S,
-                       c->bg_key);
-    hipLaunchKernelGGL(mn_prune_mark, dim3(grid_for(N, 256)), dim3(256), 0, st, P, S,
-                       opts->prune_threshold, (const u64*)c->bg_key, c->pruned, c->cnt);
+  if (call.opts.variant == MN_VARIANT_PYSEGMENTER) {
+    MN_HIP(hipMemsetAsync(c->bg_key, 0, sizeof(u64), A.st));
+    hipLaunchKernelGGL(mn_prune_find_background, dim3(grid_for(N, 256)), dim3(256), 0, A.st, P, S, c->bg_key);
+    hipLaunchKernelGGL(mn_prune_mark, dim3(grid_for(N, 256)), dim3(256), 0, A.st, P, S,
+                       call.opts.prune_threshold, (const u64*)c->bg_key, c->pruned, c->cnt);
     pruned = c->pruned;
   }
-  if (!fused_tail) {
+  if (!pl.fused_tail) {
     const int nblk = (int)grid_for(N, MN_SCAN_ITEMS);
-    hipLaunchKernelGGL(mn_rank_count, dim3(nblk), dim3(256), 0, st, N, S, pruned, c->block_count,
-                       c->scalars + 2);
-    hipLaunchKernelGGL(mn_rank_scan, dim3(1), dim3(1024), 0, st, nblk, c->block_count, c->scalars + 1);
-    hipLaunchKernelGGL(mn_rank_assign, dim3(nblk), dim3(256), 0, st, N, S, pruned,
-                       (const int*)c->block_count, c->label, d_object_class);
+    hipLaunchKernelGGL(mn_rank_count, dim3(nblk), dim3(256), 0, A.st, N, S, pruned, c->block_count, c->scalars + 2);
+    hipLaunchKernelGGL(mn_rank_scan, dim3(1), dim3(1024), 0, A.st, nblk, c->block_count, c->scalars + 1);
+    hipLaunchKernelGGL(mn_rank_assign, dim3(nblk), dim3(256), 0, A.st, N, S, pruned,
+                       (const int*)c->block_count, c->label, call.d_objcls);
   }
   {
     // (the per-pixel roots are only read by the per-pixel certificate below)
-    const bool need_root = want_cert && !fused_tail && !(mode == MN_MODE_COMPONENTS && rounds == 0 && R <= MN_FIN2_MAXR);
+    const bool need_root = pl.want_cert && !pl.fused_tail && !A.cc_certificate();
     int* root_out = need_root ? c->root : nullptr;
-    const bool aligned = (N & 3) == 0 && ((reinterpret_cast<uintptr_t>(d_mask) | reinterpret_cast<uintptr_t>(d_object_class) |
-                                           reinterpret_cast<uintptr_t>(d_partition)) & 15) == 0;
+    const bool aligned = (N & 3) == 0 && ((reinterpret_cast<uintptr_t>(call.d_mask) | reinterpret_cast<uintptr_t>(call.d_objcls) |
+                                           reinterpret_cast<uintptr_t>(call.d_part)) & 15) == 0;
     if (aligned)
-      hipLaunchKernelGGL(mn_write_mask4, dim3(grid_for((size_t)N / 4, 256)), dim3(256), 0, st, N,
-                         (const int*)c->parent, (const int*)c->label, (const int*)(c->scalars + 1),
-                         root_out, d_mask, d_partition, d_object_class);
+      hipLaunchKernelGGL(mn_write_mask4, dim3(grid_for((size_t)N / 4, 256)), dim3(256), 0, A.st, N, (const int*)c->parent,
+                         (const int*)c->label, (const int*)(c->scalars + 1), root_out, call.d_mask, call.d_part, call.d_objcls);
     else
-      hipLaunchKernelGGL(mn_write_mask, dim3(grid_for(N, 256)), dim3(256), 0, st, N,
-                         (const int*)c->parent, (const int*)c->label, (const int*)(c->scalars + 1),
-                         root_out, d_mask, d_partition, d_object_class);
+      hipLaunchKernelGGL(mn_write_mask, dim3(grid_for(N, 256)), dim3(256), 0, A.st, N, (const int*)c->parent,
+                         (const int*)c->label, (const int*)(c->scalars + 1), root_out, call.d_mask, call.d_part, call.d_objcls);
   }
-  // certificate + log-likelihood (skipped on request: compute_logprob = 0, the drop-in entry's
-  // setting -- the reference's c_run_segmentation returns neither)
-  if (!want_cert || fused_tail) {
-  } else if (mode == MN_MODE_COMPONENTS && rounds == 0 && R <= MN_FIN2_MAXR) {
+  return MN_OK;
+}
+
+// certificate + log-likelihood (skipped on request: compute_logprob = 0, the drop-in entry's
+// setting -- the reference's c_run_segmentation returns neither)
+static int launch_certificate(mn_context* c, const ImgParams& P, const Plan& pl, const Attempt& A) {
+  const int N = P.N, R = A.R;
+  const ObjState S = obj_state(c);
+  if (!pl.want_cert || pl.fused_tail) {
+  } else if (A.cc_certificate()) {
     // no further sweep over the sameness planes: the edge sweep of the contraction left the sums
     // for the components and the finisher what the merged records moved (mn_cc_certificate)
     const int nbe = c->cc_sign_blocks;
-    hipLaunchKernelGGL(mn_cc_certificate, dim3(1), dim3(MN_CC_CERT_THREADS), 0, st, P, S,
-                       (const unsigned char*)c->cls0, (const int*)c->mate, (const int*)c->cc_roots,
-                       (const int*)(c->scalars + 8), nbe, (const double*)c->partial,
-                       (const Counters*)c->cnt, c->lp_out, c->scalars);
-    if (R > 0)
-      hipLaunchKernelGGL(mn_verify_records, dim3(grid_for(R, 256)), dim3(256), 0, st, P, S, cur, R,
-                         c->scalars, speculate ? (const int*)&c->cnt->n_records : (const int*)nullptr);
+    hipLaunchKernelGGL(mn_cc_certificate, dim3(1), dim3(MN_CC_CERT_THREADS), 0, A.st, P, S, (const unsigned char*)c->cls0,
+                       (const int*)c->mate, (const int*)c->cc_roots, (const int*)(c->scalars + 8), nbe,
+                       (const double*)c->partial, (const Counters*)c->cnt, c->lp_out, c->scalars);
   } else {
     const bool four = P.W % 4 == 0;              // 4 pixels of one row per lane
     const int vb = (int)grid_for(four ? (size_t)N / 4 : (size_t)N, four ? MN_VERIFY4_THREADS : 256);
     if (four)
-      hipLaunchKernelGGL(mn_verify_edges4, dim3(vb), dim3(MN_VERIFY4_THREADS), 0, st, P, S,
+      hipLaunchKernelGGL(mn_verify_edges4, dim3(vb), dim3(MN_VERIFY4_THREADS), 0, A.st, P, S,
                          (const unsigned char*)c->cls0, (const int*)c->root, c->partial, c->scalars);
     else
-      hipLaunchKernelGGL(mn_verify_edges, dim3(vb), dim3(256), 0, st, P, S,
+      hipLaunchKernelGGL(mn_verify_edges, dim3(vb), dim3(256), 0, A.st, P, S,
                          (const unsigned char*)c->cls0, (const int*)c->root, c->partial, c->scalars);
-    hipLaunchKernelGGL(mn_verify_reduce, dim3(1), dim3(256), 0, st, vb, (const double*)c->partial,
-                       P.omf, c->lp_out);
-    if (xengine)
-      hipLaunchKernelGGL(mn_x_verify_records, dim3(grid_for((size_t)c->xw.X.NL, 256)), dim3(256), 0, st, P,
+    hipLaunchKernelGGL(mn_verify_reduce, dim3(1), dim3(256), 0, A.st, vb, (const double*)c->partial, P.omf, c->lp_out);
+    if (pl.xengine)
+      hipLaunchKernelGGL(mn_x_verify_records, dim3(grid_for((size_t)c->xw.X.NL, 256)), dim3(256), 0, A.st, P,
                          c->xw.X, c->scalars);
-    if (R > 0)
-      hipLaunchKernelGGL(mn_verify_records, dim3(grid_for(R, 256)), dim3(256), 0, st, P, S, cur, R,
-                         c->scalars, speculate ? (const int*)&c->cnt->n_records : (const int*)nullptr);
   }
-  if (!lean) MN_HIP(hipEventRecord(c->ev[4], st));
+  if (pl.want_cert && !pl.fused_tail && R > 0)      // (either form ends with the records the finisher was given)
+    hipLaunchKernelGGL(mn_verify_records, dim3(grid_for(R, 256)), dim3(256), 0, A.st, P, S, A.cur, R,
+                       c->scalars, pl.speculate ? (const int*)&c->cnt->n_records : (const int*)nullptr);
+  if (!pl.lean) MN_HIP(hipEventRecord(c->ev[4], A.st));
   MN_HIP(hipGetLastError());
-  c->last_params = P;
-  c->last_valid = 1;
+  return MN_OK;
+}
 
+// Statistics copied out, the fused attempt's clean-up queued, a recording closed; then MN_PENDING or wait and read back.
+static int close_attempt(mn_context* c, const ImageCall& call, const Plan& pl, Attempt& A, mn_stats* stats, bool defer) {
+  hipStream_t st = A.st;
+  const Queued q = {A.mode, A.rounds, pl.finish_limit, call.W * call.H, pl.R0, pl.speculate, pl.want_cert};
   MN_HIP(hipMemcpyAsync(c->h_statblk, c->statblk, MN_STAT_BYTES, hipMemcpyDeviceToHost, st));
-  if (fused_tail) {                // (st is the side stream here)
-    post.launch(st);
+  if (pl.fused_tail) {             // (st is the side stream here)
+    A.post.launch(st);
     c->cc_clean = 1;
   }
   if (c->replay.capturing) {
@@ -1916,17 +1944,74 @@ static int segment_attempt(mn_context* c, const void* d_class_pred, int class_di
     st = c->side;
     c->replay.capturing = 0;
     c->replay.state = 2;
-    c->replay.finish_limit = finish_limit; c->replay.R0 = R0; c->replay.want_cert = want_cert;
+    c->replay.queued = q;
   }
-  if (defer && speculate) {
+  if (defer && pl.speculate) {
     MN_HIP(hipEventRecord(c->ev_done, st));
-    c->pend.mode = mode; c->pend.rounds = rounds; c->pend.finish_limit = finish_limit; c->pend.N = N;
-    c->pend.R0 = R0; c->pend.speculate = true; c->pend.want_cert = want_cert;
+    c->pend.queued = q;
     return MN_PENDING;
   }
   MN_HIP(hipStreamSynchronize(st));
-  (void)merges;
-  return segment_read_back(c, opts, mode, speculate, finish_limit, N, R0, rounds, want_cert, stats);
+  return segment_read_back(c, &call.opts, q, stats);
+}
+
+// One attempt at an image, as a sequence of stages on one stream.  `speculate`: in components mode the host does
+// not wait for the record count and the separability verdict in the middle of the image; finisher and output are
+// queued behind the contraction and everything is read at the one synchronisation at the end.  Sign-separable maps
+// with few components -- the case the mode exists for -- are done then; otherwise a verdict above is returned and
+// mn_segment_finish runs the attempt again on the ordinary path.  `defer` (with a speculative attempt only): return
+// MN_PENDING as soon as everything is queued; the caller reads back later with segment_read_back after waiting for ev_done.
+static int segment_attempt(mn_context* c, const ImageCall& call, mn_stats* stats, int force_mode, bool speculate, bool defer = false) {
+  ImgParams P;
+  int rc = begin_call(c, call, call.d_mask && call.d_objcls, stats, &P);
+  if (rc != MN_OK) return rc;
+  // (development aid: MN_DEBUG_FLAGS_OR in the environment is OR-ed into debug_flags, so that a whole
+  //  test run can be put through an opt-in code path)
+  static const int env_flags = getenv("MN_DEBUG_FLAGS_OR") ? atoi(getenv("MN_DEBUG_FLAGS_OR")) : 0;
+  c->debug_flags = call.opts.debug_flags | env_flags;
+  c->ext_events = !(call.opts.debug_flags & 2) && !(call.opts.debug_flags & 128);
+  c->core_radius = call.opts.core_radius != 0 ? call.opts.core_radius : MN_DEFAULT_CORE_RADIUS;
+  const Plan pl = make_plan(call, force_mode, speculate);
+  c->tie_ref = pl.xengine ? call.opts.tie_order : MN_TIES_LOWEST_ID;
+  c->tie_used = 0; c->cores_used = 0;
+  if (!pl.xengine && (rc = ensure_fast(c)) != MN_OK) return rc;
+  // everything but the speculative components attempt and the exact engine works on full-size record lists
+  if (!pl.speculate && !pl.xengine && (rc = ensure_general(c)) != MN_OK) return rc;
+  Attempt A = {call.stream, pl.mode, pl.mode == MN_MODE_ROUNDS && pl.cores_ok, c->LA, c->LB, 0, 0};
+  build_clear_list(c, P, pl, A);
+  if ((rc = run_first_phase(c, P, pl, A)) != MN_OK) return rc;
+  if ((rc = run_round0(c, P, pl, A)) != MN_OK) return rc;
+  if ((rc = run_rounds(c, P, pl, A)) != MN_OK) return rc;
+  if ((rc = launch_finisher(c, P, pl, A, call)) != MN_OK) return rc;
+  if ((rc = launch_output(c, P, pl, A, call)) != MN_OK) return rc;
+  if ((rc = launch_certificate(c, P, pl, A)) != MN_OK) return rc;
+  c->last_params = P; c->last_valid = 1;
+  return close_attempt(c, call, pl, A, stats, defer);
+}
+
+// The image of last time again, through the same buffers: the sweep between its events, then the two graphs.
+static int replay_launch(mn_context* c, const ImageCall& call) {
+  ImgParams P;
+  const int rc = begin_call(c, call, true, nullptr, &P);
+  if (rc != MN_OK) return rc;
+  const hipStream_t st = call.stream;
+  c->debug_flags = call.opts.debug_flags;      // (deliberate carry-over: without MN_DEBUG_FLAGS_OR, unlike segment_attempt)
+  c->ext_events = !(call.opts.debug_flags & 2) && !(call.opts.debug_flags & 128);
+  c->cores_used = 0;
+  const bool timed = !(call.opts.debug_flags & 2) && !c->ext_events;
+  if (timed) MN_HIP(hipEventRecord(c->ev[0], st));
+  launch_sweep(c, P, st, sweep_px(c, P), true, true);      // (the key holds buffers and dtype: the recorded form)
+  if (timed) MN_HIP(hipEventRecord(c->ev[10], st));
+  MN_HIP(hipGraphLaunch(c->replay.eA, st));
+  MN_HIP(hipEventRecord(c->ev_fork, st));
+  MN_HIP(hipStreamWaitEvent(c->side, c->ev_fork, 0));
+  MN_HIP(hipGraphLaunch(c->replay.eB, c->side));
+  MN_HIP(hipEventRecord(c->ev_done, c->side));
+  c->last_params = P; c->last_valid = 1;
+  c->pend.queued = c->replay.queued;
+  memset(&c->pend.stats, 0, sizeof(c->pend.stats));
+  c->pend.active = 1;
+  return MN_OK;
 }
 
 // First half: queue everything for one image and return.  In components mode (the default for
@@ -1938,18 +2023,14 @@ extern "C" int mn_segment_launch_t(mn_context* c, const void* d_class_pred, int 
                                    int* d_object_class, int* d_partition, const mn_options* opts,
                                    void* stream) {
   if (!c || c->pend.active || !dtype_ok(dtype)) { g_last_status = MN_ERR_ARGUMENT; return MN_ERR_ARGUMENT; }
-  c->dtype = dtype;
   HostLaunchTimer host_timer;
   mn_context::Pending& q = c->pend;
-  if (opts) q.opts = *opts; else mn_default_options(&q.opts);
-  q.d_class = d_class_pred; q.class_dim = class_dim; q.d_adj = d_adj_pred; q.offset_dim = offset_dim;
-  q.W = W; q.H = H; q.num_classes = num_classes;
-  q.d_mask = d_mask; q.d_objcls = d_object_class; q.d_part = d_partition; q.stream = stream;
-  if (offset_list && offset_dim > 0 && offset_dim <= MN_MAX_OFFSETS)
-    memcpy(q.offs, offset_list, sizeof(int) * 2 * (size_t)offset_dim);
+  q.call = ImageCall{d_class_pred, d_adj_pred, dtype, class_dim, offset_dim, W, H, num_classes, d_mask, d_object_class, d_partition};
+  image_call(&q.call, offset_list, opts, stream);
+  const mn_options& o = q.call.opts;
   // ---- replay (debug_flags bit 5, with bit 4): see mn_context::Replay ----
   mn_context::Replay& rp = c->replay;
-  const bool want_replay = (q.opts.debug_flags & 32) && (q.opts.debug_flags & 16) && offset_list &&
+  const bool want_replay = (o.debug_flags & 32) && (o.debug_flags & 16) && offset_list &&
                            offset_dim > 0 && offset_dim <= MN_MAX_OFFSETS && W % 4 == 0;
   unsigned char key[256];
   size_t kb = 0;
@@ -1959,52 +2040,17 @@ extern "C" int mn_segment_launch_t(mn_context* c, const void* d_class_pred, int 
     const int dims[6] = {class_dim, offset_dim, W, H, num_classes, dtype};
     memcpy(key + kb, ptrs, sizeof(ptrs)); kb += sizeof(ptrs);
     memcpy(key + kb, dims, sizeof(dims)); kb += sizeof(dims);
-    memcpy(key + kb, &q.opts, sizeof(q.opts)); kb += sizeof(q.opts);
+    memcpy(key + kb, &o, sizeof(o)); kb += sizeof(o);
     const size_t ob = sizeof(int) * 2 * (size_t)offset_dim;
-    if (kb + ob <= sizeof(key)) { memcpy(key + kb, offset_list, ob); kb += ob; } else kb = 0;
+    if (kb + ob <= sizeof(key)) { memcpy(key + kb, q.call.offs, ob); kb += ob; } else kb = 0;
   }
   const bool same_key = want_replay && kb && rp.state >= 1 && rp.key_bytes == kb && memcmp(rp.key, key, kb) == 0;
-  if (same_key && rp.state == 2 && c->cc_clean) {
-    // the image of last time again, through the same buffers: sweep between its events, two graphs
-    int rc0 = check_args(c, class_dim, offset_dim, W, H, num_classes, offset_list, &q.opts);
-    if (rc0 != MN_OK) { g_last_status = rc0; return rc0; }
-    MN_HIP(hipSetDevice(c->device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    ImgParams P;
-    fill_params(&P, d_class_pred, d_adj_pred, dtype, offset_dim, W, H, num_classes, offset_list, &q.opts);
-    c->debug_flags = q.opts.debug_flags;
-    c->ext_events = !(q.opts.debug_flags & 2) && !(q.opts.debug_flags & 128);
-    c->cores_used = 0;
-    const bool timed = !(q.opts.debug_flags & 2) && !c->ext_events;
-    if (timed) MN_HIP(hipEventRecord(c->ev[0], st));
-    launch_sweep(c, P, st, sweep_px(c, P), true, true);      // (the key holds buffers and dtype: the recorded form)
-    if (timed) MN_HIP(hipEventRecord(c->ev[10], st));
-    MN_HIP(hipGraphLaunch(rp.eA, st));
-    MN_HIP(hipEventRecord(c->ev_fork, st));
-    MN_HIP(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-    MN_HIP(hipGraphLaunch(rp.eB, c->side));
-    MN_HIP(hipEventRecord(c->ev_done, c->side));
-    c->last_params = P;
-    c->last_valid = 1;
-    c->pend.mode = MN_MODE_COMPONENTS; c->pend.rounds = 0; c->pend.finish_limit = rp.finish_limit;
-    c->pend.N = P.N; c->pend.R0 = rp.R0; c->pend.speculate = true; c->pend.want_cert = rp.want_cert;
-    memset(&q.stats, 0, sizeof(q.stats));
-    q.active = 1;
-    return MN_OK;
-  }
-  if (want_replay && kb && !same_key) {          // a new key: forget the graphs of the old one
-    if (rp.eA) { (void)hipGraphExecDestroy(rp.eA); rp.eA = nullptr; }
-    if (rp.eB) { (void)hipGraphExecDestroy(rp.eB); rp.eB = nullptr; }
-    if (rp.gA) { (void)hipGraphDestroy(rp.gA); rp.gA = nullptr; }
-    if (rp.gB) { (void)hipGraphDestroy(rp.gB); rp.gB = nullptr; }
-    rp.state = 0;
-  }
+  if (same_key && rp.state == 2 && c->cc_clean) return replay_launch(c, q.call);
+  if (want_replay && kb && !same_key) drop_replay_graphs(rp);      // a new key: forget the graphs of the old one
   // second identical call in the steady state (the counters were cleared by the previous image): record
   rp.capturing = (same_key && rp.state == 1 && c->cc_clean) ? 1 : 0;
   const int was_clean = c->cc_clean;
-  const int rc = segment_attempt(c, d_class_pred, class_dim, d_adj_pred, offset_dim, W, H, num_classes,
-                                 offset_list, d_mask, d_object_class, d_partition, &q.opts, stream,
-                                 &q.stats, 0, true, true);
+  const int rc = segment_attempt(c, q.call, &q.stats, 0, true, true);
   if (rp.capturing) {              // the attempt did not take the fused path after all, or failed half-way
     hipGraph_t open_graph = nullptr;
     if (hipStreamEndCapture(rp.cap, &open_graph) == hipSuccess && open_graph) (void)hipGraphDestroy(open_graph);
@@ -2013,7 +2059,7 @@ extern "C" int mn_segment_launch_t(mn_context* c, const void* d_class_pred, int 
     rp.state = 0;
   }
   if (want_replay && kb && rp.state == 0 && rc == MN_PENDING && was_clean && c->cc_clean &&
-      q.opts.variant == MN_VARIANT_CSEGMENT && (W * H) % 4 == 0) {
+      o.variant == MN_VARIANT_CSEGMENT && (W * H) % 4 == 0) {
     memcpy(rp.key, key, kb);       // a fused speculative attempt in the steady state: the next one records
     rp.key_bytes = kb;
     rp.state = 1;
@@ -2041,12 +2087,12 @@ extern "C" int mn_segment_finish(mn_context* c, mn_stats* stats) {
   const double t_in = host_now_us();
   double t_synced = t_in;
   mn_context::Pending& q = c->pend;
+  const mn_options& o = q.call.opts;
   int rc;
   // require_proof: 1 = always, -1 = never, 0 = by mode -- AUTO hands back proven results only, an
   // explicitly requested ROUNDS / COMPONENTS run is taken as a request for that engine's answer
-  const bool explicit_mode = q.opts.mode == MN_MODE_EXACT || q.opts.mode == MN_MODE_ROUNDS ||
-                             q.opts.mode == MN_MODE_COMPONENTS;
-  const bool must_prove = q.opts.require_proof > 0 || (q.opts.require_proof == 0 && !explicit_mode);
+  const bool explicit_mode = o.mode == MN_MODE_EXACT || o.mode == MN_MODE_ROUNDS || o.mode == MN_MODE_COMPONENTS;
+  const bool must_prove = o.require_proof > 0 || (o.require_proof == 0 && !explicit_mode);
   if (q.active == 2) {
     rc = q.rc;
   } else {
@@ -2054,37 +2100,29 @@ extern "C" int mn_segment_finish(mn_context* c, mn_stats* stats) {
     MN_HIP(hipEventSynchronize(c->ev_done));
     t_synced = host_now_us();
     memset(&q.stats, 0, sizeof(q.stats));
-    rc = segment_read_back(c, &q.opts, q.mode, true, q.finish_limit, q.N, q.R0, q.rounds, q.want_cert,
-                           &q.stats);
+    rc = segment_read_back(c, &o, q.queued, &q.stats);
     // a speculative attempt that does not hold is redone: by the sequential order itself when the
     // caller wants a proven result and the input is not sign-separable (the rounds would only
     // approximate it), else on the ordinary path
     if (rc == MN_RETRY_ROUNDS && must_prove)
-      rc = segment_attempt(c, q.d_class, q.class_dim, q.d_adj, q.offset_dim, q.W, q.H, q.num_classes,
-                           q.offs, q.d_mask, q.d_objcls, q.d_part, &q.opts, q.stream, &q.stats,
-                           MN_MODE_EXACT, false);
+      rc = segment_attempt(c, q.call, &q.stats, MN_MODE_EXACT, false);
     else if (rc == MN_RETRY_ROUNDS || rc == MN_RETRY_WAIT)
-      rc = segment_attempt(c, q.d_class, q.class_dim, q.d_adj, q.offset_dim, q.W, q.H, q.num_classes,
-                           q.offs, q.d_mask, q.d_objcls, q.d_part, &q.opts, q.stream, &q.stats,
-                           rc == MN_RETRY_ROUNDS ? MN_MODE_ROUNDS : 0, false);
+      rc = segment_attempt(c, q.call, &q.stats, rc == MN_RETRY_ROUNDS ? MN_MODE_ROUNDS : 0, false);
   }
   // A result that is neither certified nor from the sequential order is only an approximation of the
   // reference's result on an order-dependent input: redone by the exact engine (any image size).
   if (rc == MN_OK && must_prove && q.stats.proof == 0) {
-    rc = segment_attempt(c, q.d_class, q.class_dim, q.d_adj, q.offset_dim, q.W, q.H, q.num_classes,
-                         q.offs, q.d_mask, q.d_objcls, q.d_part, &q.opts, q.stream, &q.stats,
-                         MN_MODE_EXACT, false);
+    rc = segment_attempt(c, q.call, &q.stats, MN_MODE_EXACT, false);
     if (rc == MN_ERR_CAPACITY) rc = MN_ERR_UNPROVEN;      // (no room for the engine's workspace)
     if (rc == MN_ERR_UNPROVEN) { q.stats.status = rc; g_last_status = rc; }
   }
   // require_proof = 1 does not take "the sequential order, equal priorities in creation order" for proven: the
   // image is redone in the reference's own order among equals (mn_reforder.h: slow, csegment variant only)
-  if (rc == MN_OK && q.opts.require_proof > 0 && q.stats.proof == MN_PROOF_SEQUENTIAL_TIES) {
-    if (q.opts.variant == MN_VARIANT_CSEGMENT) {
-      mn_options o2 = q.opts;
-      o2.tie_order = MN_TIES_REFERENCE;
-      rc = segment_attempt(c, q.d_class, q.class_dim, q.d_adj, q.offset_dim, q.W, q.H, q.num_classes,
-                           q.offs, q.d_mask, q.d_objcls, q.d_part, &o2, q.stream, &q.stats, MN_MODE_EXACT, false);
+  if (rc == MN_OK && o.require_proof > 0 && q.stats.proof == MN_PROOF_SEQUENTIAL_TIES) {
+    if (o.variant == MN_VARIANT_CSEGMENT) {
+      ImageCall again = q.call;
+      again.opts.tie_order = MN_TIES_REFERENCE;
+      rc = segment_attempt(c, again, &q.stats, MN_MODE_EXACT, false);
       if (rc == MN_ERR_CAPACITY) rc = MN_ERR_UNPROVEN;
     } else {
       rc = MN_ERR_UNPROVEN;            // (the Python variant's heapq / dict order is not restated)
@@ -2129,9 +2167,10 @@ extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void
                                         int num_classes, const int* offset_list, int* const* d_mask,
                                         int* const* d_object_class, int* const* d_partition, const mn_options* opts,
                                         void* stream, mn_stats* stats) {
-  mn_options o;
-  if (opts) o = *opts; else mn_default_options(&o);
-  o.mode = MN_MODE_EXACT;
+  ImageCall shared = {nullptr, nullptr, dtype, class_dim, offset_dim, W, H, num_classes};   // (maps and outputs: per image, below)
+  image_call(&shared, offset_list, opts, stream);
+  shared.opts.mode = MN_MODE_EXACT;
+  const mn_options& o = shared.opts;
   if (!ctxs || count <= 0 || count > 4096 || !d_class_pred || !d_adj_pred || !d_mask || !d_object_class ||
       !dtype_ok(dtype)) {
     g_last_status = MN_ERR_ARGUMENT;
@@ -2140,7 +2179,7 @@ extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void
   for (int i = 0; i < count; i++) {
     if (!ctxs[i] || ctxs[i]->pend.active || ctxs[i]->device != ctxs[0]->device) { g_last_status = MN_ERR_ARGUMENT; return MN_ERR_ARGUMENT; }
     for (int j = 0; j < i; j++) if (ctxs[j] == ctxs[i]) { g_last_status = MN_ERR_ARGUMENT; return MN_ERR_ARGUMENT; }
-    const int rc = check_args(ctxs[i], class_dim, offset_dim, W, H, num_classes, offset_list, &o);
+    const int rc = check_args(ctxs[i], shared);
     if (rc != MN_OK || !d_class_pred[i] || !d_adj_pred[i] || !d_mask[i] || !d_object_class[i]) {
       g_last_status = rc != MN_OK ? rc : MN_ERR_ARGUMENT;
       return g_last_status;
@@ -2148,12 +2187,19 @@ extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void
   }
   MN_HIP(hipSetDevice(ctxs[0]->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  ImgParams* Ps = static_cast<ImgParams*>(malloc((size_t)count * sizeof(ImgParams)));
-  if (!Ps) return MN_ERR_INTERNAL;
+  // (require_proof reads every image's verdict after the hand-over: statistics are kept also when the caller wants none)
+  HostBuf<mn_stats> own_stats((!stats && o.require_proof > 0) ? (size_t)count : 0);
+  mn_stats* out = stats ? stats : (o.require_proof > 0 ? (mn_stats*)own_stats : nullptr);
+  HostBuf<ImageCall> calls((size_t)count); HostBuf<ImgParams> Ps((size_t)count), rc_P((size_t)count);
+  HostBuf<mn_context*> rc_ctx((size_t)count); HostBuf<unsigned char> redo((size_t)count); HostBuf<int> rc_idx((size_t)count);
+  if (!calls.ok() || !Ps.ok() || !rc_P.ok() || !rc_ctx.ok() || !redo.ok() || !rc_idx.ok() || !own_stats.ok())
+    return g_last_status = MN_ERR_INTERNAL;
   int rc = MN_OK;
   for (int i = 0; i < count; i++) {
-    ctxs[i]->dtype = dtype;
-    fill_params(&Ps[i], d_class_pred[i], d_adj_pred[i], dtype, offset_dim, W, H, num_classes, offset_list, &o);
+    calls[i] = shared;
+    calls[i].d_class = d_class_pred[i]; calls[i].d_adj = d_adj_pred[i];
+    calls[i].d_mask = d_mask[i]; calls[i].d_objcls = d_object_class[i]; calls[i].d_part = d_partition ? d_partition[i] : nullptr;
+    fill_params(&Ps[i], calls[i]);
   }
   {
     // more images than compute units: two workgroups per unit if each keeps its LDS under half of it
@@ -2168,7 +2214,7 @@ extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void
   const bool ref_only = ref_possible && o.tie_order == MN_TIES_REFERENCE;
   if (!ref_only) rc = exact_run(ctxs, count, Ps, st);
   for (int i = 0; i < count; i++) ctxs[i]->xw.max_blocks = 0;
-  if (rc != MN_OK) { free(Ps); g_last_status = rc; return rc; }
+  if (rc != MN_OK) { g_last_status = rc; return rc; }
   // The tie policy, as a single call applies it: images whose tied choices conflict (or all, with
   // MN_TIES_REFERENCE) are redone in the reference's order among equals -- TOGETHER, one workgroup per image in one
   // launch of that loop.  Inside a batch the loop's cost is shared, so the size limit is higher than for a single
@@ -2176,41 +2222,18 @@ extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void
   long long tie_limit = MN_TIE_LIMIT_BATCH_RECORDS;
   if (const char* e = getenv("MN_TIE_LIMIT")) tie_limit = atoll(e);
   int n_redo = 0;
-  mn_context** rc_ctx = static_cast<mn_context**>(malloc((size_t)count * sizeof(mn_context*)));
-  ImgParams* rc_P = static_cast<ImgParams*>(malloc((size_t)count * sizeof(ImgParams)));
-  struct Saved { long long ts, tm, tc; int tt; };
-  Saved* saved = static_cast<Saved*>(malloc((size_t)count * sizeof(Saved)));
-  unsigned char* redo = static_cast<unsigned char*>(calloc((size_t)count, 1));
-  int* rc_idx = static_cast<int*>(malloc((size_t)count * sizeof(int)));
-  // (require_proof reads every image's verdict after the hand-over: statistics are kept also when the caller wants none)
-  mn_stats* own_stats = (!stats && o.require_proof > 0) ? static_cast<mn_stats*>(calloc((size_t)count, sizeof(mn_stats))) : nullptr;
-  mn_stats* out = stats ? stats : own_stats;
-  auto release = [&]() { free(Ps); free(rc_ctx); free(rc_P); free(saved); free(redo); free(rc_idx); free(own_stats); };
-  if (!rc_ctx || !rc_P || !saved || !redo || !rc_idx || (o.require_proof > 0 && !out)) rc = MN_ERR_INTERNAL;
-  for (int i = 0; i < count && rc == MN_OK; i++) {
+  for (int i = 0; i < count; i++) {
     redo[i] = ref_only || (ref_possible && o.tie_order == MN_TIES_DEFAULT && x_ties_unresolved(ctxs[i]->xw.h_ctl) &&
                            (long long)W * H * offset_dim <= tie_limit);
     if (!redo[i]) continue;
-    if (!ref_only) {
-      const XCtl* h = ctxs[i]->xw.h_ctl;
-      saved[n_redo] = Saved{h->tied_steps, h->tied_merges, h->tied_conflicts, h->ttrack};
-    }
     rc_ctx[n_redo] = ctxs[i]; rc_P[n_redo] = Ps[i]; n_redo++;
   }
-  if (rc == MN_OK && n_redo > 0) {
-    rc = run_reforder_batch(rc_ctx, n_redo, rc_P, st);
-    for (int j = 0; j < n_redo && rc == MN_OK && !ref_only; j++) {
-      XCtl* h = rc_ctx[j]->xw.h_ctl;                   // (what the exact engine met)
-      h->tied_steps = saved[j].ts; h->tied_merges = saved[j].tm; h->tied_conflicts = saved[j].tc; h->ttrack = saved[j].tt;
-    }
-  }
-  if (rc != MN_OK) { release(); g_last_status = rc; return rc; }
+  if (n_redo > 0) rc = redo_in_reference_order(rc_ctx, n_redo, rc_P, st, !ref_only);
+  if (rc != MN_OK) { g_last_status = rc; return rc; }
   // hand-over and output stage of every image (labels, mask, class table, certificate, log-likelihood)
   for (int i = 0; i < count; i++) {
     ctxs[i]->xw.prerun = redo[i] ? 2 : 1;
-    const int r = segment_attempt(ctxs[i], d_class_pred[i], class_dim, d_adj_pred[i], offset_dim, W, H, num_classes,
-                                  offset_list, d_mask[i], d_object_class[i], d_partition ? d_partition[i] : nullptr,
-                                  &o, stream, out ? &out[i] : nullptr, MN_MODE_EXACT, false);
+    const int r = segment_attempt(ctxs[i], calls[i], out ? &out[i] : nullptr, MN_MODE_EXACT, false);
     ctxs[i]->xw.prerun = 0;
     if (r != MN_OK && rc == MN_OK) rc = r;
   }
@@ -2228,33 +2251,24 @@ extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void
         if (rc == MN_OK) rc = MN_ERR_UNPROVEN;
         continue;
       }
-      const XCtl* h = ctxs[i]->xw.h_ctl;
-      saved[n2] = Saved{h->tied_steps, h->tied_merges, h->tied_conflicts, h->ttrack};
       rc_ctx[n2] = ctxs[i]; rc_P[n2] = Ps[i]; rc_idx[n2] = i; n2++;
     }
-    if (n2 > 0) {
-      const int r2 = run_reforder_batch(rc_ctx, n2, rc_P, st);
-      if (r2 == MN_ERR_CAPACITY) {
-        for (int j = 0; j < n2; j++) out[rc_idx[j]].status = MN_ERR_UNPROVEN;
-        if (rc == MN_OK) rc = MN_ERR_UNPROVEN;
-      } else if (r2 != MN_OK) {
-        release(); g_last_status = r2; return r2;
-      } else {
-        for (int j = 0; j < n2; j++) {
-          const int i = rc_idx[j];
-          XCtl* h = ctxs[i]->xw.h_ctl;                 // (what the exact engine met)
-          h->tied_steps = saved[j].ts; h->tied_merges = saved[j].tm; h->tied_conflicts = saved[j].tc; h->ttrack = saved[j].tt;
-          ctxs[i]->xw.prerun = 2;
-          const int r = segment_attempt(ctxs[i], d_class_pred[i], class_dim, d_adj_pred[i], offset_dim, W, H, num_classes,
-                                        offset_list, d_mask[i], d_object_class[i], d_partition ? d_partition[i] : nullptr,
-                                        &o, stream, &out[i], MN_MODE_EXACT, false);
-          ctxs[i]->xw.prerun = 0;
-          if (r != MN_OK && rc == MN_OK) rc = r;
-        }
-      }
+    const int r2 = n2 > 0 ? redo_in_reference_order(rc_ctx, n2, rc_P, st, true) : MN_OK;
+    if (r2 == MN_ERR_CAPACITY) {
+      for (int j = 0; j < n2; j++) out[rc_idx[j]].status = MN_ERR_UNPROVEN;
+      if (rc == MN_OK) rc = MN_ERR_UNPROVEN;
+    } else if (r2 != MN_OK) {
+      g_last_status = r2;
+      return r2;
+    }
+    for (int j = 0; j < n2 && r2 == MN_OK; j++) {
+      const int i = rc_idx[j];
+      ctxs[i]->xw.prerun = 2;
+      const int r = segment_attempt(ctxs[i], calls[i], &out[i], MN_MODE_EXACT, false);
+      ctxs[i]->xw.prerun = 0;
+      if (r != MN_OK && rc == MN_OK) rc = r;
     }
   }
-  release();
   g_last_status = rc;
   return rc;
 }
@@ -2275,21 +2289,15 @@ extern "C" int mn_score_device_t(mn_context* c, const void* d_class_pred, int cl
                                  void* stream, unsigned char* d_cls_out,
                                  unsigned long long* d_best_out, float* ms_class_pass,
                                  float* ms_edge_pass) {
-  mn_options defaults;
-  if (!opts) { mn_default_options(&defaults); opts = &defaults; }
-  int rc = check_args(c, class_dim, offset_dim, W, H, num_classes, offset_list, opts);
-  if (rc == MN_OK && (!d_class_pred || !d_adj_pred || !dtype_ok(dtype))) rc = MN_ERR_ARGUMENT;
-  if (rc != MN_OK) { g_last_status = rc; return rc; }
-  MN_HIP(hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  c->dtype = dtype;
+  ImageCall call = {d_class_pred, d_adj_pred, dtype, class_dim, offset_dim, W, H, num_classes};
+  image_call(&call, offset_list, opts, stream);
   ImgParams P;
-  fill_params(&P, d_class_pred, d_adj_pred, dtype, offset_dim, W, H, num_classes, offset_list, opts);
-  c->debug_flags = opts->debug_flags;
-  rc = ensure_fast(c);
+  int rc = begin_call(c, call, true, nullptr, &P);
   if (rc != MN_OK) return rc;
-  rc = run_phase_a(c, P, st, true);
-  if (rc != MN_OK) return rc;
+  const hipStream_t st = call.stream;
+  // (deliberate carry-over: the flags as given, without MN_DEBUG_FLAGS_OR; ext_events and core_radius as the last call left them)
+  c->debug_flags = call.opts.debug_flags;
+  if ((rc = ensure_fast(c)) != MN_OK || (rc = run_phase_a(c, P, st, true)) != MN_OK) return rc;
   if (d_cls_out) MN_HIP(hipMemcpyAsync(d_cls_out, c->ocls, P.N, hipMemcpyDeviceToDevice, st));
   if (d_best_out)
     MN_HIP(hipMemcpyAsync(d_best_out, c->ball, (size_t)P.N * sizeof(u64), hipMemcpyDeviceToDevice, st));
@@ -2320,19 +2328,15 @@ extern "C" int mn_sweep_device_t(mn_context* c, const void* d_class_pred, int cl
                                  const int* offset_list, const mn_options* opts, void* stream,
                                  unsigned* d_bits_out, float* d_neg_out, unsigned char* d_cls_out,
                                  int* d_gsum_out, double* logsum_out, int* info_out) {
-  mn_options defaults;
-  if (!opts) { mn_default_options(&defaults); opts = &defaults; }
-  int rc = check_args(c, class_dim, offset_dim, W, H, num_classes, offset_list, opts);
-  if (rc == MN_OK && (!d_class_pred || !d_adj_pred || !d_bits_out || !d_neg_out || !dtype_ok(dtype))) rc = MN_ERR_ARGUMENT;
-  if (rc != MN_OK) { g_last_status = rc; return rc; }
-  MN_HIP(hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  c->dtype = dtype;
+  ImageCall call = {d_class_pred, d_adj_pred, dtype, class_dim, offset_dim, W, H, num_classes};
+  image_call(&call, offset_list, opts, stream);
   ImgParams P;
-  fill_params(&P, d_class_pred, d_adj_pred, dtype, offset_dim, W, H, num_classes, offset_list, opts);
+  const int rc = begin_call(c, call, d_bits_out && d_neg_out, nullptr, &P);
+  if (rc != MN_OK) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
   const int N = P.N;
-  if (ensure_fast(c) != MN_OK) return MN_ERR_NO_DEVICE;
-  c->debug_flags = opts->debug_flags | 2;          // (no events)
+  if (ensure_fast(c) != MN_OK) return MN_ERR_NO_DEVICE;      // (deliberate carry-over: any failure reads as "no device" here)
+  c->debug_flags = call.opts.debug_flags | 2;      // (no events)
   c->ext_events = 0;
   c->cc_clean = 0;
   const int px = sweep_px(c, P);                // (4 pixels per lane: also with W % 4 != 0, see run_components)
@@ -2350,14 +2354,13 @@ extern "C" int mn_sweep_device_t(mn_context* c, const void* d_class_pred, int cl
   if (d_gsum_out && fused_cls)          // (plane c of the sweep's products starts at c * N ints and holds N / 4 of them)
     MN_HIP(hipMemcpy2DAsync(d_gsum_out, (size_t)(N / 4) * sizeof(int), c->lpsum, gsum_stride(N) * sizeof(int),
                             (size_t)(N / 4) * sizeof(int), (size_t)P.C, hipMemcpyDeviceToDevice, st));
-  double* hp = static_cast<double*>(malloc(sign_waves * 2 * sizeof(double)));
-  if (!hp) return MN_ERR_INTERNAL;
+  HostBuf<double> hp(sign_waves * 2);
+  if (!hp.ok()) return MN_ERR_INTERNAL;
   MN_HIP(hipMemcpyAsync(hp, c->partial, sign_waves * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
   MN_HIP(hipMemcpyAsync(c->h_scalars, c->scalars, MN_NSCALARS * sizeof(int), hipMemcpyDeviceToHost, st));
   MN_HIP(hipStreamSynchronize(st));
   double t = 0.0;
   for (size_t b = 0; b < sign_waves; b++) t += hp[2 * b];
-  free(hp);
   if (logsum_out) *logsum_out = t;
   if (info_out) { info_out[0] = px; info_out[1] = fused_cls ? 1 : 0; info_out[2] = c->h_scalars[6]; }
   MN_HIP(hipGetLastError());
@@ -2365,9 +2368,6 @@ extern "C" int mn_sweep_device_t(mn_context* c, const void* d_class_pred, int cl
   return MN_OK;
 }
 
-// Timing of the sweep alone (tuning; see include/mergenet_hip.h): `reps` launches back to back on `stream`,
-// input set i % n_inputs for launch i, in the form the default path launches it.  Returns the average time per
-// launch by HIP events around the whole train (launch gaps of consecutive kernels included).
 extern "C" int mn_sweep_device(mn_context* c, const float* d_class_pred, int class_dim,
                                const float* d_adj_pred, int offset_dim, int W, int H, int num_classes,
                                const int* offset_list, const mn_options* opts, void* stream,
@@ -2377,30 +2377,32 @@ extern "C" int mn_sweep_device(mn_context* c, const float* d_class_pred, int cla
                            offset_list, opts, stream, d_bits_out, d_neg_out, d_cls_out, d_gsum_out, logsum_out, info_out);
 }
 
+// Timing of the sweep alone (tuning; see include/mergenet_hip.h): `reps` launches back to back on `stream`,
+// input set i % n_inputs for launch i, in the form the default path launches it.  Returns the average time per
+// launch by HIP events around the whole train (launch gaps of consecutive kernels included).
 extern "C" int mn_sweep_time_device_t(mn_context* c, const void* const* d_class_pred, const void* const* d_adj_pred,
                                       int dtype, int n_inputs, int class_dim, int offset_dim, int W, int H,
                                       int num_classes, const int* offset_list, const mn_options* opts, void* stream,
                                       int reps, float* us_per_launch) {
-  mn_options defaults;
-  if (!opts) { mn_default_options(&defaults); opts = &defaults; }
-  int rc = check_args(c, class_dim, offset_dim, W, H, num_classes, offset_list, opts);
-  if (rc == MN_OK && (!d_class_pred || !d_adj_pred || n_inputs < 1 || reps < 1 || !us_per_launch || !dtype_ok(dtype)))
-    rc = MN_ERR_ARGUMENT;
-  if (rc != MN_OK) { g_last_status = rc; return rc; }
-  MN_HIP(hipSetDevice(c->device));
+  // (the first pair of maps stands for all in the shared checks, which newly reject a null one; each launch fills in its own)
+  const bool ok = d_class_pred && d_adj_pred && n_inputs >= 1 && reps >= 1 && us_per_launch;
+  ImageCall call = {ok ? d_class_pred[0] : nullptr, ok ? d_adj_pred[0] : nullptr, dtype, class_dim, offset_dim, W, H, num_classes};
+  image_call(&call, offset_list, opts, stream);
+  ImgParams P;
+  const int rc = begin_call(c, call, ok, nullptr, &P);
+  if (rc != MN_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (ensure_fast(c) != MN_OK) return MN_ERR_NO_DEVICE;
-  c->debug_flags = opts->debug_flags | 2;          // (no events inside)
+  if (ensure_fast(c) != MN_OK) return MN_ERR_NO_DEVICE;      // (deliberate carry-over: any failure reads as "no device" here)
+  c->debug_flags = call.opts.debug_flags | 2;      // (no events inside)
   c->ext_events = 0;
   c->cc_clean = 0;
-  c->dtype = dtype;
   MN_HIP(hipMemsetAsync(c->scalars, 0, MN_NSCALARS * sizeof(int), st));
   for (int phase = 0; phase < 2; phase++) {          // a tenth of the launches untimed first
     const int n = phase == 0 ? (reps + 9) / 10 : reps;
     if (phase == 1) MN_HIP(hipEventRecord(c->ev[0], st));
     for (int i = 0; i < n; i++) {
-      ImgParams P;
-      fill_params(&P, d_class_pred[i % n_inputs], d_adj_pred[i % n_inputs], dtype, offset_dim, W, H, num_classes, offset_list, opts);
+      call.d_class = d_class_pred[i % n_inputs]; call.d_adj = d_adj_pred[i % n_inputs];
+      fill_params(&P, call);
       launch_sweep(c, P, st, sweep_px(c, P), true, true);
     }
     if (phase == 1) MN_HIP(hipEventRecord(c->ev[1], st));
@@ -2414,8 +2416,6 @@ extern "C" int mn_sweep_time_device_t(mn_context* c, const void* const* d_class_
   return MN_OK;
 }
 
-// Phase A of the exact engine (tests): log-odds and initial priority of every record in the layout
-// of the oracle's phase-A export ([offset][source pixel], NaN outside the image), arg-max classes.
 extern "C" int mn_sweep_time_device(mn_context* c, const float* const* d_class_pred, const float* const* d_adj_pred,
                                     int n_inputs, int class_dim, int offset_dim, int W, int H, int num_classes,
                                     const int* offset_list, const mn_options* opts, void* stream, int reps,
@@ -2425,23 +2425,21 @@ extern "C" int mn_sweep_time_device(mn_context* c, const float* const* d_class_p
                                 offset_dim, W, H, num_classes, offset_list, opts, stream, reps, us_per_launch);
 }
 
+// Phase A of the exact engine (tests): log-odds and initial priority of every record in the layout
+// of the oracle's phase-A export ([offset][source pixel], NaN outside the image), arg-max classes.
 extern "C" int mn_exact_phase_a_device_t(mn_context* c, const void* d_class_pred, int class_dim,
                                          const void* d_adj_pred, int offset_dim, int dtype, int W, int H,
                                          int num_classes, const int* offset_list, const mn_options* opts,
                                          void* stream, unsigned char* d_cls_out, float* d_oml_out,
                                          float* d_prio_out) {
-  mn_options defaults;
-  if (!opts) { mn_default_options(&defaults); opts = &defaults; }
-  int rc = check_args(c, class_dim, offset_dim, W, H, num_classes, offset_list, opts);
-  if (rc == MN_OK && (!d_class_pred || !d_adj_pred || !d_oml_out || !d_prio_out || !dtype_ok(dtype))) rc = MN_ERR_ARGUMENT;
-  if (rc != MN_OK) { g_last_status = rc; return rc; }
-  MN_HIP(hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  c->dtype = dtype;
+  ImageCall call = {d_class_pred, d_adj_pred, dtype, class_dim, offset_dim, W, H, num_classes};
+  image_call(&call, offset_list, opts, stream);
   ImgParams P;
-  fill_params(&P, d_class_pred, d_adj_pred, dtype, offset_dim, W, H, num_classes, offset_list, opts);
-  rc = exact_setup(c, P, st);
-  if (rc != MN_OK) { g_last_status = rc; return rc; }
+  int rc = begin_call(c, call, d_oml_out && d_prio_out, nullptr, &P);
+  if (rc != MN_OK) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // (deliberate carry-over: debug_flags is not set here -- nothing below reads it)
+  if ((rc = exact_setup(c, P, st)) != MN_OK) { g_last_status = rc; return rc; }
   hipLaunchKernelGGL(mn_x_export_phase_a, dim3(grid_for((size_t)P.N * P.O, 256)), dim3(256), 0, st, P, c->xw.X,
                      d_oml_out, d_prio_out, d_cls_out);
   MN_HIP(hipGetLastError());
@@ -2473,9 +2471,10 @@ extern "C" int mn_segment_host(mn_context* c, const float* class_pred, int class
                                const float* adj_pred, int offset_dim, int W, int H, int num_classes,
                                const int* offset_list, int* mask, int* object_class, int* partition,
                                const mn_options* opts, mn_stats* stats) {
-  mn_options defaults;
-  if (!opts) { mn_default_options(&defaults); opts = &defaults; }
-  int rc = check_args(c, class_dim, offset_dim, W, H, num_classes, offset_list, opts);
+  ImageCall call = {class_pred, adj_pred, MN_DTYPE_F32, class_dim, offset_dim, W, H, num_classes};
+  image_call(&call, offset_list, opts, NULL);
+  opts = &call.opts;
+  int rc = check_args(c, call);
   if (rc == MN_OK && (!class_pred || !adj_pred || !mask || !object_class)) rc = MN_ERR_ARGUMENT;
   if (rc != MN_OK) { g_last_status = rc; if (stats) { memset(stats, 0, sizeof(*stats)); stats->status = rc; } return rc; }
   MN_HIP(hipSetDevice(c->device));
