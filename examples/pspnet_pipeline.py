@@ -7,7 +7,9 @@ shape with random weights: a plumbing / throughput configuration, not a model-pa
 The hand-off is device resident: sigmoid outputs (utils/inference_utils.py:44,96) -> Merger with
 the binding's clip fused into the loads; no .npy files (utils/inference_utils.py:122-126), no host
 copy.  Under autocast (--dtype bfloat16 | float16, the default here) the network writes 16-bit maps and
-the merger reads them in that width: no float32 copy in between either.
+the merger reads them in that width: no float32 copy in between either.  With --logits there is no
+torch.sigmoid pass either: the network's output goes to the merger as it is and the kernels take the sigmoid,
+in float32, where they load an element (a 16-bit logit keeps its own probability up to a logit of about 17).
 """
 
 from __future__ import annotations
@@ -81,18 +83,23 @@ class PSPNetResNet50(nn.Module):
 
 
 @torch.no_grad()
-def segment_image(model: PSPNetResNet50, image, offsets, merger, opts, dtype=None):
+def segment_image(model: PSPNetResNet50, image, offsets, merger, opts, dtype=None, logits=False):
     """image [1,3,H,W] on the GPU -> (mask, class_table, stats); everything stays on the device.
     dtype: torch.bfloat16 / torch.float16 runs the model under autocast and hands its 16-bit sigmoid
-    outputs to the merger as they are; None: float32 throughout."""
+    outputs to the merger as they are; None: float32 throughout.
+    logits: the network's output goes to the merger as it is (in `dtype`), which takes the sigmoid on load."""
     if dtype is None or dtype == torch.float32:
-        probs = torch.sigmoid(model(image)[0]).float()           # inference_utils.py:44,96
+        maps = model(image)[0].float()
+        if not logits:
+            maps = torch.sigmoid(maps)                           # inference_utils.py:44,96
     else:
         with torch.autocast("cuda", dtype=dtype):
-            probs = torch.sigmoid(model(image)[0])               # stays 16 bit: the merger widens on load
+            maps = model(image)[0]                               # stays 16 bit: the merger widens on load
+            if not logits:
+                maps = torch.sigmoid(maps)
     C = model.num_classes
     # (slices along the first axis of a contiguous tensor are contiguous: views, not copies)
-    return merger.segment(probs[:C], probs[C:], offsets, opts)
+    return merger.segment(maps[:C], maps[C:], offsets, opts, logits=logits)
 
 
 if __name__ == "__main__":
@@ -102,6 +109,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("size", nargs="*", type=int, default=[512, 1024], help="H W")
     ap.add_argument("--dtype", choices=["bfloat16", "float16", "float32"], default="bfloat16")
+    ap.add_argument("--logits", action="store_true", help="hand the logits to the merger: no torch.sigmoid pass")
     args = ap.parse_args()
     H, W = args.size[0], args.size[1]
     dtype = getattr(torch, args.dtype)
@@ -113,7 +121,8 @@ if __name__ == "__main__":
     opts = seg.default_options(clip_inputs=1, mode=seg.MN_MODE_ROUNDS)
     for _ in range(2):
         torch.cuda.synchronize(); t = time.perf_counter()
-        mask, table, _, st = segment_image(model, img, offs, merger, opts, dtype=dtype)
+        mask, table, _, st = segment_image(model, img, offs, merger, opts, dtype=dtype, logits=args.logits)
         torch.cuda.synchronize(); dt = time.perf_counter() - t
-    print("PSPNet-ResNet50 forward + merge %dx%d, maps in %s: %.1f ms (merger %.1f ms), %d instances"
-          % (H, W, args.dtype, dt * 1e3, st["ms_total"], st["num_instances"]))
+    print("PSPNet-ResNet50 forward + merge %dx%d, %s in %s: %.1f ms (merger %.1f ms), %d instances"
+          % (H, W, "logits" if args.logits else "probabilities", args.dtype, dt * 1e3, st["ms_total"],
+             st["num_instances"]))

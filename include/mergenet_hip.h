@@ -331,7 +331,22 @@ int mn_exact_phase_a_device(mn_context* ctx, const float* d_class_pred, int clas
  * mn_sweep_device_t is then 8), which regroups the float products behind total_logprob / logsum_out: those
  * agree to rounding (1e-5 relative), everything else bit for bit.  The float entry points are one-line calls
  * of these with MN_DTYPE_F32; mn_segment_finish serves both.  c_run_segmentation and mn_segment_host stay
- * float32 only. */
+ * float32 only.
+ *
+ * LOGITS.  The reference's two networks emit logits and put a sigmoid behind them (utils/inference_utils.py:
+ * 44,96).  MN_MAPS_LOGITS or-ed into `dtype` (the low byte stays the element type) says that BOTH maps of the
+ * call hold logits: every kernel then takes p = 1.0f / (1.0f + expf(-(float)x)) where it loads an element, in
+ * float32 after the exact widening, and no probability copy of the maps is made.  The call gives bit for bit
+ * what it gives on those p as float32 maps with clip_inputs = 1 -- what mn_prepare_device_t(..., apply_sigmoid
+ * = 1, clip = 0) writes at unchanged size -- with the one regrouping above where 16-bit logits take 8 pixels
+ * per lane (the rule looks at the element type only).  Logits are ALWAYS clipped on load, whatever clip_inputs
+ * says: the float32 sigmoid is exactly 1.0 from about 17 up and 0 below about -104.  +-inf are legal logits,
+ * NaN is undefined as for probabilities.  same_different_bias is applied to the probability, as ever.  A
+ * 16-bit logit keeps a distinct probability per distinct logit up to about 17, where a 16-bit probability
+ * above 0.5 has 128 (bfloat16) values and is 1.0 from a logit of about 5.5.  The seven entry points below
+ * this line and above mn_prepare_device_t take the flag; mn_prepare_device_t has apply_sigmoid of its own and
+ * refuses it in either dtype (MN_ERR_ARGUMENT), the float entry points stay probabilities only. */
+#define MN_MAPS_LOGITS 0x100
 int mn_segment_device_t(mn_context* ctx, const void* d_class_pred, int class_dim, const void* d_adj_pred,
                         int offset_dim, int dtype, int img_width, int img_height, int num_classes,
                         const int* offset_list, int* d_mask, int* d_object_class, int* d_partition,

@@ -60,7 +60,7 @@ struct HostBuf {
 // One image call as an entry point received it.  The entry sets the maps, the shape and the outputs; image_call the rest.
 struct ImageCall {
   const void *d_class, *d_adj;   // maps, elements of `dtype`
-  int dtype;                     // enum mn_dtype
+  int dtype;                     // enum mn_dtype, | MN_MAPS_LOGITS when the maps hold logits (fill_params splits it)
   int class_dim, offset_dim, W, H, num_classes;
   int *d_mask, *d_objcls, *d_part;
   hipStream_t stream;
@@ -577,7 +577,13 @@ static int check_args(const mn_context* c, const ImageCall& call) {
   return MN_OK;
 }
 
-static inline bool dtype_ok(int dtype) { return dtype == MN_DTYPE_F32 || dtype == MN_DTYPE_F16 || dtype == MN_DTYPE_BF16; }
+// `dtype` as an entry point takes it: the element type in the low byte, for the entries that read maps
+// (`logits_allowed`) optionally MN_MAPS_LOGITS above it; any other bit is an unknown dtype.
+static inline bool dtype_ok(int dtype, bool logits_allowed) {
+  if (dtype & ~(0xFF | (logits_allowed ? MN_MAPS_LOGITS : 0))) return false;
+  const int elem = dtype & 0xFF;
+  return elem == MN_DTYPE_F32 || elem == MN_DTYPE_F16 || elem == MN_DTYPE_BF16;
+}
 
 // A null offset list is only noted (check_args rejects the call before `offs` is read), as is an offset_dim out of range.
 static void image_call(ImageCall* call, const int* offset_list, const mn_options* opts, void* stream) {
@@ -589,14 +595,16 @@ static void image_call(ImageCall* call, const int* offset_list, const mn_options
 }
 
 static void fill_params(ImgParams* P, const ImageCall& call) {
-  const int dtype = call.dtype, offset_dim = call.offset_dim, W = call.W, H = call.H;
+  const int dtype = call.dtype & 0xFF, logits = (call.dtype & MN_MAPS_LOGITS) ? 1 : 0;
+  const int offset_dim = call.offset_dim, W = call.W, H = call.H;
   const mn_options* o = &call.opts;
   memset(P, 0, sizeof(*P));
   P->H = H; P->W = W; P->N = W * H; P->C = call.num_classes; P->O = offset_dim;
   P->sdb = o->same_different_bias; P->omf = o->object_merge_factor; P->bias = o->merge_logprob_bias;
-  // a 16-bit map cannot hold 1 - 2^-23 and a saturated sigmoid is exactly 1.0 in it: always clipped on load
-  P->variant = o->variant; P->clip = (o->clip_inputs || dtype != MN_DTYPE_F32) ? 1 : 0;
-  P->dtype = dtype;
+  // a 16-bit map cannot hold 1 - 2^-23 and a saturated sigmoid is exactly 1.0 in it: always clipped on load;
+  // so are logits: the float32 sigmoid taken on load is exactly 1.0 from about 17 up and 0 below about -104
+  P->variant = o->variant; P->clip = (o->clip_inputs || dtype != MN_DTYPE_F32 || logits) ? 1 : 0;
+  P->dtype = dtype; P->logits = logits;
   P->cls = call.d_class; P->same = call.d_adj;
   P->djmin = 0; P->djmax = 0;
   for (int k = 0; k < offset_dim; k++) {
@@ -639,7 +647,7 @@ static void fill_params(ImgParams* P, const ImageCall& call) {
 // segment_attempt and the replay branch: the checks of the maps and the element type; their callers make them first.)
 static int begin_call(mn_context* c, const ImageCall& call, bool entry_ok, mn_stats* stats, ImgParams* P) {
   int rc = check_args(c, call);
-  if (rc == MN_OK && (!call.d_class || !call.d_adj || !dtype_ok(call.dtype) || !entry_ok)) rc = MN_ERR_ARGUMENT;
+  if (rc == MN_OK && (!call.d_class || !call.d_adj || !dtype_ok(call.dtype, true) || !entry_ok)) rc = MN_ERR_ARGUMENT;
   if (stats) { memset(stats, 0, sizeof(*stats)); stats->status = rc; stats->total_logprob = NAN; }
   if (rc != MN_OK) { g_last_status = rc; return rc; }
   MN_HIP(hipSetDevice(c->device));
@@ -804,8 +812,8 @@ static size_t gsum_stride(int N) {
 #endif
 }
 
-// The sweep (mn_cc_sign) in the form for PX pixels per lane and maps of element type DT.
-template <int PX, int DT>
+// The sweep (mn_cc_sign) in the form for PX pixels per lane and maps of element type DT (LG: holding logits).
+template <int PX, int DT, bool LG = false>
 static void launch_sign(mn_context* c, const ImgParams& P, hipStream_t st, bool cls, bool lean_cls) {
   const int N = P.N, ngroups = (N + PX - 1) / PX;
   const dim3 g(grid_for(ngroups, MN_CC_SIGN_THREADS)), b(MN_CC_SIGN_THREADS);
@@ -814,17 +822,18 @@ static void launch_sign(mn_context* c, const ImgParams& P, hipStream_t st, bool 
   CO.gsum = reinterpret_cast<int*>(c->lpsum);     // (the summed class log-probs are written later, at roots only)
   CO.gstride = gsum_stride(P.N);
   // (a 16-bit map is always clipped on load; its plain form is the clip alone: mn_cc_value)
-  const bool plain = (DT != MN_DTYPE_F32 || !P.clip) && P.sdb == 0.0f;
+  // (logits likewise: sigmoid + clip)
+  const bool plain = (DT != MN_DTYPE_F32 || LG || !P.clip) && P.sdb == 0.0f;
   // Timed: the dispatch itself carries the two events (hipExtLaunchKernel: start and stop time of THIS
   // kernel), instead of an event packet in front of it and one behind -- each of those cost a ~6 us
   // dispatch gap on the stream, and the pair measured gap + kernel (54 us where rocprofv3 saw 46).
 #define MN_LAUNCH_SIGN(PLAINV, CLSV)                                                                    \
   do {                                                                                                \
     if (c->ext_events)                                                                                \
-      hipExtLaunchKernelGGL((mn_cc_sign<PX, PLAINV, (CLSV) && PX >= 4, DT>), g, b, 0, st, c->ev[0], c->ev[10], 0, \
+      hipExtLaunchKernelGGL((mn_cc_sign<PX, PLAINV, (CLSV) && PX >= 4, DT, LG>), g, b, 0, st, c->ev[0], c->ev[10], 0, \
                             P, c->cc_bits, c->cc_negbits, c->scalars + 6, c->partial, CO); \
     else                                                                                              \
-      hipLaunchKernelGGL((mn_cc_sign<PX, PLAINV, (CLSV) && PX >= 4, DT>), g, b, 0, st, P, c->cc_bits, c->cc_negbits, \
+      hipLaunchKernelGGL((mn_cc_sign<PX, PLAINV, (CLSV) && PX >= 4, DT, LG>), g, b, 0, st, P, c->cc_bits, c->cc_negbits, \
                          c->scalars + 6, c->partial, CO);                                             \
   } while (0)
   if (plain && cls) MN_LAUNCH_SIGN(true, true);
@@ -848,19 +857,24 @@ static int sweep_px(const mn_context* c, const ImgParams& P) {
 }
 
 // The sweep in the form sweep_px chose (`cls`: it takes the class planes too; only with px >= 4).
-static void launch_sweep(mn_context* c, const ImgParams& P, hipStream_t st, int px, bool cls, bool lean_cls) {
+template <bool LG>
+static void launch_sweep_lg(mn_context* c, const ImgParams& P, hipStream_t st, int px, bool cls, bool lean_cls) {
 #define MN_SWEEP_DT(PXV)                                                                         \
   do {                                                                                           \
-    if (P.dtype == MN_DTYPE_F16) launch_sign<PXV, MN_DTYPE_F16>(c, P, st, cls, lean_cls);        \
-    else launch_sign<PXV, MN_DTYPE_BF16>(c, P, st, cls, lean_cls);                               \
+    if (P.dtype == MN_DTYPE_F16) launch_sign<PXV, MN_DTYPE_F16, LG>(c, P, st, cls, lean_cls);    \
+    else launch_sign<PXV, MN_DTYPE_BF16, LG>(c, P, st, cls, lean_cls);                           \
   } while (0)
   if (P.dtype == MN_DTYPE_F32) {
-    if (px == 4) launch_sign<4, MN_DTYPE_F32>(c, P, st, cls, lean_cls);
-    else launch_sign<1, MN_DTYPE_F32>(c, P, st, false, false);
+    if (px == 4) launch_sign<4, MN_DTYPE_F32, LG>(c, P, st, cls, lean_cls);
+    else launch_sign<1, MN_DTYPE_F32, LG>(c, P, st, false, false);
   } else if (px == 8) MN_SWEEP_DT(8);
   else if (px == 4) MN_SWEEP_DT(4);
   else { cls = false; lean_cls = false; MN_SWEEP_DT(1); }
 #undef MN_SWEEP_DT
+}
+static void launch_sweep(mn_context* c, const ImgParams& P, hipStream_t st, int px, bool cls, bool lean_cls) {
+  if (P.logits) launch_sweep_lg<true>(c, P, st, px, cls, lean_cls);      // (the sigmoid on load: a compile-time form)
+  else launch_sweep_lg<false>(c, P, st, px, cls, lean_cls);
 }
 
 // the sweep over the positive masks that hooks the offsets the tile stages did not take
@@ -2022,7 +2036,7 @@ extern "C" int mn_segment_launch_t(mn_context* c, const void* d_class_pred, int 
                                    int num_classes, const int* offset_list, int* d_mask,
                                    int* d_object_class, int* d_partition, const mn_options* opts,
                                    void* stream) {
-  if (!c || c->pend.active || !dtype_ok(dtype)) { g_last_status = MN_ERR_ARGUMENT; return MN_ERR_ARGUMENT; }
+  if (!c || c->pend.active || !dtype_ok(dtype, true)) { g_last_status = MN_ERR_ARGUMENT; return MN_ERR_ARGUMENT; }
   HostLaunchTimer host_timer;
   mn_context::Pending& q = c->pend;
   q.call = ImageCall{d_class_pred, d_adj_pred, dtype, class_dim, offset_dim, W, H, num_classes, d_mask, d_object_class, d_partition};
@@ -2037,7 +2051,7 @@ extern "C" int mn_segment_launch_t(mn_context* c, const void* d_class_pred, int 
   if (want_replay) {
     memset(key, 0, sizeof(key));
     const void* ptrs[6] = {d_class_pred, d_adj_pred, d_mask, d_object_class, d_partition, stream};
-    const int dims[6] = {class_dim, offset_dim, W, H, num_classes, dtype};
+    const int dims[6] = {class_dim, offset_dim, W, H, num_classes, dtype};      // (dtype with MN_MAPS_LOGITS: a logits call never replays a probability call's graphs)
     memcpy(key + kb, ptrs, sizeof(ptrs)); kb += sizeof(ptrs);
     memcpy(key + kb, dims, sizeof(dims)); kb += sizeof(dims);
     memcpy(key + kb, &o, sizeof(o)); kb += sizeof(o);
@@ -2172,7 +2186,7 @@ extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void
   shared.opts.mode = MN_MODE_EXACT;
   const mn_options& o = shared.opts;
   if (!ctxs || count <= 0 || count > 4096 || !d_class_pred || !d_adj_pred || !d_mask || !d_object_class ||
-      !dtype_ok(dtype)) {
+      !dtype_ok(dtype, true)) {
     g_last_status = MN_ERR_ARGUMENT;
     return MN_ERR_ARGUMENT;
   }
@@ -2541,7 +2555,7 @@ extern "C" int mn_prepare_device_t(mn_context* c, const void* d_in, int in_dtype
                                    int in_width, void* d_out, int out_dtype, int out_height, int out_width,
                                    int apply_sigmoid, int clip, void* stream) {
   if (!c || !d_in || !d_out || channels <= 0 || in_height <= 0 || in_width <= 0 || out_height <= 0 ||
-      out_width <= 0 || out_height > 65535 || channels > 65535 || !dtype_ok(in_dtype) || !dtype_ok(out_dtype)) {
+      out_width <= 0 || out_height > 65535 || channels > 65535 || !dtype_ok(in_dtype, false) || !dtype_ok(out_dtype, false)) {
     g_last_status = MN_ERR_ARGUMENT;
     return MN_ERR_ARGUMENT;
   }

@@ -27,6 +27,8 @@ struct ImgParams {
   float sep_hi, sep_lo; // components mode: an edge inside a component needs a sameness value >= sep_hi,
                         // one between components <= sep_lo (0.5 widened by the float32 rounding margin)
   int dtype;           // enum mn_dtype of BOTH maps; a 16-bit dtype always comes with clip == 1
+  int logits;          // 1: both maps hold logits (MN_MAPS_LOGITS): every loader below returns mn_sigmoid of the
+                       // element, so no kernel ever holds a logit; always comes with clip == 1
   const void* cls;     // [C][N] class probabilities (borrowed), elements of `dtype`
   const void* same;    // [O][N] sameness probabilities (borrowed), elements of `dtype`
   int di[MN_MAX_OFFSETS];
@@ -82,6 +84,11 @@ __device__ __forceinline__ float4 mn_ld_map4(const void* base, int dtype, size_t
   return make_float4(a.x, a.y, b.x, b.y);
 }
 
+// The reference's networks end in this sigmoid (utils/inference_utils.py:44,96), in float32.  One expression
+// for every site: the loaders of logits maps, mn_same_value, mn_prepare_maps.  It is exactly 1.0 from about 17
+// up and exactly 0 below about -104 (expf(+inf) = inf, 1 / inf = 0), which is why logits are always clipped.
+__device__ __forceinline__ float mn_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
 __device__ __forceinline__ float mn_clip(float v) {
   return fminf(fmaxf(v, MN_EPS32), 1.0f - MN_EPS32);
 }
@@ -100,24 +107,34 @@ __device__ __forceinline__ float mn_same_value(const ImgParams& P, float v) {
   if (P.clip) v = mn_clip(v);
   if (P.sdb != 0.0f) {
     const float logit = (logf(v) - mn_log1m(v)) + P.sdb;
-    v = 1.0f / (1.0f + expf(-logit));
+    v = mn_sigmoid(logit);
   }
   return v;
 }
 
+// The sigmoid of a logits map is part of the load (P.logits is uniform over the launch, like the dtype): what
+// the four loaders below return is a probability either way, and they are the only readers of P.cls / P.same
+// besides the sweep's own typed loaders (mn_kernels_cc.h), which do the same at compile time.
+__device__ __forceinline__ float4 mn_sigmoid4(float4 v) {
+  return make_float4(mn_sigmoid(v.x), mn_sigmoid(v.y), mn_sigmoid(v.z), mn_sigmoid(v.w));
+}
 // raw sameness value of offset k at pixel p (mn_same_value clips and applies the bias)
 __device__ __forceinline__ float mn_ld_same(const ImgParams& P, int k, int p) {
-  return mn_ld_map(P.same, P.dtype, (size_t)k * P.N + p);
+  const float v = mn_ld_map(P.same, P.dtype, (size_t)k * P.N + p);
+  return P.logits ? mn_sigmoid(v) : v;
 }
 __device__ __forceinline__ float4 mn_ld_same4(const ImgParams& P, int k, int p) {
-  return mn_ld_map4(P.same, P.dtype, (size_t)k * P.N + p);
+  const float4 v = mn_ld_map4(P.same, P.dtype, (size_t)k * P.N + p);
+  return P.logits ? mn_sigmoid4(v) : v;
 }
 __device__ __forceinline__ float4 mn_ld_class4(const ImgParams& P, int c, int p) {
-  return mn_ld_map4(P.cls, P.dtype, (size_t)c * P.N + p);
+  const float4 v = mn_ld_map4(P.cls, P.dtype, (size_t)c * P.N + p);
+  return P.logits ? mn_sigmoid4(v) : v;
 }
 
 __device__ __forceinline__ float mn_ld_class(const ImgParams& P, int c, int p) {
   float v = mn_ld_map(P.cls, P.dtype, (size_t)c * P.N + p);
+  if (P.logits) v = mn_sigmoid(v);
   if (P.clip) v = mn_clip(v);
   return v;
 }

@@ -103,10 +103,14 @@ __device__ __forceinline__ float4 mn_ld_stream4(const float* p) {
 }
 // The 16-bit maps (DT = MN_DTYPE_F16 / MN_DTYPE_BF16): a lane's 4 values are one 8-byte load, its 8 values one
 // 16-byte load; DT = MN_DTYPE_F32 is the float load above, unchanged.
+// LG: the maps hold logits (MN_MAPS_LOGITS) -- the loaders return mn_sigmoid of every element, in float32, so
+// the sweep works on probabilities as ever; LG = false is the load alone, unchanged.
 typedef unsigned mn_u2v __attribute__((ext_vector_type(2)));
-template <int DT>
+template <int DT, bool LG = false>
 __device__ __forceinline__ float4 mn_ld_stream4_t(const void* base, size_t i) {
-  if constexpr (DT == MN_DTYPE_F32) {
+  if constexpr (LG) {
+    return mn_sigmoid4(mn_ld_stream4_t<DT, false>(base, i));
+  } else if constexpr (DT == MN_DTYPE_F32) {
     return mn_ld_stream4(static_cast<const float*>(base) + i);
   } else {
     const mn_u2v* q = reinterpret_cast<const mn_u2v*>(static_cast<const mn_u16*>(base) + i);
@@ -119,7 +123,7 @@ __device__ __forceinline__ float4 mn_ld_stream4_t(const void* base, size_t i) {
     return make_float4(a.x, a.y, b.x, b.y);
   }
 }
-template <int DT>
+template <int DT, bool LG = false>
 __device__ __forceinline__ void mn_ld_stream8_t(const void* base, size_t i, float* v) {
   static_assert(DT != MN_DTYPE_F32, "8 values per load: 16-bit maps only");
   const mn_u4v* q = reinterpret_cast<const mn_u4v*>(static_cast<const mn_u16*>(base) + i);
@@ -130,10 +134,15 @@ __device__ __forceinline__ void mn_ld_stream8_t(const void* base, size_t i, floa
 #endif
   const float2 a = mn_widen2<DT>(t.x), b = mn_widen2<DT>(t.y), c = mn_widen2<DT>(t.z), d = mn_widen2<DT>(t.w);
   v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y; v[4] = c.x; v[5] = c.y; v[6] = d.x; v[7] = d.y;
+  if constexpr (LG) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) v[j] = mn_sigmoid(v[j]);
+  }
 }
-template <int DT>
+template <int DT, bool LG = false>
 __device__ __forceinline__ float mn_ld_stream1_t(const void* base, size_t i) {
-  if constexpr (DT == MN_DTYPE_F32) return static_cast<const float*>(base)[i];
+  if constexpr (LG) return mn_sigmoid(mn_ld_stream1_t<DT, false>(base, i));
+  else if constexpr (DT == MN_DTYPE_F32) return static_cast<const float*>(base)[i];
   else return mn_widen<DT>(static_cast<const mn_u16*>(base)[i]);
 }
 __device__ __forceinline__ void mn_st_stream(int* p, int v) {
@@ -152,10 +161,11 @@ __device__ __forceinline__ void mn_st_stream(uint4* p, uint4 v) {
 #endif
 }
 
-// (a 16-bit map is always clipped on load: its PLAIN form is the clip alone, no same_different_bias)
-template <bool PLAIN, int DT = MN_DTYPE_F32>
+// (a 16-bit map is always clipped on load: its PLAIN form is the clip alone, no same_different_bias; so are
+//  logits of any element type, LG -- `v` is the probability their loader returned)
+template <bool PLAIN, int DT = MN_DTYPE_F32, bool LG = false>
 __device__ __forceinline__ float mn_cc_value(const ImgParams& P, float v) {
-  return PLAIN ? (DT == MN_DTYPE_F32 ? v : mn_clip(v)) : mn_same_value(P, v);
+  return PLAIN ? ((DT == MN_DTYPE_F32 && !LG) ? v : mn_clip(v)) : mn_same_value(P, v);
 }
 
 // CLS (PX == 4, N % 4 == 0): the lane also streams the C class planes of its four pixels first -- the
@@ -180,12 +190,12 @@ __device__ __forceinline__ int mn_cc_argmax_logf(const ImgParams& P, int p) {
 }
 
 // mn_cc_argmax_logf with the maps' element type known at compile time (the sweep's own instantiations)
-template <int DT>
+template <int DT, bool LG = false>
 __device__ __forceinline__ int mn_cc_argmax_logf_t(const ImgParams& P, int p) {
   float best = 0.0f;
   int b = 0;
   for (int c = 0; c < P.C; c++) {
-    float v = mn_ld_stream1_t<DT>(P.cls, (size_t)c * P.N + p);
+    float v = mn_ld_stream1_t<DT, LG>(P.cls, (size_t)c * P.N + p);
     if (P.clip) v = mn_clip(v);
     const float l = logf(v);
     if (c == 0 || l > best) { best = l; b = c; }
@@ -193,7 +203,7 @@ __device__ __forceinline__ int mn_cc_argmax_logf_t(const ImgParams& P, int p) {
   return b;
 }
 
-template <int DT>
+template <int DT, bool LG = false>
 __device__ __forceinline__ void mn_cc_class_part(const ImgParams& P, const ClsOut& CO, int i) {
   // The arg-max is taken on the VALUES (logf is monotone); the reference's first-maximum rule on
   // logf values differs only if a class of LOWER index lies within rounding distance of the maximum
@@ -203,11 +213,11 @@ __device__ __forceinline__ void mn_cc_class_part(const ImgParams& P, const ClsOu
   // of the reference it stands for).
   float4 best, prev = make_float4(-1.0f, -1.0f, -1.0f, -1.0f);
   int b0 = 0, b1 = 0, b2 = 0, b3 = 0;
-  float4 nxt = mn_ld_stream4_t<DT>(P.cls, 4 * (size_t)i);
+  float4 nxt = mn_ld_stream4_t<DT, LG>(P.cls, 4 * (size_t)i);
   for (int c = 0; c < P.C; c++) {
     float4 v = nxt;
     if (c + 1 < P.C)
-      nxt = mn_ld_stream4_t<DT>(P.cls, (size_t)(c + 1) * P.N + 4 * (size_t)i);
+      nxt = mn_ld_stream4_t<DT, LG>(P.cls, (size_t)(c + 1) * P.N + 4 * (size_t)i);
     if (P.clip) { v.x = mn_clip(v.x); v.y = mn_clip(v.y); v.z = mn_clip(v.z); v.w = mn_clip(v.w); }
     if (c == 0) {
       best = v;
@@ -223,10 +233,10 @@ __device__ __forceinline__ void mn_cc_class_part(const ImgParams& P, const ClsOu
   // a lower class within 2^-18 of the maximum (logs of magnitude < 16 are 2^-20 apart at most, and
   // the GPU's logf is within an ulp of libm's): settle it the reference's way
   const float near = 1.0f - 3.814697265625e-06f;
-  if (prev.x >= best.x * near) b0 = mn_cc_argmax_logf_t<DT>(P, 4 * i);
-  if (prev.y >= best.y * near) b1 = mn_cc_argmax_logf_t<DT>(P, 4 * i + 1);
-  if (prev.z >= best.z * near) b2 = mn_cc_argmax_logf_t<DT>(P, 4 * i + 2);
-  if (prev.w >= best.w * near) b3 = mn_cc_argmax_logf_t<DT>(P, 4 * i + 3);
+  if (prev.x >= best.x * near) b0 = mn_cc_argmax_logf_t<DT, LG>(P, 4 * i);
+  if (prev.y >= best.y * near) b1 = mn_cc_argmax_logf_t<DT, LG>(P, 4 * i + 1);
+  if (prev.z >= best.z * near) b2 = mn_cc_argmax_logf_t<DT, LG>(P, 4 * i + 2);
+  if (prev.w >= best.w * near) b3 = mn_cc_argmax_logf_t<DT, LG>(P, 4 * i + 3);
   uchar4 o;
   o.x = (unsigned char)b0; o.y = (unsigned char)b1; o.z = (unsigned char)b2; o.w = (unsigned char)b3;
   // (pure components mode: only the component roots' class and validity flag are ever read, and
@@ -240,19 +250,19 @@ __device__ __forceinline__ void mn_cc_class_part(const ImgParams& P, const ClsOu
 // of the layout above, so gsum, cls0 and everything behind the sweep are what the 4-pixel form leaves.  The
 // arithmetic per 4-pixel group is that of mn_cc_class_part on the widened values (a 16-bit map is always
 // clipped on load), so the outputs are bit-equal to the float32 sweep's on maps.float().
-template <int DT>
+template <int DT, bool LG = false>
 __device__ __forceinline__ void mn_cc_class_part8(const ImgParams& P, const ClsOut& CO, int i) {
   float best[8], prev[8];
   int b[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) { best[j] = 0.0f; prev[j] = -1.0f; b[j] = 0; }
   float nxt[8];
-  mn_ld_stream8_t<DT>(P.cls, 8 * (size_t)i, nxt);
+  mn_ld_stream8_t<DT, LG>(P.cls, 8 * (size_t)i, nxt);
   for (int c = 0; c < P.C; c++) {
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) v[j] = mn_clip(nxt[j]);
-    if (c + 1 < P.C) mn_ld_stream8_t<DT>(P.cls, (size_t)(c + 1) * P.N + 8 * (size_t)i, nxt);
+    if (c + 1 < P.C) mn_ld_stream8_t<DT, LG>(P.cls, (size_t)(c + 1) * P.N + 8 * (size_t)i, nxt);
 #pragma unroll
     for (int j = 0; j < 8; j++) {
       if (c == 0) best[j] = v[j];
@@ -266,7 +276,7 @@ __device__ __forceinline__ void mn_cc_class_part8(const ImgParams& P, const ClsO
   const float near = 1.0f - 3.814697265625e-06f;
 #pragma unroll
   for (int j = 0; j < 8; j++)
-    if (prev[j] >= best[j] * near) b[j] = mn_cc_argmax_logf_t<DT>(P, 8 * i + j);
+    if (prev[j] >= best[j] * near) b[j] = mn_cc_argmax_logf_t<DT, LG>(P, 8 * i + j);
   uint2 o;
   o.x = (unsigned)b[0] | ((unsigned)b[1] << 8) | ((unsigned)b[2] << 16) | ((unsigned)b[3] << 24);
   o.y = (unsigned)b[4] | ((unsigned)b[5] << 8) | ((unsigned)b[6] << 16) | ((unsigned)b[7] << 24);
@@ -278,7 +288,9 @@ __device__ __forceinline__ void mn_cc_class_part8(const ImgParams& P, const ClsO
 // DT: element type of the maps.  MN_DTYPE_F32 takes PX = 4 | 1 as described above.  A 16-bit map takes PX = 8
 // (one 16-byte load of eight values per plane; N % 8 == 0, W % 8 == 0 -- no lane runs over a row's end -- and
 // 16-byte aligned planes), else PX = 4 with 8-byte loads, else PX = 1; its PLAIN form clips (mn_cc_value).
-template <int PX, bool PLAIN, bool CLS, int DT = MN_DTYPE_F32>
+// LG: the maps hold logits of element type DT, PX by the same rule.  The sigmoid is taken where a value is
+// loaded, so the neutral 1.0 of an out-of-image edge below stays a probability; PLAIN is sigmoid + clip.
+template <int PX, bool PLAIN, bool CLS, int DT = MN_DTYPE_F32, bool LG = false>
 __global__ __launch_bounds__(MN_CC_SIGN_THREADS) void mn_cc_sign(
     ImgParams P, unsigned* __restrict__ bits, unsigned* __restrict__ negbits, int* __restrict__ violations,
     double* __restrict__ partial, ClsOut CO) {
@@ -290,8 +302,8 @@ __global__ __launch_bounds__(MN_CC_SIGN_THREADS) void mn_cc_sign(
   const int r = p0 / P.W, c0 = p0 - r * P.W;
   if constexpr (CLS) {
     if (live) {
-      if constexpr (PX == 8) mn_cc_class_part8<DT>(P, CO, i);
-      else mn_cc_class_part<DT>(P, CO, i);
+      if constexpr (PX == 8) mn_cc_class_part8<DT, LG>(P, CO, i);
+      else mn_cc_class_part<DT, LG>(P, CO, i);
     }
   }
   float f = 1.0f;
@@ -330,12 +342,12 @@ __global__ __launch_bounds__(MN_CC_SIGN_THREADS) void mn_cc_sign(
           rin[g] = (in1 ? 1 : 0) | (in2 ? 2 : 0);
           if (in1) rowmask |= 1u << k;
           if constexpr (PX == 8) {
-            mn_ld_stream8_t<DT>(P.same, (size_t)k * P.N + p0, v[g]);
+            mn_ld_stream8_t<DT, LG>(P.same, (size_t)k * P.N + p0, v[g]);
           } else if (PX == 4) {
-            const float4 t = mn_ld_stream4_t<DT>(P.same, (size_t)k * P.N + p0);
+            const float4 t = mn_ld_stream4_t<DT, LG>(P.same, (size_t)k * P.N + p0);
             v[g][0] = t.x; v[g][1 % PX] = t.y; v[g][2 % PX] = t.z; v[g][3 % PX] = t.w;
           } else {
-            v[g][0] = mn_ld_stream1_t<DT>(P.same, (size_t)k * P.N + p0);
+            v[g][0] = mn_ld_stream1_t<DT, LG>(P.same, (size_t)k * P.N + p0);
           }
         }
       }
@@ -348,7 +360,7 @@ __global__ __launch_bounds__(MN_CC_SIGN_THREADS) void mn_cc_sign(
         const unsigned bit = (k0 + g < P.O) ? (1u << ((k0 + g) & 31)) : 0u;
 #pragma unroll
         for (int j = 0; j < PX; j++) {
-          const float x = ((PLAIN && DT == MN_DTYPE_F32) || first[g] != INT_MIN) ? mn_cc_value<PLAIN, DT>(P, v[g][j]) : 1.0f;
+          const float x = ((PLAIN && DT == MN_DTYPE_F32 && !LG) || first[g] != INT_MIN) ? mn_cc_value<PLAIN, DT, LG>(P, v[g][j]) : 1.0f;
           m[j] |= (x >= P.sep_hi) ? bit : 0u;
           ng[j] |= (x <= P.sep_lo) ? bit : 0u;
           f *= fmaxf(x, 1.0f - x);
@@ -367,7 +379,7 @@ __global__ __launch_bounds__(MN_CC_SIGN_THREADS) void mn_cc_sign(
           const bool second = straddle && c0 + j >= P.W;
           const bool inb = ((rin[g] >> (second ? 1 : 0)) & 1) &&
                            (unsigned)(first[g] + j - (second ? P.W : 0)) < (unsigned)P.W;
-          const float x = inb ? mn_cc_value<PLAIN, DT>(P, v[g][j]) : 1.0f;
+          const float x = inb ? mn_cc_value<PLAIN, DT, LG>(P, v[g][j]) : 1.0f;
           inmask[j] |= inb ? bit : 0u;
           m[j] |= (x >= P.sep_hi) ? bit : 0u;
           ng[j] |= (x <= P.sep_lo) ? bit : 0u;

@@ -55,8 +55,8 @@ __global__ __launch_bounds__(256) void mn_prepare_maps(const void* __restrict__ 
   float a = mn_ld_map(in, in_dtype, p + (size_t)y0 * Win + x0), b = mn_ld_map(in, in_dtype, p + (size_t)y0 * Win + x1);
   float c = mn_ld_map(in, in_dtype, p + (size_t)y1 * Win + x0), d = mn_ld_map(in, in_dtype, p + (size_t)y1 * Win + x1);
   if (apply_sigmoid) {
-    a = 1.0f / (1.0f + expf(-a)); b = 1.0f / (1.0f + expf(-b));
-    c = 1.0f / (1.0f + expf(-c)); d = 1.0f / (1.0f + expf(-d));
+    a = mn_sigmoid(a); b = mn_sigmoid(b);
+    c = mn_sigmoid(c); d = mn_sigmoid(d);
   }
   const float t0 = a * (1.0f - fx) + b * fx;
   const float t1 = c * (1.0f - fx) + d * fx;

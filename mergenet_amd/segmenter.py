@@ -36,6 +36,7 @@ MN_DEBUG_GENERIC_EDGE_PASS, MN_DEBUG_NO_EVENTS, MN_DEBUG_NO_CORES = 1, 2, 4
 MN_DEBUG_LEAN_EVENTS, MN_DEBUG_REPLAY = 16, 32
 MN_DEBUG_SWEEP16_4PX = 256    # a 16-bit map's sweep takes 4 pixels per lane (8-byte loads) where it would take 8
 MN_DTYPE_F32, MN_DTYPE_F16, MN_DTYPE_BF16 = 0, 1, 2   # enum mn_dtype: element type of the maps (*_t entry points)
+MN_MAPS_LOGITS = 0x100   # or-ed into that dtype: both maps hold logits, the kernels take the sigmoid on load
 MN_ERR_ARGUMENT = -1
 MN_PROVE_ALWAYS, MN_PROVE_BY_MODE, MN_PROVE_NEVER = 1, 0, -1   # mn_options.require_proof
 MN_TIES_DEFAULT, MN_TIES_REFERENCE, MN_TIES_LOWEST_ID = 0, 1, 2   # mn_options.tie_order
@@ -423,6 +424,12 @@ class Merger:
     Both may also be ``float16`` or ``bfloat16`` (the same dtype for the two), as a network under autocast
     writes them: the kernels read them in that width -- no float32 copy is made -- and the result is what
     the float32 call gives on ``maps.float()`` with ``clip_inputs=1`` (16-bit maps are always clipped on load).
+
+    ``logits=True`` on the methods that take maps says that both tensors hold the network's logits, not
+    probabilities: the kernels take ``1 / (1 + expf(-x))`` in float32 where they load an element, so no
+    ``torch.sigmoid`` pass runs before the merge and a 16-bit logit keeps its own probability up to a logit of
+    about 17.  The result is what the float32 call gives on ``prepare(x, H, W, apply_sigmoid=True, clip=False)``
+    with ``clip_inputs=1`` (logits are always clipped on load).
     """
 
     DTYPE_NAMES = "float32, float16 or bfloat16"
@@ -461,14 +468,15 @@ class Merger:
             raise ValueError("expected %s tensors, got %s" % (self.DTYPE_NAMES, t.dtype))
         return code
 
-    def _typed(self, name: str, dtype: int):
+    def _typed(self, name: str, dtype: int, logits: bool = False):
         """The entry point that takes `dtype` and the arguments that carry it: (function, (dtype,)) of the *_t
-        form, or -- float32 maps on a variant build without the typed forms (MN_LIB) -- (float function, ())."""
+        form, or -- float32 probability maps on a variant build without the typed forms (MN_LIB) -- (float
+        function, ()).  `logits` travels as MN_MAPS_LOGITS in that dtype."""
         fn = getattr(self.lib, name + "_t", None)
         if fn is not None:
-            return fn, (dtype,)
-        if dtype != MN_DTYPE_F32:
-            raise RuntimeError("%s has no %s_t: 16-bit maps need the current library" % (LIB_PATH, name))
+            return fn, (dtype | (MN_MAPS_LOGITS if logits else 0),)
+        if dtype != MN_DTYPE_F32 or logits:
+            raise RuntimeError("%s has no %s_t: 16-bit maps and logits need the current library" % (LIB_PATH, name))
         return getattr(self.lib, name), ()
 
     def _check(self, class_probs, same_probs, offsets):
@@ -489,7 +497,7 @@ class Merger:
         return C, H, W, O, off
 
     def segment(self, class_probs, same_probs, offsets, opts: Optional[MnOptions] = None,
-                want_partition: bool = False):
+                want_partition: bool = False, logits: bool = False):
         """Returns (mask int32[H,W] tensor, object_class int32[H*W] tensor, partition|None, stats)."""
         torch = self.torch
         C, H, W, O, off = self._check(class_probs, same_probs, offsets)
@@ -500,7 +508,7 @@ class Merger:
         part = torch.empty((H, W), dtype=torch.int32, device=dev) if want_partition else None
         stats = MnStats()
         stream = torch.cuda.current_stream(dev).cuda_stream
-        fn, dt = self._typed("mn_segment_device", self._dtype(class_probs))
+        fn, dt = self._typed("mn_segment_device", self._dtype(class_probs), logits)
         rc = fn(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(), O, *dt, W, H, C,
                 off.ctypes.data_as(_i32p), mask.data_ptr(), table.data_ptr(),
                 part.data_ptr() if part is not None else None,
@@ -510,7 +518,7 @@ class Merger:
         return mask, table, part, stats.as_dict()
 
     def segment_async(self, class_probs, same_probs, offsets, opts: Optional[MnOptions] = None,
-                      want_partition: bool = False, out=None) -> "PendingSegment":
+                      want_partition: bool = False, out=None, logits: bool = False) -> "PendingSegment":
         """Queue one image (``mn_segment_launch``) and return at once; ``.result()`` of the returned
         object waits and gives what :meth:`segment` gives.  The Merger is busy until then -- use
         two of them alternately on one stream to keep the GPU busy across images: the launch of
@@ -535,7 +543,7 @@ class Merger:
             table = torch.empty((H * W,), dtype=torch.int32, device=dev)
         part = torch.empty((H, W), dtype=torch.int32, device=dev) if want_partition else None
         stream = torch.cuda.current_stream(dev).cuda_stream
-        fn, dt = self._typed("mn_segment_launch", self._dtype(class_probs))
+        fn, dt = self._typed("mn_segment_launch", self._dtype(class_probs), logits)
         rc = fn(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(), O, *dt, W, H, C,
                 off.ctypes.data_as(_i32p), mask.data_ptr(), table.data_ptr(),
                 part.data_ptr() if part is not None else None,
@@ -545,7 +553,7 @@ class Merger:
         return PendingSegment(self, mask, table, part, (class_probs, same_probs, opts))
 
     def score(self, class_probs, same_probs, offsets, opts: Optional[MnOptions] = None,
-              want_arrays: bool = False):
+              want_arrays: bool = False, logits: bool = False):
         """Phase A only.  Returns (ms_class_pass, ms_edge_pass[, cls uint8[H,W], best int64[H,W]])."""
         torch = self.torch
         C, H, W, O, off = self._check(class_probs, same_probs, offsets)
@@ -555,7 +563,7 @@ class Merger:
         best = torch.empty((H, W), dtype=torch.int64, device=dev) if want_arrays else None
         a, b = ctypes.c_float(0), ctypes.c_float(0)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        fn, dt = self._typed("mn_score_device", self._dtype(class_probs))
+        fn, dt = self._typed("mn_score_device", self._dtype(class_probs), logits)
         rc = fn(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(),
                 O, *dt, W, H, C, off.ctypes.data_as(_i32p), ctypes.byref(opts),
                 ctypes.c_void_p(stream),
@@ -569,7 +577,7 @@ class Merger:
         return a.value, b.value
 
 
-    def sweep(self, class_probs, same_probs, offsets, opts: Optional[MnOptions] = None):
+    def sweep(self, class_probs, same_probs, offsets, opts: Optional[MnOptions] = None, logits: bool = False):
         """The affinity-scoring sweep of the default path alone (mn_cc_sign).  Returns a dict: bits uint32[H,W]
         (as int32 tensor), neg float32[O,H,W] (NaN = not listed), cls uint8[H,W] | None, gsum int32[C,H*W/4] |
         None, logsum float, pixels_per_lane, fused_class, margin_edges."""
@@ -584,7 +592,7 @@ class Merger:
         logsum = ctypes.c_double(0.0)
         info = (ctypes.c_int * 3)()
         stream = torch.cuda.current_stream(dev).cuda_stream
-        fn, dt = self._typed("mn_sweep_device", self._dtype(class_probs))
+        fn, dt = self._typed("mn_sweep_device", self._dtype(class_probs), logits)
         rc = fn(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(), O, *dt, W, H, C,
                 off.ctypes.data_as(_i32p), ctypes.byref(opts), ctypes.c_void_p(stream),
                 bits.data_ptr(), neg.data_ptr(), cls.data_ptr(), gsum.data_ptr(),
@@ -595,7 +603,8 @@ class Merger:
         return dict(bits=bits, neg=neg, cls=cls if fused else None, gsum=gsum if fused else None,
                     logsum=logsum.value, pixels_per_lane=int(info[0]), fused_class=fused, margin_edges=int(info[2]))
 
-    def sweep_time(self, inputs: Sequence, offsets, opts: Optional[MnOptions] = None, reps: int = 400) -> float:
+    def sweep_time(self, inputs: Sequence, offsets, opts: Optional[MnOptions] = None, reps: int = 400,
+                   logits: bool = False) -> float:
         """Tuning aid (``mn_sweep_time_device``): microseconds per launch of the sweep alone, back to back over
         the (class_probs, same_probs) pairs of ``inputs`` in rotation."""
         for a, b in inputs:
@@ -607,7 +616,7 @@ class Merger:
         vp = ctypes.c_void_p * n
         out = ctypes.c_float(0)
         stream = self.torch.cuda.current_stream(inputs[0][0].device).cuda_stream
-        fn, dt = self._typed("mn_sweep_time_device", self._dtype(inputs[0][0]))
+        fn, dt = self._typed("mn_sweep_time_device", self._dtype(inputs[0][0]), logits)
         rc = fn(self.handle, vp(*[a.data_ptr() for a, _ in inputs]),
                 vp(*[b.data_ptr() for _, b in inputs]), *dt, n, C, O, W, H, C,
                 off.ctypes.data_as(_i32p), ctypes.byref(opts), ctypes.c_void_p(stream),
@@ -616,7 +625,8 @@ class Merger:
             raise MergeNetError(rc)
         return out.value
 
-    def exact_phase_a(self, class_probs, same_probs, offsets, opts: Optional[MnOptions] = None):
+    def exact_phase_a(self, class_probs, same_probs, offsets, opts: Optional[MnOptions] = None,
+                      logits: bool = False):
         """Phase A of the exact engine: (cls uint8[H,W], oml float32[O,H,W], prio float32[O,H,W]) in the
         layout of the oracle's phase-A export (NaN where an edge leaves the image)."""
         torch = self.torch
@@ -627,7 +637,7 @@ class Merger:
         oml = torch.empty((O, H, W), dtype=torch.float32, device=dev)
         prio = torch.empty((O, H, W), dtype=torch.float32, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        fn, dt = self._typed("mn_exact_phase_a_device", self._dtype(class_probs))
+        fn, dt = self._typed("mn_exact_phase_a_device", self._dtype(class_probs), logits)
         rc = fn(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(),
                 O, *dt, W, H, C, off.ctypes.data_as(_i32p), ctypes.byref(opts),
                 ctypes.c_void_p(stream), cls.data_ptr(), oml.data_ptr(),
@@ -800,7 +810,7 @@ class ExactBatch:
         self.torch = self.mergers[0].torch
 
     def segment(self, class_probs: Sequence, same_probs: Sequence, offsets, opts: Optional[MnOptions] = None,
-                want_partition: bool = False):
+                want_partition: bool = False, logits: bool = False):
         torch = self.torch
         n = len(class_probs)
         if n < 1 or n > len(self.mergers) or len(same_probs) != n:
@@ -819,7 +829,7 @@ class ExactBatch:
         vp = ctypes.c_void_p * n
         stats = (MnStats * n)()
         stream = torch.cuda.current_stream(dev).cuda_stream
-        fn, dt = self.mergers[0]._typed("mn_segment_exact_batch", self.mergers[0]._dtype(class_probs[0]))
+        fn, dt = self.mergers[0]._typed("mn_segment_exact_batch", self.mergers[0]._dtype(class_probs[0]), logits)
         rc = fn(
             vp(*[m.handle for m in self.mergers[:n]]), n, vp(*[t.data_ptr() for t in class_probs]), C,
             vp(*[t.data_ptr() for t in same_probs]), O, *dt, W, H, C, off.ctypes.data_as(_i32p),
@@ -898,7 +908,7 @@ class MergerPool:
                 fut.set_exception(e)
 
     def submit(self, class_probs, same_probs, offsets, opts: Optional[MnOptions] = None,
-               want_partition: bool = False):
+               want_partition: bool = False, logits: bool = False):
         from concurrent.futures import Future
         torch = self.torch
         if not self.threads:
@@ -908,12 +918,12 @@ class MergerPool:
         ready.record(home)
         fut = Future()
         self.jobs.put((fut, ready, home, (class_probs, same_probs, offsets),
-                       {"opts": opts, "want_partition": want_partition}))
+                       {"opts": opts, "want_partition": want_partition, "logits": logits}))
         return fut
 
-    def map(self, images, offsets, opts: Optional[MnOptions] = None):
+    def map(self, images, offsets, opts: Optional[MnOptions] = None, logits: bool = False):
         """Results for an iterable of (class_probs, same_probs), in order, all images in flight."""
-        futures = [self.submit(cp, sp, offsets, opts) for cp, sp in images]
+        futures = [self.submit(cp, sp, offsets, opts, logits=logits) for cp, sp in images]
         return [f.result() for f in futures]
 
     def close(self):
