@@ -439,6 +439,36 @@ int mn_sameness_targets_device(mn_context* ctx, const int* d_mask, int height, i
  * of label k (segment.h:109); the reference's COCO results carry a constant score 1. */
 int mn_instance_scores_device(mn_context* ctx, float* d_scores, void* stream);
 
+/* Instance table of a label mask (labels 0..num_instances, 0 = background): what a detection result needs per
+ * instance beside its RLE.  The reference's caller ends in convert_to_coco_result (egs/cityscape/local/
+ * segment.py:165-186) and leaves area and box to COCO.loadRes, which derives them from every RLE on the host;
+ * here ONE pass over the mask gives them for all instances.
+ * d_table int32 [num_instances][5] = {area, x_min, y_min, x_max, y_max}, maxima inclusive; a label without
+ * pixels keeps the empty row {0, W, H, -1, -1} (the identities of sum, min and max over the image).  Labels
+ * outside 1..num_instances in the mask are ignored.  Any image size (not held to the context's capacity, as in
+ * mn_upsample_mask_device: the table is most wanted on the upsampled mask); 16-byte loads where width % 4 == 0
+ * and d_mask is 16-byte aligned, 4-byte loads otherwise.  num_instances == 0 is legal (nothing written).
+ * Enqueues only: no host synchronisation, no copies. */
+int mn_instance_table_device(mn_context* ctx, const int* d_mask, int height, int width,
+                             int num_instances, int* d_table, void* stream);
+
+/* Drop instances with area < min_area (or score < min_score when d_scores != NULL) and renumber the
+ * survivors 1..K' in ascending old label: the evaluator's zero-area drop with a threshold
+ * (egs/cityscape/local/evaluate.py:52-54; such instances arise when the mask is resized back with
+ * nearest-neighbour), done so that mask, class table, scores and instance table still agree afterwards.
+ * d_table: what mn_instance_table_device wrote for d_mask.  d_remap int32 [num_instances+1] out (old -> new,
+ * 0 = dropped; d_remap[0] = 0); d_mask_out may equal d_mask (labels outside 0..num_instances become 0);
+ * the *_out arrays have num_instances entries and must not be their inputs (MN_ERR_ARGUMENT): rows / entries 0..K'-1 are
+ * the survivors', d_object_class_out is -1 from K' up to num_instances (the library's convention), the rest of
+ * d_table_out and d_scores_out is not written; d_scores_out is needed only with d_scores; d_new_count: one
+ * device int, K'.  A NaN score fails the comparison: with d_scores given it is dropped whatever min_score is
+ * (-INFINITY keeps every other score).  Any image size, any num_instances >= 0.  Enqueues only. */
+int mn_filter_instances_device(mn_context* ctx, const int* d_mask, int height, int width, int num_instances,
+                               const int* d_table, const int* d_object_class, const float* d_scores,
+                               int min_area, float min_score, int* d_mask_out, int* d_remap,
+                               int* d_table_out, int* d_object_class_out, float* d_scores_out,
+                               int* d_new_count, void* stream);
+
 /* Wire format of the multi-GPU mask exchange (the all-gather of final instance masks the north
  * star asks for; the reference has no exchange, its jobs write files: segment.py:59-61).  d_wire is
  * int16 [n_pixels + 1 + max_instances + 4]: the labels (0..K), K, the classes of labels 1..K

@@ -19,6 +19,7 @@
 #include "mn_kernels_finish.h"
 #include "mn_kernels_output.h"
 #include "mn_kernels_prepare.h"
+#include "mn_kernels_instances.h"
 #include "mn_kernels_cc.h"
 #include "mn_kernels_tail.h"
 #include "mn_kernels_exact.h"
@@ -2654,6 +2655,70 @@ extern "C" int mn_instance_scores_device(mn_context* c, float* d_scores, void* s
   hipLaunchKernelGGL(mn_instance_scores, dim3(grid_for(c->last_params.N, 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), c->last_params, obj_state(c),
                      (const int*)c->label, d_scores);
+  MN_HIP(hipGetLastError());
+  g_last_status = MN_OK;
+  return MN_OK;
+}
+
+// ---- instance table, small-instance filter (mn_kernels_instances.h) -------------------------------
+// Both entry points only enqueue: no host synchronisation, no copy.  The image is not held to the
+// context's capacity (the table is most wanted on the upsampled mask); the context names the device.
+extern "C" int mn_instance_table_device(mn_context* c, const int* d_mask, int height, int width,
+                                        int num_instances, int* d_table, void* stream) {
+  if (!c || !d_mask || height <= 0 || width <= 0 || num_instances < 0 || (num_instances > 0 && !d_table) ||
+      (size_t)height * (size_t)width > (size_t)INT_MAX) {
+    g_last_status = MN_ERR_ARGUMENT;
+    return MN_ERR_ARGUMENT;
+  }
+  g_last_status = MN_OK;
+  if (num_instances == 0) return MN_OK;
+  MN_HIP(hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(mn_instance_table_init, dim3(grid_for(num_instances, 256)), dim3(256), 0, st, num_instances,
+                     height, width, d_table);
+  const bool vec = width % 4 == 0 && (reinterpret_cast<uintptr_t>(d_mask) & 15) == 0;
+  const int per_chunk = vec ? 256 : 64;                          // pixels of one 64-lane load
+  const int chunks_per_row = (width + per_chunk - 1) / per_chunk;
+  const int total = height * chunks_per_row;                     // <= H * W
+  const int waves = MN_INST_WORKGROUPS * (MN_INST_THREADS / 64);
+  const int chunks_per_wave = (total + waves - 1) / waves;       // >= 1
+  const dim3 g(grid_for(total, (unsigned)(MN_INST_THREADS / 64) * (unsigned)chunks_per_wave)), b(MN_INST_THREADS);
+  if (vec)
+    hipLaunchKernelGGL(mn_instance_table_runs<4>, g, b, 0, st, d_mask, height, width, num_instances,
+                       chunks_per_row, total, chunks_per_wave, d_table);
+  else
+    hipLaunchKernelGGL(mn_instance_table_runs<1>, g, b, 0, st, d_mask, height, width, num_instances,
+                       chunks_per_row, total, chunks_per_wave, d_table);
+  MN_HIP(hipGetLastError());
+  return MN_OK;
+}
+
+extern "C" int mn_filter_instances_device(mn_context* c, const int* d_mask, int height, int width,
+                                          int num_instances, const int* d_table, const int* d_object_class,
+                                          const float* d_scores, int min_area, float min_score, int* d_mask_out,
+                                          int* d_remap, int* d_table_out, int* d_object_class_out,
+                                          float* d_scores_out, int* d_new_count, void* stream) {
+  if (!c || !d_mask || !d_mask_out || !d_remap || !d_new_count || height <= 0 || width <= 0 || num_instances < 0 ||
+      (size_t)height * (size_t)width > (size_t)INT_MAX ||
+      (num_instances > 0 && (!d_table || !d_object_class || !d_table_out || !d_object_class_out ||
+                             (d_scores && !d_scores_out))) ||
+      // the compaction is out of place (and d_remap is read by the relabel while the mask is written)
+      (d_table_out && d_table_out == d_table) || (d_object_class_out && d_object_class_out == d_object_class) ||
+      (d_scores_out && d_scores_out == d_scores) || d_remap == d_mask_out || d_remap == d_mask) {
+    g_last_status = MN_ERR_ARGUMENT;
+    return MN_ERR_ARGUMENT;
+  }
+  MN_HIP(hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(mn_instance_keep, dim3(1), dim3(1024), 0, st, num_instances, d_table, d_object_class, d_scores,
+                     min_area, min_score, d_remap, d_table_out, d_object_class_out, d_scores_out, d_new_count);
+  const size_t N = (size_t)height * (size_t)width;
+  if (N % 4 == 0 && ((reinterpret_cast<uintptr_t>(d_mask) | reinterpret_cast<uintptr_t>(d_mask_out)) & 15) == 0)
+    hipLaunchKernelGGL(mn_relabel_mask4, dim3(grid_for(N / 4, 256)), dim3(256), 0, st, d_mask, N / 4, num_instances,
+                       (const int*)d_remap, d_mask_out);
+  else
+    hipLaunchKernelGGL(mn_relabel_mask, dim3(grid_for(N, 256)), dim3(256), 0, st, d_mask, N, num_instances,
+                       (const int*)d_remap, d_mask_out);
   MN_HIP(hipGetLastError());
   g_last_status = MN_OK;
   return MN_OK;

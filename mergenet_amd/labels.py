@@ -3,6 +3,9 @@
 Instance ids have no canonical numbering: the reference numbers instances in hash-map iteration
 order (``utils/csegment/segment.cc:503``), this library in ascending surviving pixel id.  Results
 are therefore compared as partitions plus per-instance class.
+
+Also the numpy statements of the instance table and the small-instance filter (``instance_table``,
+``filter_instances``), the checkers of ``Merger.instance_table`` / ``Merger.filter_instances``.
 """
 
 from __future__ import annotations
@@ -79,3 +82,54 @@ def agreement(mask_a, mask_b) -> int:
         cont[i, :] = -1
         cont[:, j] = -1
     return agree
+
+
+# ---- instance table and small-instance filter: the numpy checkers of the device path ----------------------
+# (the role rle.binary_mask_counts plays for the RLE strings: written straight from the definitions)
+
+def instance_table(mask: np.ndarray, num_instances: int) -> np.ndarray:
+    """int32 [K,5]: row k-1 = {area, x_min, y_min, x_max, y_max} of the pixels with label k, maxima inclusive;
+    {0, W, H, -1, -1} for a label without pixels.  Labels outside 1..K are ignored."""
+    m = np.asarray(mask)
+    H, W = m.shape
+    table = np.empty((int(num_instances), 5), np.int32)
+    for k in range(1, int(num_instances) + 1):
+        ys, xs = np.nonzero(m == k)
+        if ys.size == 0:
+            table[k - 1] = (0, W, H, -1, -1)
+        else:
+            table[k - 1] = (ys.size, xs.min(), ys.min(), xs.max(), ys.max())
+    return table
+
+
+def filter_instances(mask: np.ndarray, class_table, num_instances: int, table: np.ndarray, min_area: int,
+                     scores=None, min_score=None):
+    """Keep label k iff table[k-1][0] >= min_area (and, where scores are given, scores[k-1] >= min_score, -inf
+    when min_score is None: a NaN score fails the comparison and is dropped); the kept
+    labels get 1..K' in ascending old label, every other pixel 0.  Returns (mask int32, class table int32 [K] with
+    -1 from K' on, scores float32 [K'] or None, table int32 [K',5], K', remap int32 [K+1] old -> new, 0 = dropped)."""
+    m = np.asarray(mask)
+    K = int(num_instances)
+    table = np.asarray(table)
+    classes = np.asarray(class_table)
+    remap = np.zeros(K + 1, np.int32)
+    kept = []
+    for k in range(1, K + 1):
+        keep = table[k - 1][0] >= min_area
+        if scores is not None:
+            keep = keep and bool(scores[k - 1] >= (-np.inf if min_score is None else min_score))
+        if keep:
+            kept.append(k)
+            remap[k] = len(kept)
+    out = np.zeros(m.shape, np.int32)
+    for k in kept:
+        out[m == k] = remap[k]
+    new_classes = np.full(K, -1, np.int32)
+    new_table = np.empty((len(kept), 5), np.int32)
+    for k in kept:
+        new_classes[remap[k] - 1] = classes[k - 1]
+        new_table[remap[k] - 1] = table[k - 1]
+    new_scores = None
+    if scores is not None:
+        new_scores = np.asarray([scores[k - 1] for k in kept], np.float32)
+    return out, new_classes, new_scores, new_table, len(kept), remap

@@ -85,6 +85,7 @@ _lib_handle = None
 EXPORTS = ["mn_default_options", "mn_create", "mn_destroy", "mn_workspace_bytes",
            "mn_segment_device", "mn_segment_launch", "mn_segment_finish", "mn_segment_exact_batch", "mn_score_device", "mn_exact_phase_a_device", "mn_sweep_device", "mn_sweep_time_device", "mn_segment_host", "c_run_segmentation",
            "mn_prepare_device", "mn_upsample_mask_device", "mn_rle_points_device", "mn_rle_encode_host", "mn_sameness_targets_device", "mn_instance_scores_device",
+           "mn_instance_table_device", "mn_filter_instances_device",
            "mn_pack_wire_device", "mn_runs_wire_words", "mn_pack_runs_device", "mn_unpack_runs_device",
            "mn_unpack_runs_batch_device",
            "mn_segment_device_t", "mn_segment_launch_t", "mn_segment_exact_batch_t", "mn_score_device_t",
@@ -198,6 +199,17 @@ def load_library() -> ctypes.CDLL:
     lib.mn_sameness_targets_device.restype = ctypes.c_int
     lib.mn_instance_scores_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.mn_instance_scores_device.restype = ctypes.c_int
+    if hasattr(lib, "mn_instance_table_device"):         # (absent from older variant builds: MN_LIB)
+        lib.mn_instance_table_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        lib.mn_instance_table_device.restype = ctypes.c_int
+    if hasattr(lib, "mn_filter_instances_device"):
+        lib.mn_filter_instances_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p]
+        lib.mn_filter_instances_device.restype = ctypes.c_int
     lib.mn_pack_wire_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
                                         ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     lib.mn_pack_wire_device.restype = ctypes.c_int
@@ -771,6 +783,105 @@ class Merger:
         if rc != 0:
             raise MergeNetError(rc)
         return out[:num_instances]
+
+    def _check_mask(self, mask):
+        torch = self.torch
+        if not (mask.is_cuda and mask.dtype == torch.int32 and mask.is_contiguous() and mask.dim() == 2):
+            raise ValueError("expected a contiguous int32 [H,W] tensor on the GPU")
+        return int(mask.shape[0]), int(mask.shape[1])
+
+    def _entry(self, name: str):
+        fn = getattr(self.lib, name, None)
+        if fn is None:
+            raise RuntimeError("%s has no %s: the instance table and the filter need the current library" % (LIB_PATH, name))
+        return fn
+
+    def instance_table(self, mask, num_instances: int):
+        """int32 [K,5] tensor on the mask's device: row k-1 = {area, x_min, y_min, x_max, y_max} of label k, maxima
+        inclusive, {0, W, H, -1, -1} for a label without pixels (``labels.instance_table`` is the numpy statement).
+        One pass over the mask on the current stream; nothing is synchronised or copied.  Any image size."""
+        torch = self.torch
+        fn = self._entry("mn_instance_table_device")
+        H, W = self._check_mask(mask)
+        K = int(num_instances)
+        if K < 0:
+            raise ValueError("num_instances must not be negative")
+        table = torch.empty((K, 5), dtype=torch.int32, device=mask.device)
+        stream = torch.cuda.current_stream(mask.device).cuda_stream
+        rc = fn(self.handle, mask.data_ptr(), H, W, K, table.data_ptr(), ctypes.c_void_p(stream))
+        if rc != 0:
+            raise MergeNetError(rc)
+        return table
+
+    def filter_instances(self, mask, class_table, num_instances: int, min_area: int = 1, scores=None,
+                         min_score: Optional[float] = None, inplace: bool = False, table=None,
+                         return_remap: bool = False):
+        """Drop the instances with fewer than ``min_area`` pixels (and, with ``scores`` and ``min_score``, those
+        that score less) and renumber the survivors 1..K' in ascending old label -- the zero-area drop of
+        ``egs/cityscape/local/evaluate.py:52-54`` with a threshold, on the device, leaving mask, class table,
+        scores and instance table in agreement.  ``class_table``: int32, at least K entries (what ``segment``
+        returns); ``scores``: float32 [K] or None -- without ``min_score`` they are carried along, except that a NaN
+        score fails every comparison and is dropped whenever scores are given; ``table``: what :meth:`instance_table` gave for this mask
+        (computed here when None); ``inplace`` rewrites ``mask`` itself.  Returns ``(mask, class_table int32 [K]
+        with -1 from K' on, scores [K'] or None, table [K',5], K')`` (and the int32 [K+1] old -> new ``remap`` with
+        ``return_remap``).  Reading K' is the one synchronisation; ``labels.filter_instances`` is the numpy statement."""
+        torch = self.torch
+        fn = self._entry("mn_filter_instances_device")
+        H, W = self._check_mask(mask)
+        K = int(num_instances)
+        if K < 0:
+            raise ValueError("num_instances must not be negative")
+        dev = mask.device
+        if not (class_table.is_cuda and class_table.dtype == torch.int32 and class_table.is_contiguous()
+                and class_table.numel() >= K and class_table.device == dev):
+            raise ValueError("class_table: a contiguous int32 tensor of at least num_instances entries on the mask's GPU")
+        if scores is not None and not (scores.is_cuda and scores.dtype == torch.float32 and scores.is_contiguous()
+                                       and scores.numel() >= K and scores.device == dev):
+            raise ValueError("scores: a contiguous float32 tensor of at least num_instances entries on the mask's GPU")
+        if table is None:
+            table = self.instance_table(mask, K)
+        elif not (table.is_cuda and table.dtype == torch.int32 and table.is_contiguous() and table.device == dev
+                  and tuple(table.shape) == (K, 5)):
+            raise ValueError("table: the contiguous int32 [num_instances,5] tensor of instance_table()")
+        out_mask = mask if inplace else torch.empty_like(mask)
+        remap = torch.empty((K + 1,), dtype=torch.int32, device=dev)
+        table_out = torch.empty((K, 5), dtype=torch.int32, device=dev)
+        classes_out = torch.empty((K,), dtype=torch.int32, device=dev)
+        scores_out = torch.empty((K,), dtype=torch.float32, device=dev) if scores is not None else None
+        count = torch.empty((1,), dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        threshold = float("-inf") if min_score is None else float(min_score)
+        rc = fn(
+            self.handle, mask.data_ptr(), H, W, K, table.data_ptr(), class_table.data_ptr(),
+            scores.data_ptr() if scores is not None else None, int(min_area), threshold, out_mask.data_ptr(),
+            remap.data_ptr(), table_out.data_ptr(), classes_out.data_ptr(),
+            scores_out.data_ptr() if scores_out is not None else None, count.data_ptr(), ctypes.c_void_p(stream))
+        if rc != 0:
+            raise MergeNetError(rc)
+        new_k = int(count.item())                             # the one synchronisation
+        res = (out_mask, classes_out, scores_out[:new_k] if scores_out is not None else None, table_out[:new_k], new_k)
+        return res + (remap,) if return_remap else res
+
+    def coco_results(self, mask, class_table, num_instances: int, image_id, cat_ids, scores=None, min_area: int = 1):
+        """The detection results of one image, as ``convert_to_coco_result`` forms them
+        (egs/cityscape/local/segment.py:165-186), with the ``area`` and ``bbox`` that ``COCO.loadRes`` would add:
+        a list of ``{"image_id", "category_id": cat_ids[class], "score" (1 without ``scores``, segment.py:181),
+        "segmentation": {"size": [H, W], "counts": bytes}, "bbox": [x_min, y_min, width, height] as floats (the
+        documented COCO [x, y, w, h]), "area"}``, in label order after :meth:`filter_instances` (``min_area``)."""
+        fmask, classes, fscores, table, new_k = self.filter_instances(mask, class_table, num_instances,
+                                                                      min_area=min_area, scores=scores)
+        rles = self.encode_rle(fmask, new_k)
+        classes = classes[:new_k].cpu().numpy()
+        table = table.cpu().numpy()
+        fscores = fscores.cpu().numpy() if fscores is not None else None
+        res = []
+        for k in range(new_k):
+            area, x0, y0, x1, y1 = (int(v) for v in table[k])
+            res.append({"image_id": image_id, "category_id": cat_ids[int(classes[k])],
+                        "score": float(fscores[k]) if fscores is not None else 1,
+                        "segmentation": {"size": rles[k]["size"], "counts": rles[k]["counts"]},
+                        "bbox": [float(x0), float(y0), float(x1 - x0 + 1), float(y1 - y0 + 1)], "area": area})
+        return res
 
 
 class PendingSegment:
