@@ -130,8 +130,15 @@ typedef struct mn_options {
                                   of start/stop events on its own dispatch (round 2's first form:
                                   measures dispatch gap + kernel); bit 8: a 16-bit map's sweep takes 4
                                   pixels per lane (8-byte loads) where it would take 8 (16-byte loads) --
-                                  same results, for the measurement of the two forms.  (Round 4 removed the
-                                  opt-in engines that were measured slower or known to deviate: bits 3, 9-13.) */
+                                  same results, for the measurement of the two forms; bit 9 (512): the sweep
+                                  of components mode leaves the FULL form of its outputs (two mask words per
+                                  pixel, per-lane class log-products for every lane) where the default path
+                                  takes the lean form (one packed word for up to 16 offsets, one record per
+                                  uniform 64-pixel run) -- same results bit for bit, the yardstick of the lean
+                                  form inside one build; the replay key holds the options, so the two forms
+                                  never share graphs.  (Round 4 removed the opt-in engines that were measured
+                                  slower or known to deviate: bits 3, 10-13; bit 9 was among them and now
+                                  means the above.) */
   int require_proof;           /* what happens to a result that is not PROVEN equal to the reference's
                                   sequential order (stats.proof == 0): 1 = it is redone in MN_MODE_EXACT,
                                   whatever mode was asked for, and -- if that run chose among bit-equal

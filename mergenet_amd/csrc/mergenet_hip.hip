@@ -149,6 +149,7 @@ struct mn_context {
     hipGraphExec_t eA, eB;
     hipStream_t cap;       // capture happens here (the caller's stream may be the null stream, which cannot capture)
     Queued queued;         // of the attempt that recorded the graphs
+    int lean_form;         // ... and the form of the sweep's outputs its graphs read (sweep_lean_form)
   } replay;
   hipStream_t side;       // the single-workgroup tail of an image runs here, beside the next image's sweeps
   hipEvent_t ev_fork;
@@ -813,9 +814,27 @@ static size_t gsum_stride(int N) {
 #endif
 }
 
+// The lean form of what the sweep leaves (LeanOut in mn_kernels_cc.h: packed masks where O <= 16, one record per
+// uniform group of 64 pixels) is what the pure components path and its replay run on.  debug_flags bit 9 keeps the
+// full form there (the yardstick inside one build); so does an image too small for the records to fit into the
+// free part of the `lpsum` planes, or a build with skewed planes.
+static bool sweep_lean_form(const mn_context* c, const ImgParams& P, int px) {
+  return px >= 4 && !(c->debug_flags & 512) && P.N >= 64 && gsum_stride(P.N) == (size_t)P.N;
+}
+static LeanOut lean_out(const ImgParams& P, bool lean_form) {
+  LeanOut LO = {-1, 0, 0, 0};
+  if (!lean_form) return LO;
+  for (int k = 0; k < P.O; k++)
+    if (P.di[k] == 0 && P.dj[k] == 1) { LO.kh = k; break; }
+  LO.packed = P.O <= 16 ? 1 : 0;
+  LO.rec0 = (P.N / 4 + 1) & ~1;                     // (i64 records: an even int index behind the per-lane values)
+  LO.flag0 = LO.rec0 + 2 * ((P.N + 63) / 64);       // (the groups' words of plane 0 behind its records)
+  return LO;
+}
+
 // The sweep (mn_cc_sign) in the form for PX pixels per lane and maps of element type DT (LG: holding logits).
 template <int PX, int DT, bool LG = false>
-static void launch_sign(mn_context* c, const ImgParams& P, hipStream_t st, bool cls, bool lean_cls) {
+static void launch_sign(mn_context* c, const ImgParams& P, hipStream_t st, bool cls, bool lean_cls, bool lean_form) {
   const int N = P.N, ngroups = (N + PX - 1) / PX;
   const dim3 g(grid_for(ngroups, MN_CC_SIGN_THREADS)), b(MN_CC_SIGN_THREADS);
   ClsOut CO;
@@ -828,19 +847,23 @@ static void launch_sign(mn_context* c, const ImgParams& P, hipStream_t st, bool 
   // Timed: the dispatch itself carries the two events (hipExtLaunchKernel: start and stop time of THIS
   // kernel), instead of an event packet in front of it and one behind -- each of those cost a ~6 us
   // dispatch gap on the stream, and the pair measured gap + kernel (54 us where rocprofv3 saw 46).
-#define MN_LAUNCH_SIGN(PLAINV, CLSV)                                                                    \
+  lean_form = lean_form && lean_cls && cls && PX >= 4;
+  const LeanOut LO = lean_out(P, lean_form);
+#define MN_LAUNCH_SIGN(PLAINV, CLSV, LEANV)                                                             \
   do {                                                                                                \
     if (c->ext_events)                                                                                \
-      hipExtLaunchKernelGGL((mn_cc_sign<PX, PLAINV, (CLSV) && PX >= 4, DT, LG>), g, b, 0, st, c->ev[0], c->ev[10], 0, \
-                            P, c->cc_bits, c->cc_negbits, c->scalars + 6, c->partial, CO); \
+      hipExtLaunchKernelGGL((mn_cc_sign<PX, PLAINV, (CLSV) && PX >= 4, DT, LG, (LEANV) && PX >= 4>), g, b, 0, st, \
+                            c->ev[0], c->ev[10], 0, P, c->cc_bits, c->cc_negbits, c->scalars + 6, c->partial, CO, LO); \
     else                                                                                              \
-      hipLaunchKernelGGL((mn_cc_sign<PX, PLAINV, (CLSV) && PX >= 4, DT, LG>), g, b, 0, st, P, c->cc_bits, c->cc_negbits, \
-                         c->scalars + 6, c->partial, CO);                                             \
+      hipLaunchKernelGGL((mn_cc_sign<PX, PLAINV, (CLSV) && PX >= 4, DT, LG, (LEANV) && PX >= 4>), g, b, 0, st, P, \
+                         c->cc_bits, c->cc_negbits, c->scalars + 6, c->partial, CO, LO);              \
   } while (0)
-  if (plain && cls) MN_LAUNCH_SIGN(true, true);
-  else if (plain) MN_LAUNCH_SIGN(true, false);
-  else if (cls) MN_LAUNCH_SIGN(false, true);
-  else MN_LAUNCH_SIGN(false, false);
+  if (plain && lean_form) MN_LAUNCH_SIGN(true, true, true);
+  else if (lean_form) MN_LAUNCH_SIGN(false, true, true);
+  else if (plain && cls) MN_LAUNCH_SIGN(true, true, false);
+  else if (plain) MN_LAUNCH_SIGN(true, false, false);
+  else if (cls) MN_LAUNCH_SIGN(false, true, false);
+  else MN_LAUNCH_SIGN(false, false, false);
 #undef MN_LAUNCH_SIGN
 }
 
@@ -859,23 +882,26 @@ static int sweep_px(const mn_context* c, const ImgParams& P) {
 
 // The sweep in the form sweep_px chose (`cls`: it takes the class planes too; only with px >= 4).
 template <bool LG>
-static void launch_sweep_lg(mn_context* c, const ImgParams& P, hipStream_t st, int px, bool cls, bool lean_cls) {
-#define MN_SWEEP_DT(PXV)                                                                         \
-  do {                                                                                           \
-    if (P.dtype == MN_DTYPE_F16) launch_sign<PXV, MN_DTYPE_F16, LG>(c, P, st, cls, lean_cls);    \
-    else launch_sign<PXV, MN_DTYPE_BF16, LG>(c, P, st, cls, lean_cls);                           \
+static void launch_sweep_lg(mn_context* c, const ImgParams& P, hipStream_t st, int px, bool cls, bool lean_cls,
+                            bool lean_form) {
+#define MN_SWEEP_DT(PXV)                                                                                   \
+  do {                                                                                                     \
+    if (P.dtype == MN_DTYPE_F16) launch_sign<PXV, MN_DTYPE_F16, LG>(c, P, st, cls, lean_cls, lean_form);   \
+    else launch_sign<PXV, MN_DTYPE_BF16, LG>(c, P, st, cls, lean_cls, lean_form);                          \
   } while (0)
   if (P.dtype == MN_DTYPE_F32) {
-    if (px == 4) launch_sign<4, MN_DTYPE_F32, LG>(c, P, st, cls, lean_cls);
-    else launch_sign<1, MN_DTYPE_F32, LG>(c, P, st, false, false);
+    if (px == 4) launch_sign<4, MN_DTYPE_F32, LG>(c, P, st, cls, lean_cls, lean_form);
+    else launch_sign<1, MN_DTYPE_F32, LG>(c, P, st, false, false, false);
   } else if (px == 8) MN_SWEEP_DT(8);
   else if (px == 4) MN_SWEEP_DT(4);
-  else { cls = false; lean_cls = false; MN_SWEEP_DT(1); }
+  else { cls = false; lean_cls = false; lean_form = false; MN_SWEEP_DT(1); }
 #undef MN_SWEEP_DT
 }
-static void launch_sweep(mn_context* c, const ImgParams& P, hipStream_t st, int px, bool cls, bool lean_cls) {
-  if (P.logits) launch_sweep_lg<true>(c, P, st, px, cls, lean_cls);      // (the sigmoid on load: a compile-time form)
-  else launch_sweep_lg<false>(c, P, st, px, cls, lean_cls);
+// `lean_form`: only with `lean_cls` (the caller asks sweep_lean_form, or replays what it recorded)
+static void launch_sweep(mn_context* c, const ImgParams& P, hipStream_t st, int px, bool cls, bool lean_cls,
+                         bool lean_form = false) {
+  if (P.logits) launch_sweep_lg<true>(c, P, st, px, cls, lean_cls, lean_form);      // (the sigmoid on load: a compile-time form)
+  else launch_sweep_lg<false>(c, P, st, px, cls, lean_cls, lean_form);
 }
 
 // the sweep over the positive masks that hooks the offsets the tile stages did not take
@@ -941,7 +967,11 @@ static int run_components(mn_context* c, const ImgParams& P, hipStream_t& st, Cc
   const bool fused_cls = sweep4;
   // (pure components mode: the roots' class and validity flag are set by mn_cc_finish)
   const bool lean_cls = fused_cls && !cores;
-  launch_sweep(c, P, st, px, fused_cls, lean_cls);
+  // (... and there mn_cc_sums and mn_cc_cross are the only readers of what the sweep writes: its lean form)
+  const bool lean_form = lean_cls && sweep_lean_form(c, P, px);
+  const LeanOut LO = lean_out(P, lean_form);
+  if (c->replay.capturing) c->replay.lean_form = lean_form ? 1 : 0;
+  launch_sweep(c, P, st, px, fused_cls, lean_cls, lean_form);
   if (!few_events && !c->ext_events) MN_HIP(hipEventRecord(c->ev[10], st));
   // cores (first step of the general rounds): the labelling runs on the edges between clean pixels
   const unsigned* lbits = c->cc_bits;
@@ -1019,10 +1049,16 @@ static int run_components(mn_context* c, const ImgParams& P, hipStream_t& st, Cc
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       MN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mn_cc_sums),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      MN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mn_cc_sums_lean),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       c->cc_sum_lds = lds;
     }
     const unsigned blocks = grid_for((size_t)(N >> 2) > 0 ? (size_t)(N >> 2) : 1, MN_CC_SUM_THREADS);
-    if (fused_cls)
+    if (lean_form)
+      hipLaunchKernelGGL(mn_cc_sums_lean, dim3((unsigned)grid_for((size_t)(N + 63) / 64, MN_CC_LEAN_GROUPS)),
+                         dim3(MN_CC_LEAN_THREADS), lds, st, P, S, (const unsigned char*)c->cls0,
+                         (const int*)reinterpret_cast<int*>(c->lpsum), gsum_stride(P.N), LO, c->lp_acc, clsmin, clsmax);
+    else if (fused_cls)
       hipLaunchKernelGGL(mn_cc_sums, dim3((blocks + MN_CC_SUMS_ITERS - 1) / MN_CC_SUMS_ITERS), dim3(MN_CC_SUM_THREADS), lds, st, P, S,
                          (const unsigned char*)c->cls0, (const int*)reinterpret_cast<int*>(c->lpsum), gsum_stride(P.N),
                          c->lp_acc, clsmin, clsmax, cores ? (const unsigned char*)c->pruned : (const unsigned char*)nullptr);
@@ -1033,12 +1069,16 @@ static int run_components(mn_context* c, const ImgParams& P, hipStream_t& st, Cc
   if (!few_events && !lean) MN_HIP(hipEventRecord(c->ev[8], st));
   if (!cores)                      // (the rounds build their records from the pixel graph: positive ones too)
   {
+    // (lean form with packed masks: the negative ones are the upper half of the word the labelling read; the ends
+    //  are chased only in a build whose mn_cc_sums_lean does not leave parent[] flat, MN_CC_LEAN_FLAT = 0)
+    const bool packed = lean_form && LO.packed;
+    const unsigned* negsrc = packed ? (const unsigned*)c->cc_bits : (const unsigned*)c->cc_negbits;
     if (sweep4)
       hipLaunchKernelGGL(mn_cc_cross<4>, dim3((unsigned)grid_for((size_t)N / 4, MN_CC_CROSS_THREADS)), dim3(MN_CC_CROSS_THREADS),
-                         0, st, P, (const int*)c->parent, T, (const unsigned*)c->cc_negbits, c->scalars + 6, c->cc_tcount);
+                         0, st, P, (const int*)c->parent, T, negsrc, packed ? 16 : 0, lean_form && !MN_CC_LEAN_FLAT ? 1 : 0, c->scalars + 6, c->cc_tcount);
     else
       hipLaunchKernelGGL(mn_cc_cross<1>, dim3((unsigned)grid_for((size_t)N, MN_CC_CROSS_THREADS)), dim3(MN_CC_CROSS_THREADS),
-                         0, st, P, (const int*)c->parent, T, (const unsigned*)c->cc_negbits, c->scalars + 6, c->cc_tcount);
+                         0, st, P, (const int*)c->parent, T, negsrc, 0, 0, c->scalars + 6, c->cc_tcount);
   }
   if (!few_events && !lean) MN_HIP(hipEventRecord(c->ev[9], st));
   // Nothing waits for the verdict here: the object state and the record list are built right
@@ -2015,7 +2055,8 @@ static int replay_launch(mn_context* c, const ImageCall& call) {
   c->cores_used = 0;
   const bool timed = !(call.opts.debug_flags & 2) && !c->ext_events;
   if (timed) MN_HIP(hipEventRecord(c->ev[0], st));
-  launch_sweep(c, P, st, sweep_px(c, P), true, true);      // (the key holds buffers and dtype: the recorded form)
+  // (the key holds buffers, dtype and options: the recorded form, lean or full as the graphs expect it)
+  launch_sweep(c, P, st, sweep_px(c, P), true, true, c->replay.lean_form != 0);
   if (timed) MN_HIP(hipEventRecord(c->ev[10], st));
   MN_HIP(hipGraphLaunch(c->replay.eA, st));
   MN_HIP(hipEventRecord(c->ev_fork, st));
@@ -2418,7 +2459,8 @@ extern "C" int mn_sweep_time_device_t(mn_context* c, const void* const* d_class_
     for (int i = 0; i < n; i++) {
       call.d_class = d_class_pred[i % n_inputs]; call.d_adj = d_adj_pred[i % n_inputs];
       fill_params(&P, call);
-      launch_sweep(c, P, st, sweep_px(c, P), true, true);
+      const int px = sweep_px(c, P);
+      launch_sweep(c, P, st, px, true, true, sweep_lean_form(c, P, px));      // (debug_flags bit 9: the full form)
     }
     if (phase == 1) MN_HIP(hipEventRecord(c->ev[1], st));
   }

@@ -27,7 +27,9 @@
 //                  of the component;
 //   mn_cc_class_sums  the class pass: arg-max class of every pixel, component sizes, class
 //                  log-prob sums and class range (block table in LDS, 64-bit fixed-point atomics);
-//                  also leaves parent[] flat;
+//                  also leaves parent[] flat (where the sweep took the class planes too: mn_cc_sums on its
+//                  per-lane products, or -- the product path -- mn_cc_sums_lean on the lean form of the sweep's
+//                  outputs, LeanOut: packed masks, one record per uniform 64-pixel group);
 //   mn_cc_cross    the mask of negative out-edges -> records between components (block scan, LDS queue,
 //                  block table in LDS, then the global table); a negative edge inside a component fails (a);
 //   mn_cc_finish   fixed-point sums -> float object state, condition (c), list of component roots.
@@ -178,6 +180,53 @@ struct ClsOut {
   unsigned char* ocls; unsigned char* cls0; unsigned char* lpvalid; int* gsum; size_t gstride;
 };
 
+// LEAN (only with CLS; the pure components path, where nothing but mn_cc_sums and mn_cc_cross reads these
+// outputs): the sweep writes what those two need and no more.
+//  * packed masks (`packed`: O <= 16, decided on the host): ONE word per pixel, pos | neg << 16, in `bits`;
+//    `negbits` is not written.  The labelling stages test single bits below O, so they read the word as it is.
+//  * group records.  A group is the 64 pixels [64 g, 64 g + 64) in linear order -- 16 lanes (one DPP row) at
+//    PX = 4, 8 lanes at PX = 8.  It is UNIFORM iff offset `kh` is (0, +1) and bit kh of the positive mask, after
+//    the in-bounds masking, is set for its first 63 pixels: the 64 pixels are then one run of one row (the bit
+//    of column W - 1 is never set) and lie in one component whatever else happens.  All mn_cc_sums does with
+//    the 16 x C per-lane products of such a group is add them up, so the sweep adds them (integers: no bit of
+//    any sum changes) and writes ONE record: C sums as i64 at ints [rec0 + 2 g, +2) of plane c of `gsum`, and
+//    the word  1 | lowest arg-max class << 8 | highest << 16  at int flag0 + g of plane 0.  Its lanes write no
+//    per-lane products.  Every other group writes the word 0 and its per-lane products as ever.  The records
+//    live in the part of the planes the per-lane products leave free (N / 4 of N ints per plane).
+struct LeanOut { int kh; int packed; int rec0; int flag0; };
+#ifndef MN_CC_LEAN_FLAT
+#define MN_CC_LEAN_FLAT 1      /* 1: mn_cc_sums_lean leaves parent[] flat, as mn_cc_sums does; 0: it only reads parent[]
+                                  and mn_cc_cross chases at both ends of its edges.  Step of the benchmark loop, three
+                                  runs each, alternating: 0.1252-0.1264 ms (1) against 0.1269-0.1275 (0) -- the 8 MB
+                                  read once more here cost less than the chases in mn_cc_cross and mn_write_mask4 */
+#endif
+
+// Sum / minimum of a 32-bit value over the GL = 16 | 8 lanes of a group (all of them get it): quad_perm xor 1,
+// xor 2, row_half_mirror and (16 lanes) row_mirror -- moves on the VALU, no LDS crossbar.
+template <int GL>
+__device__ __forceinline__ int mn_group_sum32(int x) {
+  x += __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, false);
+  x += __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, false);
+  x += __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, false);
+  if constexpr (GL == 16) x += __builtin_amdgcn_update_dpp(0, x, 0x140, 0xF, 0xF, false);
+  return x;
+}
+template <int GL>
+__device__ __forceinline__ int mn_group_min(int x) {
+  x = min(x, __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false));
+  x = min(x, __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false));
+  x = min(x, __builtin_amdgcn_update_dpp(x, x, 0x141, 0xF, 0xF, false));
+  if constexpr (GL == 16) x = min(x, __builtin_amdgcn_update_dpp(x, x, 0x140, 0xF, 0xF, false));
+  return x;
+}
+// The sum of the group's per-lane products `gv` (`n` of them per lane), exact: the low and the high 16 bits are
+// summed apart -- at most 16 x 65535 and 16 x 2^15 in magnitude, so 32-bit adds do -- and put together in 64 bits
+// by the one lane that stores (a 64-bit sum over DPP costs twice the moves and twice the adds).
+template <int GL>
+__device__ __forceinline__ i64 mn_group_sum_exact(int lo, int hi) {
+  return ((i64)mn_group_sum32<GL>(hi) << 16) + (i64)mn_group_sum32<GL>(lo);
+}
+
 // first maximum of logf over the classes of one pixel (Object::Object, segment.cc:5-21)
 __device__ __forceinline__ int mn_cc_argmax_logf(const ImgParams& P, int p) {
   float best = 0.0f;
@@ -203,8 +252,9 @@ __device__ __forceinline__ int mn_cc_argmax_logf_t(const ImgParams& P, int p) {
   return b;
 }
 
-template <int DT, bool LG = false>
-__device__ __forceinline__ void mn_cc_class_part(const ImgParams& P, const ClsOut& CO, int i) {
+template <int DT, bool LG = false, bool LEAN = false>
+__device__ __forceinline__ void mn_cc_class_part(const ImgParams& P, const ClsOut& CO, int i, bool uni = false,
+                                                 const LeanOut& LO = LeanOut()) {
   // The arg-max is taken on the VALUES (logf is monotone); the reference's first-maximum rule on
   // logf values differs only if a class of LOWER index lies within rounding distance of the maximum
   // (logf may map both to one float): `prev` keeps the largest value below the current best's index
@@ -228,6 +278,16 @@ __device__ __forceinline__ void mn_cc_class_part(const ImgParams& P, const ClsOu
       if (v.w > best.w) { prev.w = best.w; best.w = v.w; b3 = c; }
     }
     // float * 2^24 is exact: the term is the exact product rounded to the nearest integer
+    if constexpr (LEAN) {
+      const int gv = __float2int_rn(logf((v.x * v.y) * (v.z * v.w)) * 16777216.0f);
+      if (uni) {                                          // (whole DPP rows take this branch together)
+        const i64 gs = mn_group_sum_exact<16>(gv & 0xFFFF, gv >> 16);
+        if ((threadIdx.x & 15) == 0)
+          *reinterpret_cast<i64*>(&CO.gsum[(size_t)c * CO.gstride + LO.rec0 + 2 * (size_t)(i >> 4)]) = gs;
+      } else {
+        mn_st_stream(&CO.gsum[(size_t)c * CO.gstride + i], gv);
+      }
+    } else
     mn_st_stream(&CO.gsum[(size_t)c * CO.gstride + i], __float2int_rn(logf((v.x * v.y) * (v.z * v.w)) * 16777216.0f));
   }
   // a lower class within 2^-18 of the maximum (logs of magnitude < 16 are 2^-20 apart at most, and
@@ -244,14 +304,24 @@ __device__ __forceinline__ void mn_cc_class_part(const ImgParams& P, const ClsOu
   if (CO.ocls) *reinterpret_cast<uchar4*>(CO.ocls + 4 * (size_t)i) = o;
   *reinterpret_cast<uchar4*>(CO.cls0 + 4 * (size_t)i) = o;
   if (CO.lpvalid) *reinterpret_cast<uchar4*>(CO.lpvalid + 4 * (size_t)i) = make_uchar4(0, 0, 0, 0);
+  if constexpr (LEAN) {
+    int word = 0;
+    if (uni) {
+      const int lo = mn_group_min<16>(min(min(b0, b1), min(b2, b3)));
+      const int hi = -mn_group_min<16>(-max(max(b0, b1), max(b2, b3)));
+      word = 1 | (lo << 8) | (hi << 16);
+    }
+    if ((threadIdx.x & 15) == 0) CO.gsum[LO.flag0 + (i >> 4)] = word;
+  }
 }
 
 // The same for a lane of EIGHT pixels of a 16-bit map (one 16-byte load per class plane): groups 2i and 2i + 1
 // of the layout above, so gsum, cls0 and everything behind the sweep are what the 4-pixel form leaves.  The
 // arithmetic per 4-pixel group is that of mn_cc_class_part on the widened values (a 16-bit map is always
 // clipped on load), so the outputs are bit-equal to the float32 sweep's on maps.float().
-template <int DT, bool LG = false>
-__device__ __forceinline__ void mn_cc_class_part8(const ImgParams& P, const ClsOut& CO, int i) {
+template <int DT, bool LG = false, bool LEAN = false>
+__device__ __forceinline__ void mn_cc_class_part8(const ImgParams& P, const ClsOut& CO, int i, bool uni = false,
+                                                  const LeanOut& LO = LeanOut()) {
   float best[8], prev[8];
   int b[8];
 #pragma unroll
@@ -271,6 +341,15 @@ __device__ __forceinline__ void mn_cc_class_part8(const ImgParams& P, const ClsO
     int2 g;
     g.x = __float2int_rn(logf((v[0] * v[1]) * (v[2] * v[3])) * 16777216.0f);
     g.y = __float2int_rn(logf((v[4] * v[5]) * (v[6] * v[7])) * 16777216.0f);
+    if constexpr (LEAN) {
+      if (uni) {                                          // (a group is 8 lanes here: half a DPP row)
+        const i64 gs = mn_group_sum_exact<8>((g.x & 0xFFFF) + (g.y & 0xFFFF), (g.x >> 16) + (g.y >> 16));
+        if ((threadIdx.x & 7) == 0)
+          *reinterpret_cast<i64*>(&CO.gsum[(size_t)c * CO.gstride + LO.rec0 + 2 * (size_t)(i >> 3)]) = gs;
+      } else {
+        *reinterpret_cast<int2*>(&CO.gsum[(size_t)c * CO.gstride + 2 * (size_t)i]) = g;
+      }
+    } else
     *reinterpret_cast<int2*>(&CO.gsum[(size_t)c * CO.gstride + 2 * (size_t)i]) = g;
   }
   const float near = 1.0f - 3.814697265625e-06f;
@@ -283,6 +362,17 @@ __device__ __forceinline__ void mn_cc_class_part8(const ImgParams& P, const ClsO
   if (CO.ocls) *reinterpret_cast<uint2*>(CO.ocls + 8 * (size_t)i) = o;
   *reinterpret_cast<uint2*>(CO.cls0 + 8 * (size_t)i) = o;
   if (CO.lpvalid) *reinterpret_cast<uint2*>(CO.lpvalid + 8 * (size_t)i) = make_uint2(0u, 0u);
+  if constexpr (LEAN) {
+    int word = 0;
+    if (uni) {
+      int lo1 = b[0], hi1 = b[0];
+#pragma unroll
+      for (int j = 1; j < 8; j++) { lo1 = min(lo1, b[j]); hi1 = max(hi1, b[j]); }
+      const int lo = mn_group_min<8>(lo1), hi = -mn_group_min<8>(-hi1);
+      word = 1 | (lo << 8) | (hi << 16);
+    }
+    if ((threadIdx.x & 7) == 0) CO.gsum[LO.flag0 + (i >> 3)] = word;
+  }
 }
 
 // DT: element type of the maps.  MN_DTYPE_F32 takes PX = 4 | 1 as described above.  A 16-bit map takes PX = 8
@@ -290,17 +380,21 @@ __device__ __forceinline__ void mn_cc_class_part8(const ImgParams& P, const ClsO
 // 16-byte aligned planes), else PX = 4 with 8-byte loads, else PX = 1; its PLAIN form clips (mn_cc_value).
 // LG: the maps hold logits of element type DT, PX by the same rule.  The sigmoid is taken where a value is
 // loaded, so the neutral 1.0 of an out-of-image edge below stays a probability; PLAIN is sigmoid + clip.
-template <int PX, bool PLAIN, bool CLS, int DT = MN_DTYPE_F32, bool LG = false>
+// LEAN (with CLS): packed masks and group records, see LeanOut.  Whether a group is uniform must be known when
+// the class part stores, so in this form the class part runs BEHIND the sameness part, after the masks are
+// stored (nothing of them stays in registers across it).
+template <int PX, bool PLAIN, bool CLS, int DT = MN_DTYPE_F32, bool LG = false, bool LEAN = false>
 __global__ __launch_bounds__(MN_CC_SIGN_THREADS) void mn_cc_sign(
     ImgParams P, unsigned* __restrict__ bits, unsigned* __restrict__ negbits, int* __restrict__ violations,
-    double* __restrict__ partial, ClsOut CO) {
+    double* __restrict__ partial, ClsOut CO, LeanOut LO) {
+  static_assert(!LEAN || (CLS && PX >= 4), "the lean form belongs to the sweep that takes the class planes");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int ngroups = (P.N + PX - 1) / PX;
   const int i = blockIdx.x * MN_CC_SIGN_THREADS + threadIdx.x;
   const bool live = i < ngroups;
   const int p0 = live ? PX * i : 0;
   const int r = p0 / P.W, c0 = p0 - r * P.W;
-  if constexpr (CLS) {
+  if constexpr (CLS && !LEAN) {
     if (live) {
       if constexpr (PX == 8) mn_cc_class_part8<DT, LG>(P, CO, i);
       else mn_cc_class_part<DT, LG>(P, CO, i);
@@ -406,6 +500,15 @@ __global__ __launch_bounds__(MN_CC_SIGN_THREADS) void mn_cc_sign(
   // MB).  Until round 3 the sweep itself queued them in LDS behind a block-wide scan and wrote a list of
   // (edge, log-odds): two barriers and a dependent pass at the end of every block, 6.5 of 43.8 us (the sweep
   // without it: 37.3 us; a kernel that only moves the sweep's bytes: 34.3 us -- tools/stream_ceiling.hip).
+  if (LEAN && LO.packed) {                               // (O <= 16: both masks in one word, one array)
+#pragma unroll
+    for (int j = 0; j < PX; j++) m[j] |= ng[j] << 16;
+    if (live) {
+      mn_st_stream(reinterpret_cast<uint4*>(bits + p0), make_uint4(m[0], m[1 % PX], m[2 % PX], m[3 % PX]));
+      if (PX == 8)
+        mn_st_stream(reinterpret_cast<uint4*>(bits + p0) + 1, make_uint4(m[4 % PX], m[5 % PX], m[6 % PX], m[7 % PX]));
+    }
+  } else
   if (live) {
     if (PX == 8) {
       mn_st_stream(reinterpret_cast<uint4*>(bits + p0), make_uint4(m[0], m[1 % PX], m[2 % PX], m[3 % PX]));
@@ -418,6 +521,22 @@ __global__ __launch_bounds__(MN_CC_SIGN_THREADS) void mn_cc_sign(
     } else {
       bits[p0] = m[0];
       negbits[p0] = ng[0];
+    }
+  }
+  if constexpr (LEAN) {
+    // uniform group: the link to the next pixel (bit kh; the packed negative half lies above it) is positive for
+    // all of the lane's pixels but the group's last; a group with a lane past the end of the image is never one
+    constexpr int GL = 64 / PX;                          // lanes of a group
+    const unsigned hb = LO.kh >= 0 ? 1u << LO.kh : 0u;
+    unsigned all = live ? hb : 0u;
+#pragma unroll
+    for (int j = 0; j < PX - 1; j++) all &= m[j];
+    if ((lane & (GL - 1)) != GL - 1) all &= m[PX - 1];
+    const unsigned long long bal = __ballot(all != 0u);
+    const bool uni = ((unsigned)(bal >> (lane & ~(GL - 1))) & ((1u << GL) - 1u)) == ((1u << GL) - 1u);
+    if (live) {
+      if constexpr (PX == 8) mn_cc_class_part8<DT, LG, true>(P, CO, i, uni, LO);
+      else mn_cc_class_part<DT, LG, true>(P, CO, i, uni, LO);
     }
   }
   for (int off = 32; off > 0; off >>= 1) {
@@ -1051,6 +1170,51 @@ __device__ __forceinline__ void mn_cc_sums_pixelwise(const ImgParams& P, const O
   mn_cc_add(P, S, s_root, s_val, lp_acc, r.w, c, s3, (i64)__float2int_rn(logf(vw) * (float)MN_LP_FIX));
 }
 
+// item (lane `g` of the boundary queue, class c): per-pixel logs from the class planes, roots by a chase from
+// whatever is visible
+__device__ __forceinline__ void mn_cc_sums_boundary_item(const ImgParams& P, const ObjState& S, int* s_root,
+                                                         u64* s_val, int* s_min, int* s_max,
+                                                         const unsigned char* __restrict__ cls0,
+                                                         i64* __restrict__ lp_acc, int* __restrict__ clsmin,
+                                                         int* __restrict__ clsmax, int g, int c) {
+  int4 r;                                             // (a chase from whatever is visible ends at the root)
+  r.x = mn_cc_root_ro(S.parent, 4 * g); r.y = mn_cc_root_ro(S.parent, 4 * g + 1);
+  r.z = mn_cc_root_ro(S.parent, 4 * g + 2); r.w = mn_cc_root_ro(S.parent, 4 * g + 3);
+  const int s0 = mn_lds_root_slot(s_root, r.x), s1 = mn_lds_root_slot(s_root, r.y);
+  const int s2 = mn_lds_root_slot(s_root, r.z), s3 = mn_lds_root_slot(s_root, r.w);
+  const float4 v = mn_ld_class4(P, c, 4 * g);
+  mn_cc_sums_pixelwise(P, S, s_root, s_val, lp_acc, r, c, s0, s1, s2, s3, v);
+  if (c == 0) {
+    const uchar4 b = *reinterpret_cast<const uchar4*>(cls0 + 4 * (size_t)g);
+    mn_cc_add(P, S, s_root, s_val, lp_acc, r.x, P.C, s0, 1);
+    mn_cc_add(P, S, s_root, s_val, lp_acc, r.y, P.C, s1, 1);
+    mn_cc_add(P, S, s_root, s_val, lp_acc, r.z, P.C, s2, 1);
+    mn_cc_add(P, S, s_root, s_val, lp_acc, r.w, P.C, s3, 1);
+    mn_cc_cls(s_min, s_max, clsmin, clsmax, r.x, s0, b.x, b.x);
+    mn_cc_cls(s_min, s_max, clsmin, clsmax, r.y, s1, b.y, b.y);
+    mn_cc_cls(s_min, s_max, clsmin, clsmax, r.z, s2, b.z, b.z);
+    mn_cc_cls(s_min, s_max, clsmin, clsmax, r.w, s3, b.w, b.w);
+  }
+}
+
+// the block's table -> the global sums: ONE global atomic per root and class
+template <int THREADS>
+__device__ __forceinline__ void mn_cc_sums_flush(const ImgParams& P, const ObjState& S, int* s_root, u64* s_val,
+                                                 int* s_min, int* s_max, i64* __restrict__ lp_acc,
+                                                 int* __restrict__ clsmin, int* __restrict__ clsmax) {
+  const int nval = MN_CC_SUM_SLOTS * (P.C + 1);
+  if (threadIdx.x < MN_CC_SUM_SLOTS && s_root[threadIdx.x] >= 0) {
+    atomicMin(&clsmin[s_root[threadIdx.x]], s_min[threadIdx.x]);
+    atomicMax(&clsmax[s_root[threadIdx.x]], s_max[threadIdx.x]);
+  }
+  for (int j = threadIdx.x; j < nval; j += THREADS) {
+    const u64 v = s_val[j];
+    if (v == 0) continue;
+    const int slot = j / (P.C + 1), c = j - slot * (P.C + 1);
+    mn_cc_add(P, S, s_root, s_val, lp_acc, s_root[slot], c, -1, (i64)v);
+  }
+}
+
 // Class sums of the components from what the sweep left (CLS form of mn_cc_sign): per lane and
 // class the fixed-point log of the product of its four values, per pixel the arg-max class.  A lane
 // whose four pixels share a component -- nearly all -- adds its C numbers and its class range to
@@ -1182,37 +1346,128 @@ __global__ __launch_bounds__(MN_CC_SUM_THREADS) void mn_cc_sums(
         }
         continue;
       }
-      int4 r;                                             // (a chase from whatever is visible ends at the root)
-      r.x = mn_cc_root_ro(S.parent, 4 * g); r.y = mn_cc_root_ro(S.parent, 4 * g + 1);
-      r.z = mn_cc_root_ro(S.parent, 4 * g + 2); r.w = mn_cc_root_ro(S.parent, 4 * g + 3);
-      const int s0 = mn_lds_root_slot(s_root, r.x), s1 = mn_lds_root_slot(s_root, r.y);
-      const int s2 = mn_lds_root_slot(s_root, r.z), s3 = mn_lds_root_slot(s_root, r.w);
-      const float4 v = mn_ld_class4(P, c, 4 * g);
-      mn_cc_sums_pixelwise(P, S, s_root, s_val, lp_acc, r, c, s0, s1, s2, s3, v);
-      if (c == 0) {
-        const uchar4 b = *reinterpret_cast<const uchar4*>(cls0 + 4 * (size_t)g);
-        mn_cc_add(P, S, s_root, s_val, lp_acc, r.x, P.C, s0, 1);
-        mn_cc_add(P, S, s_root, s_val, lp_acc, r.y, P.C, s1, 1);
-        mn_cc_add(P, S, s_root, s_val, lp_acc, r.z, P.C, s2, 1);
-        mn_cc_add(P, S, s_root, s_val, lp_acc, r.w, P.C, s3, 1);
-        mn_cc_cls(s_min, s_max, clsmin, clsmax, r.x, s0, b.x, b.x);
-        mn_cc_cls(s_min, s_max, clsmin, clsmax, r.y, s1, b.y, b.y);
-        mn_cc_cls(s_min, s_max, clsmin, clsmax, r.z, s2, b.z, b.z);
-        mn_cc_cls(s_min, s_max, clsmin, clsmax, r.w, s3, b.w, b.w);
-      }
+      mn_cc_sums_boundary_item(P, S, s_root, s_val, s_min, s_max, cls0, lp_acc, clsmin, clsmax, g, c);
     }
   }
   __syncthreads();
-  if (threadIdx.x < MN_CC_SUM_SLOTS && s_root[threadIdx.x] >= 0) {
-    atomicMin(&clsmin[s_root[threadIdx.x]], s_min[threadIdx.x]);
-    atomicMax(&clsmax[s_root[threadIdx.x]], s_max[threadIdx.x]);
+  mn_cc_sums_flush<MN_CC_SUM_THREADS>(P, S, s_root, s_val, s_min, s_max, lp_acc, clsmin, clsmax);
+}
+
+// The same from the LEAN form of what the sweep left (LeanOut; never with cores).  A block takes
+// MN_CC_LEAN_GROUPS groups of 64 pixels -- the 4096 pixels per flush of the block's table that mn_cc_sums has.
+//  1. One lane per group reads the group's word.  A uniform group costs ONE root look-up from its first pixel
+//     (a pixel may be one or two steps from its root after the hook; the 64 pixels share the root even where
+//     their `parent` entries differ), then C sums, the count 64 and the class range go into the block's table:
+//     neither `cls0` nor a per-lane value is read for it.  The others are listed in LDS.
+//  2. The listed groups are worked off 16 lanes each, by all lanes of the block, the way every lane of
+//     mn_cc_sums goes; lanes across a component boundary are queued and
+//  3. worked off one (lane, class) item each.
+//  (MN_CC_LEAN_FLAT, the default: between 2 and 3 every lane of the block's pixels re-roots its four `parent`
+//  entries and writes back those the hook left one or two steps from their root, as mn_cc_sums does.  Without it
+//  `parent` is only read here and mn_cc_cross chases at both ends of its edges, as mn_write_mask4 always does:
+//  measured slower, see the macro.)
+// With five groups in six uniform, 16 lanes per group would leave most of a wide block idle: 256 lanes, of
+// which stage 1 uses 64 and stage 2 about 160 at the benchmark's maps.
+#define MN_CC_LEAN_THREADS 256
+#define MN_CC_LEAN_GROUPS 64
+__global__ __launch_bounds__(MN_CC_LEAN_THREADS) void mn_cc_sums_lean(
+    ImgParams P, ObjState S, const unsigned char* __restrict__ cls0, const int* __restrict__ gsum,
+    size_t gstride, LeanOut LO, i64* __restrict__ lp_acc, int* __restrict__ clsmin, int* __restrict__ clsmax) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char cc_smem[];
+  u64* s_val = reinterpret_cast<u64*>(cc_smem);                   // [SLOTS][C+1], index C = count
+  __shared__ int s_root[MN_CC_SUM_SLOTS];
+  __shared__ int s_min[MN_CC_SUM_SLOTS];
+  __shared__ int s_max[MN_CC_SUM_SLOTS];
+  __shared__ int s_grp[MN_CC_LEAN_GROUPS];                        // groups that are not uniform
+  __shared__ int s_q[MN_CC_LEAN_GROUPS * 16];                     // (a lane queues at most once)
+  __shared__ int s_ngrp, s_qn;
+  const int nval = MN_CC_SUM_SLOTS * (P.C + 1);
+  for (int i = threadIdx.x; i < nval; i += MN_CC_LEAN_THREADS) s_val[i] = 0;
+  if (threadIdx.x == 0) { s_ngrp = 0; s_qn = 0; }
+  if (threadIdx.x < MN_CC_SUM_SLOTS) { s_root[threadIdx.x] = -1; s_min[threadIdx.x] = 255; s_max[threadIdx.x] = 0; }
+  __syncthreads();
+  constexpr int G = MN_CC_SUMS_G;
+  const int n4 = P.N >> 2, ngroups = (n4 + 15) >> 4;
+  const int g0 = blockIdx.x * MN_CC_LEAN_GROUPS;
+  if (threadIdx.x < MN_CC_LEAN_GROUPS && g0 + (int)threadIdx.x < ngroups) {
+    const int grp = g0 + (int)threadIdx.x;
+    const int word = gsum[LO.flag0 + grp];
+    if (word & 1) {
+      const int root = mn_cc_root_ro(S.parent, 64 * grp);
+      const int s0 = mn_lds_root_slot(s_root, root);
+      for (int c0 = 0; c0 < P.C; c0 += G) {
+        i64 v[G];
+#pragma unroll
+        for (int a = 0; a < G; a++)
+          v[a] = c0 + a < P.C ? *reinterpret_cast<const i64*>(&gsum[(size_t)(c0 + a) * gstride + LO.rec0 + 2 * (size_t)grp]) : 0;
+#pragma unroll
+        for (int a = 0; a < G; a++) {
+          if (c0 + a >= P.C) break;
+          mn_cc_add(P, S, s_root, s_val, lp_acc, root, c0 + a, s0, v[a]);
+        }
+      }
+      mn_cc_add(P, S, s_root, s_val, lp_acc, root, P.C, s0, 64);
+      mn_cc_cls(s_min, s_max, clsmin, clsmax, root, s0, (word >> 8) & 255, (word >> 16) & 255);
+    } else {
+      s_grp[atomicAdd(&s_ngrp, 1)] = (int)threadIdx.x;
+    }
   }
-  for (int j = threadIdx.x; j < nval; j += MN_CC_SUM_THREADS) {
-    const u64 v = s_val[j];
-    if (v == 0) continue;
-    const int slot = j / (P.C + 1), c = j - slot * (P.C + 1);
-    mn_cc_add(P, S, s_root, s_val, lp_acc, s_root[slot], c, -1, (i64)v);
+  __syncthreads();
+  const int nlanes = s_ngrp * 16;
+  for (int t = threadIdx.x; t < nlanes; t += MN_CC_LEAN_THREADS) {
+    const int i = (g0 + s_grp[t >> 4]) * 16 + (t & 15);
+    if (i >= n4) continue;
+    int4 r = *reinterpret_cast<const int4*>(S.parent + 4 * (size_t)i);
+    const uchar4 b = *reinterpret_cast<const uchar4*>(cls0 + 4 * (size_t)i);
+    int g[G];
+#pragma unroll
+    for (int a = 0; a < G; a++) g[a] = a < P.C ? gsum[(size_t)a * gstride + i] : 0;
+    r.x = mn_cc_root_ro(S.parent, r.x);
+    r.y = r.y == r.x ? r.x : mn_cc_root_ro(S.parent, r.y);
+    r.z = r.z == r.x ? r.x : mn_cc_root_ro(S.parent, r.z);
+    r.w = r.w == r.x ? r.x : mn_cc_root_ro(S.parent, r.w);
+    if (r.x == r.y && r.x == r.z && r.x == r.w) {
+      const int s0 = mn_lds_root_slot(s_root, r.x);
+      for (int c0 = 0; c0 < P.C; c0 += G) {
+        if (c0 > 0) {
+#pragma unroll
+          for (int a = 0; a < G; a++) g[a] = c0 + a < P.C ? gsum[(size_t)(c0 + a) * gstride + i] : 0;
+        }
+#pragma unroll
+        for (int a = 0; a < G; a++) {
+          if (c0 + a >= P.C) break;
+          mn_cc_add(P, S, s_root, s_val, lp_acc, r.x, c0 + a, s0, (i64)g[a]);
+        }
+      }
+      mn_cc_add(P, S, s_root, s_val, lp_acc, r.x, P.C, s0, 4);
+      mn_cc_cls(s_min, s_max, clsmin, clsmax, r.x, s0, min(min((int)b.x, (int)b.y), min((int)b.z, (int)b.w)),
+                max(max((int)b.x, (int)b.y), max((int)b.z, (int)b.w)));
+    } else {
+      s_q[atomicAdd(&s_qn, 1)] = i;
+    }
   }
+#if MN_CC_LEAN_FLAT
+  for (int t = threadIdx.x; t < MN_CC_LEAN_GROUPS * 16; t += MN_CC_LEAN_THREADS) {      // every lane of the block's pixels
+    const int i = g0 * 16 + t;
+    if (i >= n4) continue;
+    int4 r = *reinterpret_cast<const int4*>(S.parent + 4 * (size_t)i);
+    const int4 r_in = r;
+    r.x = mn_cc_root_ro(S.parent, r.x);
+    r.y = r.y == r_in.x ? r.x : mn_cc_root_ro(S.parent, r.y);
+    r.z = r.z == r_in.x ? r.x : mn_cc_root_ro(S.parent, r.z);
+    r.w = r.w == r_in.x ? r.x : mn_cc_root_ro(S.parent, r.w);
+    if (r.x != r_in.x || r.y != r_in.y || r.z != r_in.z || r.w != r_in.w)
+      *reinterpret_cast<int4*>(S.parent + 4 * (size_t)i) = r;
+  }
+#endif
+  __syncthreads();
+  const int nq = s_qn;
+  for (int t = threadIdx.x; t < nq * P.C; t += MN_CC_LEAN_THREADS) {
+    const int item = t / P.C;
+    mn_cc_sums_boundary_item(P, S, s_root, s_val, s_min, s_max, cls0, lp_acc, clsmin, clsmax, s_q[item], t - item * P.C);
+  }
+  __syncthreads();
+  mn_cc_sums_flush<MN_CC_LEAN_THREADS>(P, S, s_root, s_val, s_min, s_max, lp_acc, clsmin, clsmax);
 }
 
 // insert with a bounded probe sequence: the table is sized for "few records between components";
@@ -1268,8 +1523,11 @@ __device__ __forceinline__ bool mn_cc_lds_add_cnt(u64* s_key, u64* s_sum, int* s
 #define MN_CC_CROSS_THREADS 256
 template <int PX>
 __global__ __launch_bounds__(MN_CC_CROSS_THREADS) void mn_cc_cross(
-    ImgParams P, const int* __restrict__ parent, HashTab T, const unsigned* __restrict__ negbits,
-    int* __restrict__ violations, int* __restrict__ tcount) {
+    ImgParams P, const int* __restrict__ parent, HashTab T, const unsigned* __restrict__ negbits, int shift,
+    int chase, int* __restrict__ violations, int* __restrict__ tcount) {
+  // `shift`: 16 with the packed masks of the sweep's lean form (the word the labelling read, negative half
+  // above the positive one), else 0 and `negbits` is the array of negative masks.  `chase`: parent[] was not
+  // left flat (mn_cc_sums_lean) -- both ends are chased to their roots.
   constexpr int QCAP = MN_CC_CROSS_THREADS * PX * MN_MAX_OFFSETS > 10240 ? 10240 : MN_CC_CROSS_THREADS * PX * MN_MAX_OFFSETS;
   __shared__ unsigned short s_item[QCAP];
   __shared__ int s_w[MN_CC_CROSS_THREADS / 64];
@@ -1285,9 +1543,9 @@ __global__ __launch_bounds__(MN_CC_CROSS_THREADS) void mn_cc_cross(
   if (i < ngroups) {
     if (PX == 4) {
       const uint4 t = *reinterpret_cast<const uint4*>(negbits + 4 * (size_t)i);
-      ng[0] = t.x; ng[1 % PX] = t.y; ng[2 % PX] = t.z; ng[3 % PX] = t.w;
+      ng[0] = t.x >> shift; ng[1 % PX] = t.y >> shift; ng[2 % PX] = t.z >> shift; ng[3 % PX] = t.w >> shift;
     } else {
-      ng[0] = negbits[i];
+      ng[0] = negbits[i] >> shift;
     }
   }
   int nneg = 0;
@@ -1333,7 +1591,7 @@ __global__ __launch_bounds__(MN_CC_CROSS_THREADS) void mn_cc_cross(
         const int p = blockIdx.x * (MN_CC_CROSS_THREADS * PX) + (int)(it >> 5);
         const int q = p + P.di[k] * P.W + P.dj[k];
         const float x = mn_same_value(P, mn_ld_same(P, k, p));
-        const int ru = parent[p], rv = parent[q];
+        const int ru = chase ? mn_cc_root_ro(parent, p) : parent[p], rv = chase ? mn_cc_root_ro(parent, q) : parent[q];
         if (ru == rv) bad++;                                           // (a)
         else {
           key = mn_key(ru, rv);

@@ -133,3 +133,25 @@ def filter_instances(mask: np.ndarray, class_table, num_instances: int, table: n
     if scores is not None:
         new_scores = np.asarray([scores[k - 1] for k in kept], np.float32)
     return out, new_classes, new_scores, new_table, len(kept), remap
+
+
+# ---- uniform groups of the sweep's lean form: the numpy twin of the rule in mn_cc_sign ----------------------
+
+def uniform_groups(pos_bits: np.ndarray, offsets) -> np.ndarray:
+    """bool [ceil(N / 64)]: group g is the pixels [64 g, 64 g + 64) of the image in linear order.  It is uniform iff
+    the offset list holds (0, +1) -- as offset k -- and bit k of the positive mask is set for its first 63 pixels;
+    a last group of fewer than 64 pixels never is.  `pos_bits`: [H, W] positive out-edge masks (bit k = offset k,
+    only in-bounds edges set: the bit of a row's last column is never set, so no group across a row's end is
+    uniform)."""
+    bits = np.asarray(pos_bits).astype(np.int64).reshape(-1) & 0xFFFFFFFF
+    n = bits.size
+    groups = (n + 63) // 64
+    flags = np.zeros(groups, bool)
+    offs = [(int(i), int(j)) for (i, j) in offsets]
+    if (0, 1) not in offs:
+        return flags
+    k = offs.index((0, 1))
+    link = ((bits >> k) & 1).astype(bool)
+    full = n // 64
+    flags[:full] = link[: full * 64].reshape(full, 64)[:, :63].all(axis=1)
+    return flags
