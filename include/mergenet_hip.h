@@ -90,6 +90,30 @@ enum mn_proof {
 #define MN_TIE_LIMIT_RECORDS 400000   /* MN_TIES_DEFAULT: largest image (initial records) redone in the reference's order */
 #define MN_TIE_LIMIT_BATCH_RECORDS 1400000   /* ... inside mn_segment_exact_batch, where the images are redone together (256x512 at O = 10) */
 
+/* mn_options.debug_flags.  (Round 4 removed the opt-in engines that were measured slower or known to deviate: bits 3,
+   10-13; bit 9 was among them and now means the below.) */
+enum mn_debug_flags {
+  MN_DEBUG_GENERIC_EDGE_PASS = 1,      /* use the generic edge pass where the fast form would run (tests compare the two) */
+  MN_DEBUG_NO_EVENTS = 2,              /* no per-kernel timestamps in components mode (ms_cc_* stay 0; each is an event
+                                          on the caller's stream) */
+  MN_DEBUG_NO_CORES = 4,               /* general rounds from single pixels instead of from the cores */
+  MN_DEBUG_LEAN_EVENTS = 16,           /* only the sweep is timed (ms_cc_edges; the other ms_* stay 0) -- an event costs
+                                          the host ~3.5 us to record and ~8 us to read */
+  MN_DEBUG_REPLAY = 32,                /* (with MN_DEBUG_LEAN_EVENTS) replay -- when mn_segment_launch is called again with
+                                          the same buffers, shape, options and stream, the launches after the sweep are
+                                          recorded into two hipGraphs (second call) and replayed (from the third): a loop
+                                          over images through fixed buffers */
+  MN_DEBUG_SWEEP_EVENT_PACKETS = 128,  /* time the sweep with an event packet before and behind it instead of start/stop
+                                          events on its own dispatch (round 2's first form: measures dispatch gap + kernel) */
+  MN_DEBUG_SWEEP16_4PX = 256,          /* a 16-bit map's sweep takes 4 pixels per lane (8-byte loads) where it would take 8
+                                          (16-byte loads) -- same results, for the measurement of the two forms */
+  MN_DEBUG_SWEEP_FULL_FORM = 512       /* the sweep of components mode leaves the FULL form of its outputs (two mask words
+                                          per pixel, per-lane class log-products for every lane) where the default path
+                                          takes the lean form (one packed word for up to 16 offsets, one record per uniform
+                                          64-pixel run) -- same results bit for bit, the yardstick of the lean form inside
+                                          one build; the replay key holds the options, so the two forms never share graphs */
+};
+
 typedef struct mn_options {
   float same_different_bias;   /* segment.h:246 */
   float object_merge_factor;   /* segment.h:247 */
@@ -116,29 +140,7 @@ typedef struct mn_options {
                                   10, once in 65 runs at 25, never from 50 up; round 2, rounds from the
                                   cores: 100, 50 and 20 give the same verdict and pixel agreement on
                                   every reference vector, 50 is a fifth faster than 100)            */
-  int debug_flags;             /* bit 0: use the generic edge pass where the fast form would run (tests
-                                  compare the two); bit 1: no per-kernel timestamps in components mode
-                                  (ms_cc_* stay 0; each is an event on the caller's stream); bit 2:
-                                  general rounds from single pixels instead of from the cores; bit 4: only
-                                  the sweep is timed (ms_cc_edges; the other ms_* stay 0) -- an event
-                                  costs the host ~3.5 us to record and ~8 us to read; bit 5 (with
-                                  bit 4): replay -- when mn_segment_launch is called again with the
-                                  same buffers, shape, options and stream, the launches after the
-                                  sweep are recorded into two hipGraphs (second call) and replayed
-                                  (from the third): a loop over images through fixed buffers; bit 7:
-                                  time the sweep with an event packet before and behind it instead
-                                  of start/stop events on its own dispatch (round 2's first form:
-                                  measures dispatch gap + kernel); bit 8: a 16-bit map's sweep takes 4
-                                  pixels per lane (8-byte loads) where it would take 8 (16-byte loads) --
-                                  same results, for the measurement of the two forms; bit 9 (512): the sweep
-                                  of components mode leaves the FULL form of its outputs (two mask words per
-                                  pixel, per-lane class log-products for every lane) where the default path
-                                  takes the lean form (one packed word for up to 16 offsets, one record per
-                                  uniform 64-pixel run) -- same results bit for bit, the yardstick of the lean
-                                  form inside one build; the replay key holds the options, so the two forms
-                                  never share graphs.  (Round 4 removed the opt-in engines that were measured
-                                  slower or known to deviate: bits 3, 10-13; bit 9 was among them and now
-                                  means the above.) */
+  int debug_flags;             /* enum mn_debug_flags, or-ed */
   int require_proof;           /* what happens to a result that is not PROVEN equal to the reference's
                                   sequential order (stats.proof == 0): 1 = it is redone in MN_MODE_EXACT,
                                   whatever mode was asked for, and -- if that run chose among bit-equal

@@ -11,6 +11,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
+#include <type_traits>
 
 #include "../../include/mergenet_hip.h"
 #include "mn_device.h"
@@ -21,6 +22,7 @@
 #include "mn_kernels_prepare.h"
 #include "mn_kernels_instances.h"
 #include "mn_kernels_cc.h"
+#include "mn_sweep_form.h"
 #include "mn_kernels_tail.h"
 #include "mn_kernels_exact.h"
 #include "mn_kernels_reforder.h"
@@ -122,7 +124,7 @@ struct mn_context {
   int *cc_tcount, *cc_lcount;   // pixel edges per record: parallel to the components-mode table / list
   unsigned* cc_bits;            // [N] positive out-edges of every pixel (mn_cc_sign)
   int* cc_roots;                // [N] component roots (mn_cc_finish)
-  int cc_sign_blocks;           // WAVES of the last sign sweep (one partial sum each)
+  SweepForm cc_sweep;           // of the last contraction (its `waves` partial sums: the tail and the certificate add them up)
   unsigned* cc_negbits;         // per pixel: its negative out-edges (bit k = offset k), written by the sweep
   size_t cc_cap_max;
   hipEvent_t ev[12];   // 0-4 phases, 6-11 components-mode kernels
@@ -135,7 +137,7 @@ struct mn_context {
     mn_stats stats;
   } pend;
   hipEvent_t ev_done;
-  // Replay (debug_flags bit 5): a loop that merges image after image through the same buffers issues
+  // Replay (MN_DEBUG_REPLAY): a loop that merges image after image through the same buffers issues
   // the same ~17 launches every time, ~3.5 us of host time each -- more than the kernels on the
   // caller's stream take.  The second identical call captures what follows the sweep into two
   // hipGraphs (labelling on the caller's stream, the tail on the side stream); later calls launch
@@ -148,8 +150,9 @@ struct mn_context {
     hipGraph_t gA, gB;
     hipGraphExec_t eA, eB;
     hipStream_t cap;       // capture happens here (the caller's stream may be the null stream, which cannot capture)
+    hipStream_t behind;    // the stream an open recording stands for
     Queued queued;         // of the attempt that recorded the graphs
-    int lean_form;         // ... and the form of the sweep's outputs its graphs read (sweep_lean_form)
+    SweepForm sweep;       // ... and the form of its sweep, whose outputs the graphs read
   } replay;
   hipStream_t side;       // the single-workgroup tail of an image runs here, beside the next image's sweeps
   hipEvent_t ev_fork;
@@ -667,6 +670,10 @@ static long long count_records(const ImageCall& call) {
 }
 
 static inline unsigned grid_for(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
+// blocks of lanes that take four pixels each
+static inline unsigned quad_grid(int N, unsigned block) { return grid_for((size_t)(N >> 2) > 0 ? (size_t)(N >> 2) : 1, block); }
+static inline unsigned all_offsets(int O) { return O >= 32 ? 0xFFFFFFFFu : ((1u << O) - 1u); }
+template <int V> using Int = std::integral_constant<int, V>;
 
 struct FillList {
   FillJobs j;
@@ -692,6 +699,9 @@ struct FillList {
   }
 };
 
+// the record table at `cap` slots (a power of two)
+static HashTab table_of(const mn_context* c, size_t cap) { HashTab T = c->T; T.mask = (unsigned)(cap - 1); return T; }
+
 static ObjState obj_state(mn_context* c) {
   ObjState S;
   S.ocls = c->ocls; S.osize = c->osize; S.parent = c->parent; S.lpsum = c->lpsum;
@@ -709,7 +719,7 @@ static void launch_edge_pass(mn_context* c, const ImgParams& P, hipStream_t st, 
   const dim3 gx(8 * ((grid_for(P.N, 256) + 7) / 8));
   const unsigned char* cls0 = c->ocls;       // unchanged until mn_pix_apply
   const unsigned char* matched = c->matched;
-  const bool fast = P.omf > 0.0f && P.sdb == 0.0f && !(c->debug_flags & 1);
+  const bool fast = P.omf > 0.0f && P.sdb == 0.0f && !(c->debug_flags & MN_DEBUG_GENERIC_EDGE_PASS);
   if (fast && P.O == 10 && !P.clip)
     hipLaunchKernelGGL((mn_edge_pass_fast<10, FIRST, false>), gx, b, 0, st, P, cls0, matched, out,
                        progress, s);
@@ -748,10 +758,7 @@ static int run_phase_a(mn_context* c, const ImgParams& P, hipStream_t st, bool e
   hipLaunchKernelGGL(mn_init_objects, dim3(grid_for(N, 256)), dim3(256), 0, st, N, c->osize,
                      c->parent, c->mate);
   MN_HIP(hipEventRecord(c->ev[0], st));
-  {
-    const unsigned blocks = grid_for((size_t)(N >> 2) > 0 ? (size_t)(N >> 2) : 1, 256);
-    hipLaunchKernelGGL(mn_class_pass, dim3(blocks), dim3(256), 0, st, P, c->ocls);
-  }
+  hipLaunchKernelGGL(mn_class_pass, dim3(quad_grid(N, 256)), dim3(256), 0, st, P, c->ocls);
   MN_HIP(hipEventRecord(c->ev[1], st));
   if (edge) {
     launch_edge_pass<true>(c, P, st, c->ball, 0);
@@ -773,8 +780,7 @@ static int read_counters(mn_context* c, hipStream_t st) {
 static int build_list(mn_context* c, const ImgParams& P, hipStream_t st, size_t cap, RecList L,
                       const RecList* src, int Rsrc, int* Rout) {
   ObjState S = obj_state(c);
-  HashTab T = c->T;
-  T.mask = (unsigned)(cap - 1);
+  const HashTab T = table_of(c, cap);
   // the next list is appended to by both kernels below; they also fill the best-record slots and
   // the band maximum of the coming round.  ONE launch clears all of it (six memsets cost six
   // dispatch gaps, which is what a late round is made of)
@@ -803,119 +809,88 @@ static int build_list(mn_context* c, const ImgParams& P, hipStream_t st, size_t 
   return MN_OK;
 }
 
-// Plane stride of the sweep's per-lane class log-products (N / 4 ints used per plane, inside the [C][N] float
-// buffer of the class sums): an odd multiple of 256 B, so that the C planes a lane writes one after the other
-// do not all start on the same memory channel (a stride of N ints is a power of two at 1024 x 2048).
-static size_t gsum_stride(int N) {
-#ifdef MN_GSUM_SKEW
-  return ((((size_t)N / 4 + 63) / 64) | 1) * 64;
-#else
-  return (size_t)N;
-#endif
+// The form of the sweep for the call in progress, as `who` asks for it (the rules: mn_sweep_form.h).
+static SweepForm sweep_form_of(const mn_context* c, const ImgParams& P, SweepAsker who) {
+  const bool aligned16 = ((reinterpret_cast<uintptr_t>(P.cls) | reinterpret_cast<uintptr_t>(P.same)) & 15) == 0;
+  return sweep_form(P.N, P.W, P.O, P.di, P.dj, P.dtype, P.logits != 0, P.clip != 0, P.sdb, aligned16, c->debug_flags, who);
 }
 
-// The lean form of what the sweep leaves (LeanOut in mn_kernels_cc.h: packed masks where O <= 16, one record per
-// uniform group of 64 pixels) is what the pure components path and its replay run on.  debug_flags bit 9 keeps the
-// full form there (the yardstick inside one build); so does an image too small for the records to fit into the
-// free part of the `lpsum` planes, or a build with skewed planes.
-static bool sweep_lean_form(const mn_context* c, const ImgParams& P, int px) {
-  return px >= 4 && !(c->debug_flags & 512) && P.N >= 64 && gsum_stride(P.N) == (size_t)P.N;
-}
-static LeanOut lean_out(const ImgParams& P, bool lean_form) {
-  LeanOut LO = {-1, 0, 0, 0};
-  if (!lean_form) return LO;
-  for (int k = 0; k < P.O; k++)
-    if (P.di[k] == 0 && P.dj[k] == 1) { LO.kh = k; break; }
-  LO.packed = P.O <= 16 ? 1 : 0;
-  LO.rec0 = (P.N / 4 + 1) & ~1;                     // (i64 records: an even int index behind the per-lane values)
-  LO.flag0 = LO.rec0 + 2 * ((P.N + 63) / 64);       // (the groups' words of plane 0 behind its records)
-  return LO;
-}
-
-// The sweep (mn_cc_sign) in the form for PX pixels per lane and maps of element type DT (LG: holding logits).
-template <int PX, int DT, bool LG = false>
-static void launch_sign(mn_context* c, const ImgParams& P, hipStream_t st, bool cls, bool lean_cls, bool lean_form) {
-  const int N = P.N, ngroups = (N + PX - 1) / PX;
-  const dim3 g(grid_for(ngroups, MN_CC_SIGN_THREADS)), b(MN_CC_SIGN_THREADS);
+// The sweep (mn_cc_sign) in the form F.  It only dispatches: logits (the sigmoid on load) x element type x pixels
+// per lane x (plain, cls, lean) are compile-time forms of the kernel.
+static void launch_sweep(mn_context* c, const ImgParams& P, hipStream_t st, const SweepForm& F) {
+  const dim3 g(F.blocks), b(MN_CC_SIGN_THREADS);
   ClsOut CO;
-  CO.ocls = lean_cls ? nullptr : c->ocls; CO.cls0 = c->cls0; CO.lpvalid = lean_cls ? nullptr : c->lpvalid;
+  CO.ocls = F.lean_cls ? nullptr : c->ocls; CO.cls0 = c->cls0; CO.lpvalid = F.lean_cls ? nullptr : c->lpvalid;
   CO.gsum = reinterpret_cast<int*>(c->lpsum);     // (the summed class log-probs are written later, at roots only)
-  CO.gstride = gsum_stride(P.N);
-  // (a 16-bit map is always clipped on load; its plain form is the clip alone: mn_cc_value)
-  // (logits likewise: sigmoid + clip)
-  const bool plain = (DT != MN_DTYPE_F32 || LG || !P.clip) && P.sdb == 0.0f;
-  // Timed: the dispatch itself carries the two events (hipExtLaunchKernel: start and stop time of THIS
-  // kernel), instead of an event packet in front of it and one behind -- each of those cost a ~6 us
-  // dispatch gap on the stream, and the pair measured gap + kernel (54 us where rocprofv3 saw 46).
-  lean_form = lean_form && lean_cls && cls && PX >= 4;
-  const LeanOut LO = lean_out(P, lean_form);
-#define MN_LAUNCH_SIGN(PLAINV, CLSV, LEANV)                                                             \
-  do {                                                                                                \
-    if (c->ext_events)                                                                                \
-      hipExtLaunchKernelGGL((mn_cc_sign<PX, PLAINV, (CLSV) && PX >= 4, DT, LG, (LEANV) && PX >= 4>), g, b, 0, st, \
-                            c->ev[0], c->ev[10], 0, P, c->cc_bits, c->cc_negbits, c->scalars + 6, c->partial, CO, LO); \
-    else                                                                                              \
-      hipLaunchKernelGGL((mn_cc_sign<PX, PLAINV, (CLSV) && PX >= 4, DT, LG, (LEANV) && PX >= 4>), g, b, 0, st, P, \
-                         c->cc_bits, c->cc_negbits, c->scalars + 6, c->partial, CO, LO);              \
-  } while (0)
-  if (plain && lean_form) MN_LAUNCH_SIGN(true, true, true);
-  else if (lean_form) MN_LAUNCH_SIGN(false, true, true);
-  else if (plain && cls) MN_LAUNCH_SIGN(true, true, false);
-  else if (plain) MN_LAUNCH_SIGN(true, false, false);
-  else if (cls) MN_LAUNCH_SIGN(false, true, false);
-  else MN_LAUNCH_SIGN(false, false, false);
-#undef MN_LAUNCH_SIGN
-}
-
-// Pixels per lane of the sweep.  4 whenever the planes stay aligned for a lane's one load per plane (N % 4 == 0):
-// with W % 4 != 0 one lane per row runs over the row's end (mn_cc_sign: `straddle`; W >= 4: its four pixels then
-// span at most two rows, which is what mn_cc_sign assumes), else 1.  A 16-bit map takes 8 -- one 16-byte load per
-// plane, as the float32 map's 4 -- where N % 8 == 0, W % 8 == 0 (no lane runs over a row's end) and the planes
-// are 16-byte aligned; debug_flags bit 8 keeps it at 4 (8-byte loads), for the measurement of the two forms.
-static int sweep_px(const mn_context* c, const ImgParams& P) {
-  if (!((P.N & 3) == 0 && P.W >= 4)) return 1;
-  if (P.dtype != MN_DTYPE_F32 && !(c->debug_flags & 256) && (P.N & 7) == 0 && (P.W & 7) == 0 &&
-      ((reinterpret_cast<uintptr_t>(P.cls) | reinterpret_cast<uintptr_t>(P.same)) & 15) == 0)
-    return 8;
-  return 4;
-}
-
-// The sweep in the form sweep_px chose (`cls`: it takes the class planes too; only with px >= 4).
-template <bool LG>
-static void launch_sweep_lg(mn_context* c, const ImgParams& P, hipStream_t st, int px, bool cls, bool lean_cls,
-                            bool lean_form) {
-#define MN_SWEEP_DT(PXV)                                                                                   \
-  do {                                                                                                     \
-    if (P.dtype == MN_DTYPE_F16) launch_sign<PXV, MN_DTYPE_F16, LG>(c, P, st, cls, lean_cls, lean_form);   \
-    else launch_sign<PXV, MN_DTYPE_BF16, LG>(c, P, st, cls, lean_cls, lean_form);                          \
-  } while (0)
-  if (P.dtype == MN_DTYPE_F32) {
-    if (px == 4) launch_sign<4, MN_DTYPE_F32, LG>(c, P, st, cls, lean_cls, lean_form);
-    else launch_sign<1, MN_DTYPE_F32, LG>(c, P, st, false, false, false);
-  } else if (px == 8) MN_SWEEP_DT(8);
-  else if (px == 4) MN_SWEEP_DT(4);
-  else { cls = false; lean_cls = false; lean_form = false; MN_SWEEP_DT(1); }
-#undef MN_SWEEP_DT
-}
-// `lean_form`: only with `lean_cls` (the caller asks sweep_lean_form, or replays what it recorded)
-static void launch_sweep(mn_context* c, const ImgParams& P, hipStream_t st, int px, bool cls, bool lean_cls,
-                         bool lean_form = false) {
-  if (P.logits) launch_sweep_lg<true>(c, P, st, px, cls, lean_cls, lean_form);      // (the sigmoid on load: a compile-time form)
-  else launch_sweep_lg<false>(c, P, st, px, cls, lean_cls, lean_form);
+  CO.gstride = (size_t)P.N;
+  auto launch = [&](auto lg, auto dt, auto px, auto plain, auto cls, auto lean) {
+    constexpr bool LG = decltype(lg)::value, PLAIN = decltype(plain)::value;
+    constexpr int DT = decltype(dt)::value, PX = decltype(px)::value;
+    constexpr bool CLS = decltype(cls)::value && PX >= 4, LEAN = decltype(lean)::value && PX >= 4;   // (one pixel per lane: neither)
+    // Timed: the dispatch itself carries the two events (hipExtLaunchKernel: start and stop time of THIS kernel),
+    // instead of an event packet in front of it and one behind -- each of those cost a ~6 us dispatch gap on the
+    // stream, and the pair measured gap + kernel (54 us where rocprofv3 saw 46).
+    if (c->ext_events)
+      hipExtLaunchKernelGGL((mn_cc_sign<PX, PLAIN, CLS, DT, LG, LEAN>), g, b, 0, st, c->ev[0], c->ev[10], 0, P,
+                            c->cc_bits, c->cc_negbits, c->scalars + 6, c->partial, CO, F.LO);
+    else
+      hipLaunchKernelGGL((mn_cc_sign<PX, PLAIN, CLS, DT, LG, LEAN>), g, b, 0, st, P, c->cc_bits, c->cc_negbits,
+                         c->scalars + 6, c->partial, CO, F.LO);
+  };
+  const std::true_type yes; const std::false_type no;
+  auto by_form = [&](auto lg, auto dt, auto px) {
+    if (F.plain && F.lean_form) launch(lg, dt, px, yes, yes, yes);
+    else if (F.lean_form) launch(lg, dt, px, no, yes, yes);
+    else if (F.plain && F.cls) launch(lg, dt, px, yes, yes, no);
+    else if (F.plain) launch(lg, dt, px, yes, no, no);
+    else if (F.cls) launch(lg, dt, px, no, yes, no);
+    else launch(lg, dt, px, no, no, no);
+  };
+  auto by_16 = [&](auto lg, auto px) {
+    P.dtype == MN_DTYPE_F16 ? by_form(lg, Int<MN_DTYPE_F16>(), px) : by_form(lg, Int<MN_DTYPE_BF16>(), px);
+  };
+  auto by_px = [&](auto lg) {
+    if (P.dtype == MN_DTYPE_F32) F.px == 4 ? by_form(lg, Int<MN_DTYPE_F32>(), Int<4>()) : by_form(lg, Int<MN_DTYPE_F32>(), Int<1>());
+    else if (F.px == 8) by_16(lg, Int<8>());
+    else if (F.px == 4) by_16(lg, Int<4>());
+    else by_16(lg, Int<1>());
+  };
+  P.logits ? by_px(yes) : by_px(no);
 }
 
 // the sweep over the positive masks that hooks the offsets the tile stages did not take
 template <int PX>
-static void launch_cc_hook(mn_context* c, const ImgParams& P, hipStream_t st, unsigned kmask,
-                           const unsigned* hook_bits = nullptr, hipEvent_t hook_done = nullptr) {
-  const int N = P.N, ngroups = (N + PX - 1) / PX;
-  const dim3 gx(8 * ((grid_for(ngroups, 256) + 7) / 8));
+static void launch_cc_hook(mn_context* c, const ImgParams& P, hipStream_t st, unsigned kmask, const unsigned* bits,
+                           hipEvent_t hook_done) {
+  const dim3 gx(8 * ((grid_for((P.N + PX - 1) / PX, 256) + 7) / 8));
   if (hook_done)                 // (its completion is the fork point of the image: no event packet behind it)
-    hipExtLaunchKernelGGL(mn_cc_hook<PX>, gx, dim3(256), 0, st, nullptr, hook_done, 0, P,
-                          hook_bits ? hook_bits : (const unsigned*)c->cc_bits, c->parent, kmask);
+    hipExtLaunchKernelGGL(mn_cc_hook<PX>, gx, dim3(256), 0, st, nullptr, hook_done, 0, P, bits, c->parent, kmask);
   else
-    hipLaunchKernelGGL(mn_cc_hook<PX>, gx, dim3(256), 0, st, P, hook_bits ? hook_bits : (const unsigned*)c->cc_bits,
-                       c->parent, kmask);
+    hipLaunchKernelGGL(mn_cc_hook<PX>, gx, dim3(256), 0, st, P, bits, c->parent, kmask);
+}
+
+// Replay's recording (mn_context::Replay).  Begin: what is launched on `st` from here on goes into a graph, on the
+// capture stream.  End: the graph is instantiated and launched on the stream the recording stood for, and `st` is
+// that stream again.  Abandon: an attempt that did not get as far as the end of graph B leaves no recording open.
+static int replay_begin(mn_context* c, hipStream_t& st) {
+  MN_HIP(hipStreamBeginCapture(c->replay.cap, hipStreamCaptureModeThreadLocal));
+  c->replay.behind = st;
+  st = c->replay.cap;
+  return MN_OK;
+}
+static int replay_end(mn_context* c, hipGraph_t* graph, hipGraphExec_t* exec, hipStream_t& st) {
+  MN_HIP(hipStreamEndCapture(c->replay.cap, graph));
+  MN_HIP(hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0));
+  MN_HIP(hipGraphLaunch(*exec, c->replay.behind));
+  st = c->replay.behind;
+  return MN_OK;
+}
+static void replay_abandon(mn_context::Replay& rp) {
+  hipGraph_t open_graph = nullptr;
+  if (hipStreamEndCapture(rp.cap, &open_graph) == hipSuccess && open_graph) (void)hipGraphDestroy(open_graph);
+  (void)hipGetLastError();
+  rp.capturing = 0;
+  rp.state = 0;
 }
 
 enum CcUse {          // the four uses of the component contraction
@@ -925,194 +900,201 @@ enum CcUse {          // the four uses of the component contraction
   CC_CORES            // first step of the general rounds, on the edges between clean pixels
 };
 
-// Component contraction (mn_kernels_cc.h).  CC_WAITED: returns 0 when the input is
-// sign-separable (object state + list of records between components ready, count in h_cnt), 1
-// when it is not (caller falls back), < 0 on error.  The others: everything is queued, 0 is returned
-// and the verdict is read by the caller at the end.
-static int run_components(mn_context* c, const ImgParams& P, hipStream_t& st, CcUse use) {
-  const bool wait = use == CC_WAITED, with_ball = use == CC_WAITED;
-  const bool with_compact = use == CC_WAITED || use == CC_QUEUED_COMPACT;
-  const bool fork_before_sums = use == CC_QUEUED_TAIL, cores = use == CC_CORES;
-  const int N = P.N;
-  ObjState S = obj_state(c);
-  const dim3 b(256);
-  const bool four = P.W % 4 == 0;
-  // the unit offsets (0, +1) and (+-1, 0), if the list has them (generate_offsets always does), go
-  // to the tile and border stages; the sweep over the mask takes the rest
-  int kh = -1, kv = -1, dv = 0;
-  for (int k = 0; k < P.O; k++) {
-    if (kh < 0 && P.di[k] == 0 && P.dj[k] == 1) kh = k;
-    if (kv < 0 && P.dj[k] == 0 && (P.di[k] == 1 || P.di[k] == -1)) { kv = k; dv = P.di[k]; }
+struct CcPlan {            // everything a contraction decides before its first launch
+  bool wait, with_ball;    // CC_WAITED: the verdict is waited for; the compaction fills the best-record slots
+  bool with_compact;       // the table is compacted into the list here (mn_cc_tail takes the table itself)
+  bool fork_before_sums, cores;   // CC_QUEUED_TAIL / CC_CORES
+  SweepForm sweep;
+  UnitOffsets unit;        // go to the tile and border stages; the sweep over the mask (the hook) takes the rest
+  unsigned kshort, kmask;  // cores: the short offsets (core_radius) / the offsets left to the hook
+  unsigned* core_bits;     // cores: the edges between clean pixels (mn_core_bits; `label` is free until the finisher)
+  const unsigned* lbits;   // the masks the labelling reads: core_bits, or the sweep's
+  int *clsmin, *clsmax;    // class range of the components: `root` and `mapbuf` are free until the output stage
+  HashTab T;               // (table, violation counters and any best-record slots were cleared by the caller's fill)
+  dim3 tiles;
+  // Events.  MN_DEBUG_NO_EVENTS: no per-kernel timestamps on the caller's stream.  MN_DEBUG_LEAN_EVENTS: only the
+  // sweep is timed (ev[0], ev[10]).  An event costs the host ~3.5 us to record and ~8 us to read: a dozen per image
+  // made the HOST the bottleneck of a loop over images (0.18 ms per step against 0.12 ms of kernels on the stream).
+  bool sweep_packet, timed;   // ev[10] is a packet behind the sweep (ext_events: its dispatch carries it) / later stages record theirs
+  bool fork_by_hook;       // the last kernel on the caller's stream carries the fork event (hipExtLaunchKernel stop event)
+};
+
+static CcPlan make_cc_plan(mn_context* c, const ImgParams& P, CcUse use) {
+  CcPlan pl;
+  pl.wait = pl.with_ball = use == CC_WAITED;
+  pl.with_compact = use == CC_WAITED || use == CC_QUEUED_COMPACT;
+  pl.fork_before_sums = use == CC_QUEUED_TAIL; pl.cores = use == CC_CORES;
+  pl.sweep = sweep_form_of(c, P, pl.cores ? SWEEP_CORES : SWEEP_COMPONENTS);
+  pl.unit = unit_offsets(P.di, P.dj, P.O);
+  pl.kmask = all_offsets(P.O);
+  if (pl.unit.kh >= 0) pl.kmask &= ~(1u << pl.unit.kh);
+  if (pl.unit.kv >= 0) pl.kmask &= ~(1u << pl.unit.kv);
+  pl.kshort = 0u;          // short offsets: both components within core_radius pixels (default 6; < 0: every offset is short)
+  for (int k = 0; pl.cores && k < P.O; k++)
+    if (c->core_radius < 0 || (abs(P.di[k]) <= c->core_radius && abs(P.dj[k]) <= c->core_radius)) pl.kshort |= 1u << k;
+  pl.core_bits = pl.cores ? reinterpret_cast<unsigned*>(c->label) : nullptr;
+  pl.lbits = pl.cores ? pl.core_bits : c->cc_bits;
+  pl.clsmin = c->root; pl.clsmax = c->mapbuf;
+  pl.T = table_of(c, c->cc_cap);
+  pl.tiles = dim3((P.W + 63) / 64, (P.H + MN_CC_TILE_ROWS - 1) / MN_CC_TILE_ROWS);
+  const bool few_events = (c->debug_flags & MN_DEBUG_NO_EVENTS) != 0;
+  pl.sweep_packet = !few_events && !c->ext_events;
+  pl.timed = !few_events && !(c->debug_flags & MN_DEBUG_LEAN_EVENTS);
+  pl.fork_by_hook = pl.fork_before_sums && c->ext_events && !c->replay.capturing && pl.kmask;
+  return pl;
+}
+
+static int cc_event(mn_context* c, bool on, int ev, hipStream_t st) { if (on) MN_HIP(hipEventRecord(c->ev[ev], st)); return MN_OK; }
+
+// (ev[0], recorded by run_phase_a right before, is its start: every event on the caller's stream costs a ~6 us dispatch gap)
+static int cc_sweep(mn_context* c, const ImgParams& P, const CcPlan& pl, hipStream_t st) {
+  c->cc_sweep = pl.sweep;
+  if (c->replay.capturing) c->replay.sweep = pl.sweep;
+  launch_sweep(c, P, st, pl.sweep);
+  return cc_event(c, pl.sweep_packet, 10, st);
+}
+
+// Cores (first step of the general rounds): the labelling runs on the edges between clean pixels.
+static void cc_core_masks(mn_context* c, const ImgParams& P, const CcPlan& pl, hipStream_t st) {
+  const dim3 g(grid_for(P.N, 256)), b(256);
+  if (!pl.sweep.cls)               // (one pixel per lane: the sweep did not take the class planes)
+    hipLaunchKernelGGL(mn_class_pass, dim3(quad_grid(P.N, 256)), b, 0, st, P, c->cls0);
+  hipLaunchKernelGGL(mn_core_clean, g, b, 0, st, P, (const unsigned*)c->cc_bits, (const unsigned char*)c->cls0,
+                     c->pruned, pl.kshort);
+  hipLaunchKernelGGL(mn_core_bits, g, b, 0, st, P, (const unsigned char*)c->pruned, (const unsigned*)c->cc_bits,
+                     (const unsigned char*)c->cls0, pl.core_bits);
+}
+
+// Labelling: tiles, borders, flatten, hook.  (Labelling the tiles inside the sign sweep -- a block = a 16 x 64 tile --
+// was tried: 40.6 us for the fused kernel against 27 + 15 apart; the LDS union-find and its barriers sit on every
+// block's critical path and the tile layout reads 256-byte row segments.)
+static void cc_label(mn_context* c, const ImgParams& P, const CcPlan& pl, hipStream_t st) {
+  const int kh = pl.unit.kh, kv = pl.unit.kv, dv = pl.unit.dv;
+  hipLaunchKernelGGL(mn_cc_tiles, pl.tiles, dim3(MN_CC_TILE_ROWS * 64), 0, st, P, pl.lbits, c->parent, kh, kv, dv,
+                     c->osize, c->lp_acc, pl.clsmin, pl.clsmax, c->matched);   // `matched` is free in this mode
+  if (kh >= 0 || kv >= 0)
+    hipLaunchKernelGGL(mn_cc_borders, pl.tiles, dim3(128), 0, st, P, pl.lbits, c->parent, kh, kv, dv);
+  hipLaunchKernelGGL(mn_cc_flatten, dim3(quad_grid(P.N, 256)), dim3(256), 0, st, P.N, c->parent);
+  if (pl.kmask) {
+    const hipEvent_t hook_done = pl.fork_by_hook ? c->ev_fork : nullptr;
+    if (P.W % 4 == 0) launch_cc_hook<4>(c, P, st, pl.kmask, pl.lbits, hook_done);
+    else launch_cc_hook<1>(c, P, st, pl.kmask, pl.lbits, hook_done);
   }
-  const bool few_events = (c->debug_flags & 2) != 0;   // no per-kernel timestamps on the caller's stream
-  // bit 4: only the sweep is timed (ev[0], ev[10]).  An event costs the host ~3.5 us to record and ~8 us
-  // to read (hipEventElapsedTime): a dozen of them per image made the HOST the bottleneck of a loop
-  // over images (0.18 ms per step against 0.12 ms of kernels on the caller's stream).
-  const bool lean = (c->debug_flags & 16) != 0;
-  const dim3 tiles((P.W + 63) / 64, (P.H + MN_CC_TILE_ROWS - 1) / MN_CC_TILE_ROWS);
-  // the sweep takes 4 pixels per lane whenever the planes stay 16-byte aligned (N % 4 == 0): with
-  // W % 4 != 0 one lane per row runs over the row's end (mn_cc_sign: `straddle`)
-  // (W >= 4: a straddling lane's four pixels then span at most two rows, which is what mn_cc_sign assumes)
-  // (a 16-bit map: 8 where it can, sweep_px; what the sweep leaves is laid out per 4 pixels either way)
-  const int px = sweep_px(c, P);
-  const bool sweep4 = px >= 4;
-  const size_t sign_blocks = grid_for((size_t)(N / px), MN_CC_SIGN_THREADS);
-  c->cc_sign_blocks = (int)(sign_blocks * (MN_CC_SIGN_THREADS / 64));       // (waves: one partial sum each)
-  // class range of the components: `root` and `mapbuf` are free until the output stage
-  int* clsmin = c->root;
-  int* clsmax = c->mapbuf;
-  // (ev[0], recorded by run_phase_a right before, is the start of the sweep: every event on the
-  // caller's stream costs a ~6 us dispatch gap)
-  // the sweep takes the class planes too when a lane's four pixels are four pixels of the image
-  const bool fused_cls = sweep4;
-  // (pure components mode: the roots' class and validity flag are set by mn_cc_finish)
-  const bool lean_cls = fused_cls && !cores;
-  // (... and there mn_cc_sums and mn_cc_cross are the only readers of what the sweep writes: its lean form)
-  const bool lean_form = lean_cls && sweep_lean_form(c, P, px);
-  const LeanOut LO = lean_out(P, lean_form);
-  if (c->replay.capturing) c->replay.lean_form = lean_form ? 1 : 0;
-  launch_sweep(c, P, st, px, fused_cls, lean_cls, lean_form);
-  if (!few_events && !c->ext_events) MN_HIP(hipEventRecord(c->ev[10], st));
-  // cores (first step of the general rounds): the labelling runs on the edges between clean pixels
-  const unsigned* lbits = c->cc_bits;
-  unsigned kshort = 0u;
-  if (cores) {
-    if (!fused_cls) {                // (the class sweep of this form comes after the labelling)
-      const unsigned blocks = grid_for((size_t)(N >> 2) > 0 ? (size_t)(N >> 2) : 1, 256);
-      hipLaunchKernelGGL(mn_class_pass, dim3(blocks), dim3(256), 0, st, P, c->cls0);
-    }
-    unsigned* bits2 = reinterpret_cast<unsigned*>(c->label);      // free until the finisher
-    // short offsets: both components within core_radius pixels (default 6; < 0: every offset is short)
-    for (int k = 0; k < P.O; k++)
-      if (c->core_radius < 0 || (abs(P.di[k]) <= c->core_radius && abs(P.dj[k]) <= c->core_radius)) kshort |= 1u << k;
-    hipLaunchKernelGGL(mn_core_clean, dim3(grid_for(N, 256)), b, 0, st, P, (const unsigned*)c->cc_bits,
-                       (const unsigned char*)c->cls0, c->pruned, kshort);
-    hipLaunchKernelGGL(mn_core_bits, dim3(grid_for(N, 256)), b, 0, st, P, (const unsigned char*)c->pruned,
-                       (const unsigned*)c->cc_bits, (const unsigned char*)c->cls0, bits2);
-    lbits = bits2;
+}
+
+// From here on the image is latency-bound work of a few workgroups (and one pixel-wide mask write): it moves to the
+// context's side stream, so that the sweeps of the NEXT image (another context, the caller's stream) run beside it
+// instead of behind it.  mn_segment_finish waits for the side stream; nothing of this image is left on the caller's.
+static int cc_fork(mn_context* c, const CcPlan& pl, hipStream_t& st) {
+  if (!pl.fork_by_hook) MN_HIP(hipEventRecord(c->ev_fork, st));
+  MN_HIP(hipStreamWaitEvent(c->side, c->ev_fork, 0));
+  st = c->side;
+  if (c->replay.capturing) return replay_begin(c, st);     // everything from here to the end of the image goes into graph B
+  return MN_OK;
+}
+
+// Class sums of the components, between ev[11] and ev[8]: from the sweep's lean form, from its per-lane products,
+// or (one pixel per lane) from the class planes themselves.
+static int cc_sums(mn_context* c, const ImgParams& P, const CcPlan& pl, hipStream_t st) {
+  const ObjState S = obj_state(c);
+  const int* gsum = reinterpret_cast<const int*>(c->lpsum);
+  if (cc_event(c, pl.timed, 11, st) != MN_OK) return MN_ERR_NO_DEVICE;
+  const size_t lds = (size_t)MN_CC_SUM_SLOTS * (P.C + 1) * sizeof(u64);
+  if (lds > c->cc_sum_lds) {
+    for (const void* k : {reinterpret_cast<const void*>(mn_cc_class_sums), reinterpret_cast<const void*>(mn_cc_sums),
+                          reinterpret_cast<const void*>(mn_cc_sums_lean)})
+      MN_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    c->cc_sum_lds = lds;
   }
-  // (labelling the tiles inside the sign sweep -- a block = a 16 x 64 tile -- was tried: 40.6 us for
-  // the fused kernel against 27 + 15 apart; the LDS union-find and its barriers sit on every block's
-  // critical path and the tile layout reads 256-byte row segments)
-  hipStream_t real = st;
-  if (c->replay.capturing) {       // the labelling stages go into graph A (recorded on the capture stream)
-    MN_HIP(hipStreamBeginCapture(c->replay.cap, hipStreamCaptureModeThreadLocal));
-    st = c->replay.cap;
-  }
-  unsigned kmask = P.O >= 32 ? 0xFFFFFFFFu : ((1u << P.O) - 1u);
-  const bool fork_ext = fork_before_sums && c->ext_events && !c->replay.capturing;
-  bool fork_by_hook = false;
-  hipLaunchKernelGGL(mn_cc_tiles, tiles, dim3(MN_CC_TILE_ROWS * 64), 0, st, P, lbits, c->parent, kh, kv, dv,
-                     c->osize, c->lp_acc, clsmin, clsmax, c->matched);   // `matched` is free in this mode
-  if (kh >= 0 || kv >= 0) {
-    hipLaunchKernelGGL(mn_cc_borders, tiles, dim3(128), 0, st, P, lbits, c->parent, kh, kv, dv);
-    if (kh >= 0) kmask &= ~(1u << kh);
-    if (kv >= 0) kmask &= ~(1u << kv);
-  }
-  hipLaunchKernelGGL(mn_cc_flatten, dim3(grid_for((size_t)(N >> 2) > 0 ? (size_t)(N >> 2) : 1, 256)), b, 0, st, N, c->parent);
-  // the last kernel on the caller's stream can carry the fork event itself (hipExtLaunchKernel stop event)
-  fork_by_hook = fork_ext && kmask;
-  if (kmask) {
-    if (four) launch_cc_hook<4>(c, P, st, kmask, lbits, fork_by_hook ? c->ev_fork : nullptr);
-    else launch_cc_hook<1>(c, P, st, kmask, lbits, fork_by_hook ? c->ev_fork : nullptr);
-  }
-  if (c->replay.capturing) {
-    MN_HIP(hipStreamEndCapture(c->replay.cap, &c->replay.gA));
-    MN_HIP(hipGraphInstantiate(&c->replay.eA, c->replay.gA, nullptr, nullptr, 0));
-    MN_HIP(hipGraphLaunch(c->replay.eA, real));
-    st = real;
-  }
-  // the violation counters, the table and (if asked for) the best-record slots were cleared by the
-  // caller's fill
-  HashTab T = c->T;
-  T.mask = (unsigned)(c->cc_cap - 1);
-  // end of the labelling stages, on the stream they ran on (the side stream starts when it gets the chip)
-  if (!few_events && !lean) MN_HIP(hipEventRecord(c->ev[7], st));
-  if (fork_before_sums) {
-    // From here on the image is latency-bound work of a few workgroups (and one pixel-wide mask
-    // write): it moves to the context's side stream, so that the sweeps of the NEXT image (another
-    // context, the caller's stream) run beside it instead of behind it.  mn_segment_finish waits
-    // for the side stream; nothing of this image is left on the caller's stream after this point.
-    if (!fork_by_hook) MN_HIP(hipEventRecord(c->ev_fork, st));
-    MN_HIP(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-    st = c->side;
-    if (c->replay.capturing) {     // everything from here to the end of the image goes into graph B
-      MN_HIP(hipStreamBeginCapture(c->replay.cap, hipStreamCaptureModeThreadLocal));
-      st = c->replay.cap;
-    }
-  }
-  if (!few_events && !lean) MN_HIP(hipEventRecord(c->ev[11], st));
-  {
-    const size_t lds = (size_t)MN_CC_SUM_SLOTS * (P.C + 1) * sizeof(u64);
-    if (lds > c->cc_sum_lds) {
-      MN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mn_cc_class_sums),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      MN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mn_cc_sums),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      MN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mn_cc_sums_lean),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      c->cc_sum_lds = lds;
-    }
-    const unsigned blocks = grid_for((size_t)(N >> 2) > 0 ? (size_t)(N >> 2) : 1, MN_CC_SUM_THREADS);
-    if (lean_form)
-      hipLaunchKernelGGL(mn_cc_sums_lean, dim3((unsigned)grid_for((size_t)(N + 63) / 64, MN_CC_LEAN_GROUPS)),
-                         dim3(MN_CC_LEAN_THREADS), lds, st, P, S, (const unsigned char*)c->cls0,
-                         (const int*)reinterpret_cast<int*>(c->lpsum), gsum_stride(P.N), LO, c->lp_acc, clsmin, clsmax);
-    else if (fused_cls)
-      hipLaunchKernelGGL(mn_cc_sums, dim3((blocks + MN_CC_SUMS_ITERS - 1) / MN_CC_SUMS_ITERS), dim3(MN_CC_SUM_THREADS), lds, st, P, S,
-                         (const unsigned char*)c->cls0, (const int*)reinterpret_cast<int*>(c->lpsum), gsum_stride(P.N),
-                         c->lp_acc, clsmin, clsmax, cores ? (const unsigned char*)c->pruned : (const unsigned char*)nullptr);
-    else
-      hipLaunchKernelGGL(mn_cc_class_sums, dim3(blocks), dim3(MN_CC_SUM_THREADS), lds, st, P, S, c->cls0,
-                         c->lp_acc, clsmin, clsmax);
-  }
-  if (!few_events && !lean) MN_HIP(hipEventRecord(c->ev[8], st));
-  if (!cores)                      // (the rounds build their records from the pixel graph: positive ones too)
-  {
-    // (lean form with packed masks: the negative ones are the upper half of the word the labelling read; the ends
-    //  are chased only in a build whose mn_cc_sums_lean does not leave parent[] flat, MN_CC_LEAN_FLAT = 0)
-    const bool packed = lean_form && LO.packed;
+  const unsigned blocks = quad_grid(P.N, MN_CC_SUM_THREADS);
+  if (pl.sweep.lean_form)
+    hipLaunchKernelGGL(mn_cc_sums_lean, dim3(grid_for((size_t)(P.N + 63) / 64, MN_CC_LEAN_GROUPS)),
+                       dim3(MN_CC_LEAN_THREADS), lds, st, P, S, (const unsigned char*)c->cls0, gsum, (size_t)P.N,
+                       pl.sweep.LO, c->lp_acc, pl.clsmin, pl.clsmax);
+  else if (pl.sweep.cls)
+    hipLaunchKernelGGL(mn_cc_sums, dim3((blocks + MN_CC_SUMS_ITERS - 1) / MN_CC_SUMS_ITERS), dim3(MN_CC_SUM_THREADS), lds, st, P, S,
+                       (const unsigned char*)c->cls0, gsum, (size_t)P.N, c->lp_acc, pl.clsmin, pl.clsmax,
+                       pl.cores ? (const unsigned char*)c->pruned : (const unsigned char*)nullptr);
+  else
+    hipLaunchKernelGGL(mn_cc_class_sums, dim3(blocks), dim3(MN_CC_SUM_THREADS), lds, st, P, S, c->cls0,
+                       c->lp_acc, pl.clsmin, pl.clsmax);
+  return cc_event(c, pl.timed, 8, st);
+}
+
+// Records between components, then ev[9].  (Not for the cores: the rounds build theirs from the pixel graph, positive ones too.)
+static int cc_cross(mn_context* c, const ImgParams& P, const CcPlan& pl, hipStream_t st) {
+  if (!pl.cores) {
+    // (lean form with packed masks: the negative ones are the upper half of the word the labelling read)
+    const bool packed = pl.sweep.LO.packed != 0;
     const unsigned* negsrc = packed ? (const unsigned*)c->cc_bits : (const unsigned*)c->cc_negbits;
-    if (sweep4)
-      hipLaunchKernelGGL(mn_cc_cross<4>, dim3((unsigned)grid_for((size_t)N / 4, MN_CC_CROSS_THREADS)), dim3(MN_CC_CROSS_THREADS),
-                         0, st, P, (const int*)c->parent, T, negsrc, packed ? 16 : 0, lean_form && !MN_CC_LEAN_FLAT ? 1 : 0, c->scalars + 6, c->cc_tcount);
+    const dim3 b(MN_CC_CROSS_THREADS);
+    if (pl.sweep.px >= 4)
+      hipLaunchKernelGGL(mn_cc_cross<4>, dim3(grid_for((size_t)P.N / 4, MN_CC_CROSS_THREADS)), b, 0, st, P,
+                         (const int*)c->parent, pl.T, negsrc, packed ? 16 : 0, 0, c->scalars + 6, c->cc_tcount);
     else
-      hipLaunchKernelGGL(mn_cc_cross<1>, dim3((unsigned)grid_for((size_t)N, MN_CC_CROSS_THREADS)), dim3(MN_CC_CROSS_THREADS),
-                         0, st, P, (const int*)c->parent, T, negsrc, 0, 0, c->scalars + 6, c->cc_tcount);
+      hipLaunchKernelGGL(mn_cc_cross<1>, dim3(grid_for((size_t)P.N, MN_CC_CROSS_THREADS)), b, 0, st, P,
+                         (const int*)c->parent, pl.T, negsrc, 0, 0, c->scalars + 6, c->cc_tcount);
   }
-  if (!few_events && !lean) MN_HIP(hipEventRecord(c->ev[9], st));
-  // Nothing waits for the verdict here: the object state and the record list are built right
-  // away and the violation count travels to the host together with the record count.  If the
-  // input turns out not to be separable, all of it is discarded (run_phase_a starts over).
-  hipLaunchKernelGGL(mn_cc_finish, dim3(grid_for((size_t)(N >> 4) > 0 ? (size_t)(N >> 4) : 1, 256)), b, 0, st, P, S,
+  return cc_event(c, pl.timed, 9, st);
+}
+
+// Nothing waits for the verdict here: the object state and the record list are built right away and the violation
+// count travels to the host with the record count.  A map that is not separable discards it all (run_phase_a again).
+static int cc_finish(mn_context* c, const ImgParams& P, const CcPlan& pl, hipStream_t st) {
+  const ObjState S = obj_state(c);
+  const dim3 g(grid_for(P.N, 256)), b(256);
+  // (`mate` is free in this mode: it keeps the component sizes; lean_cls: the roots' class and validity flag are set here)
+  hipLaunchKernelGGL(mn_cc_finish, dim3(grid_for((size_t)(P.N >> 4) > 0 ? (size_t)(P.N >> 4) : 1, 256)), b, 0, st, P, S,
                      (const unsigned char*)c->matched, (const i64*)c->lp_acc,
-                     (const int*)clsmin, (const int*)clsmax, c->mate, cores ? (int*)nullptr : c->cc_roots,
-                     c->scalars + 8, c->scalars + 6, lean_cls ? (const unsigned char*)c->cls0 : (const unsigned char*)nullptr);  // `mate` is free in this mode: it keeps the component sizes
-  if (cores) {
-    const unsigned all = P.O >= 32 ? 0xFFFFFFFFu : ((1u << P.O) - 1u);
-    if (kshort != all) {           // a core with a non-positive edge inside falls apart again
-      MN_HIP(hipMemsetAsync(c->matched, 0, (size_t)N, st));      // (the root candidates are done with)
-      hipLaunchKernelGGL(mn_core_check, dim3(grid_for(N, 256)), b, 0, st, P, (const int*)c->parent, lbits, c->matched);
-      hipLaunchKernelGGL(mn_core_dissolve, dim3(grid_for(N, 256)), b, 0, st, P, S,
-                         (const unsigned char*)c->matched, c->scalars + 9);
+                     (const int*)pl.clsmin, (const int*)pl.clsmax, c->mate, pl.cores ? (int*)nullptr : c->cc_roots,
+                     c->scalars + 8, c->scalars + 6, pl.sweep.lean_cls ? (const unsigned char*)c->cls0 : (const unsigned char*)nullptr);
+  if (pl.cores) {
+    if (pl.kshort != all_offsets(P.O)) {           // a core with a non-positive edge inside falls apart again
+      MN_HIP(hipMemsetAsync(c->matched, 0, (size_t)P.N, st));    // (the root candidates are done with)
+      hipLaunchKernelGGL(mn_core_check, g, b, 0, st, P, (const int*)c->parent, pl.lbits, c->matched);
+      hipLaunchKernelGGL(mn_core_dissolve, g, b, 0, st, P, S, (const unsigned char*)c->matched, c->scalars + 9);
     }
     // what mn_build_from_pixels will insert: sizes its table (c->touch was cleared by the caller's fill)
-    hipLaunchKernelGGL(mn_count_cross_edges, dim3(grid_for(N, 256)), b, 0, st, P, (const int*)c->parent, c->touch);
+    hipLaunchKernelGGL(mn_count_cross_edges, g, b, 0, st, P, (const int*)c->parent, c->touch);
   }
-  if (with_compact)                // (mn_cc_tail takes the table itself)
+  if (pl.with_compact)             // (mn_cc_tail takes the table itself)
     hipLaunchKernelGGL(mn_compact<4>, dim3(grid_for(c->cc_cap, MN_COMPACT_SLOTS)), dim3(256), 0, st, P, S,
-                       T, c->LA, with_ball ? c->ball : (u64*)nullptr, c->gmax, c->cnt,
+                       pl.T, c->LA, pl.with_ball ? c->ball : (u64*)nullptr, c->gmax, c->cnt,
                        (const int*)c->cc_tcount, c->cc_lcount);
   MN_HIP(hipGetLastError());
-  if (!wait) return 0;             // speculative: the caller finds out at its final synchronisation
+  return MN_OK;
+}
+
+// 0 when the input is sign-separable, 1 when it is not, or the table filled up (the caller falls back)
+static int cc_verdict(mn_context* c, hipStream_t st) {
   MN_HIP(hipMemcpyAsync(c->h_scalars, c->scalars, MN_NSCALARS * sizeof(int), hipMemcpyDeviceToHost, st));
   MN_HIP(hipMemcpyAsync(c->h_cnt, c->cnt, sizeof(Counters), hipMemcpyDeviceToHost, st));
   MN_HIP(hipStreamSynchronize(st));
-  if (c->h_scalars[6] != 0 || c->h_scalars[7] != 0) {     // not separable, or the table filled up
-    MN_HIP(hipMemsetAsync(c->cnt, 0, sizeof(Counters), st));
-    return 1;
-  }
-  return 0;
+  if (c->h_scalars[6] == 0 && c->h_scalars[7] == 0) return 0;
+  MN_HIP(hipMemsetAsync(c->cnt, 0, sizeof(Counters), st));
+  return 1;
+}
+
+// Component contraction (mn_kernels_cc.h).  CC_WAITED: returns 0 when the input is sign-separable (object state +
+// list of records between components ready, count in h_cnt), 1 when it is not (caller falls back), < 0 on error.
+// The others: everything is queued, 0 is returned and the verdict is read by the caller at the end.  `st` ends on
+// the side stream where the image forked, and on replay's capture stream while graph B is being recorded.
+static int run_components(mn_context* c, const ImgParams& P, hipStream_t& st, CcUse use) {
+  const CcPlan pl = make_cc_plan(c, P, use);
+  mn_context::Replay& rp = c->replay;
+  int rc;
+  if ((rc = cc_sweep(c, P, pl, st)) != MN_OK) return rc;
+  if (pl.cores) cc_core_masks(c, P, pl, st);
+  if (rp.capturing && (rc = replay_begin(c, st)) != MN_OK) return rc;       // the labelling stages go into graph A
+  cc_label(c, P, pl, st);
+  if (rp.capturing && (rc = replay_end(c, &rp.gA, &rp.eA, st)) != MN_OK) return rc;
+  // end of the labelling stages, on the stream they ran on (the side stream starts when it gets the chip)
+  if ((rc = cc_event(c, pl.timed, 7, st)) != MN_OK) return rc;
+  if (pl.fork_before_sums && (rc = cc_fork(c, pl, st)) != MN_OK) return rc;
+  if ((rc = cc_sums(c, P, pl, st)) != MN_OK) return rc;
+  if ((rc = cc_cross(c, P, pl, st)) != MN_OK) return rc;
+  if ((rc = cc_finish(c, P, pl, st)) != MN_OK) return rc;
+  return pl.wait ? cc_verdict(c, st) : 0;             // speculative: the caller finds out at its final synchronisation
 }
 
 // ---- exact engine: set-up kernels, the loop, hand-over to the output stage ------------------------
@@ -1613,7 +1595,7 @@ static int segment_read_back(mn_context* c, const mn_options* opts, const Queued
     stats->total_logprob = q.want_cert ? c->h_lp[0] : NAN;
     float ms = 0;
     const bool cmode = mode == MN_MODE_COMPONENTS || c->cores_used;   // (no separate scoring phase: ev[1], ev[2] not recorded)
-    if (c->cores_used && !(opts->debug_flags & 2)) {
+    if (c->cores_used && !(opts->debug_flags & MN_DEBUG_NO_EVENTS)) {
       (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[10]); stats->ms_edge_pass = ms;    // the sweep: class + sameness planes
     }
     if (!cmode) {
@@ -1621,16 +1603,16 @@ static int segment_read_back(mn_context* c, const mn_options* opts, const Queued
       (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]); stats->ms_edge_pass = ms;
     }
     stats->ms_score = stats->ms_class_pass + stats->ms_edge_pass;
-    const bool lean = (opts->debug_flags & 16) != 0 && q.speculate && mode == MN_MODE_COMPONENTS &&
+    const bool lean = (opts->debug_flags & MN_DEBUG_LEAN_EVENTS) != 0 && q.speculate && mode == MN_MODE_COMPONENTS &&
                       opts->variant == MN_VARIANT_CSEGMENT;      // (only ev[0], ev[10] were recorded)
     if (!lean) {
       (void)hipEventElapsedTime(&ms, c->ev[cmode ? 0 : 2], c->ev[3]); stats->ms_merge = ms;
       (void)hipEventElapsedTime(&ms, c->ev[3], c->ev[4]); stats->ms_output = ms;
       (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[4]); stats->ms_total = ms;
     }
-    if (mode == MN_MODE_COMPONENTS && !(opts->debug_flags & 2)) {
+    if (mode == MN_MODE_COMPONENTS && !(opts->debug_flags & MN_DEBUG_NO_EVENTS)) {
       (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[10]); stats->ms_cc_edges = ms;
-      if (!(opts->debug_flags & 16)) {
+      if (!(opts->debug_flags & MN_DEBUG_LEAN_EVENTS)) {
         (void)hipEventElapsedTime(&ms, c->ev[10], c->ev[7]); stats->ms_cc_label = ms;
         (void)hipEventElapsedTime(&ms, c->ev[11], c->ev[8]); stats->ms_cc_sums = ms;
         (void)hipEventElapsedTime(&ms, c->ev[8], c->ev[9]); stats->ms_cc_cross = ms;
@@ -1674,12 +1656,12 @@ static Plan make_plan(const ImageCall& call, int force_mode, bool speculate) {
   if (pl.mode == MN_MODE_COMPONENTS && !contractible) pl.mode = MN_MODE_ROUNDS;
   pl.xengine = pl.mode == MN_MODE_EXACT;
   // the same conditions let the general rounds start from the cores (mn_core_clean) instead of from
-  // single pixels; debug_flags bit 2 keeps the round on the implicit pixel graph
-  pl.cores_ok = contractible && !(opts->debug_flags & 4);
+  // single pixels; MN_DEBUG_NO_CORES keeps the round on the implicit pixel graph
+  pl.cores_ok = contractible && !(opts->debug_flags & MN_DEBUG_NO_CORES);
   pl.speculate = speculate && pl.mode == MN_MODE_COMPONENTS && pl.finish_limit <= MN_FIN2_MAXR;
   pl.fused_tail = pl.speculate && opts->variant == MN_VARIANT_CSEGMENT;
   pl.want_cert = opts->compute_logprob != 0;
-  pl.lean = (opts->debug_flags & 16) != 0 && pl.fused_tail;
+  pl.lean = (opts->debug_flags & MN_DEBUG_LEAN_EVENTS) != 0 && pl.fused_tail;
   return pl;
 }
 
@@ -1879,9 +1861,8 @@ static int launch_finisher(mn_context* c, const ImgParams& P, const Plan& pl, co
                                  hipFuncAttributeMaxDynamicSharedMemorySize, MN_FIN2_MAXR * 12));
       c->tail_lds_ready = 1;
     }
-    HashTab T = c->T;
-    T.mask = (unsigned)(c->cc_cap - 1);
-    const int nbe = c->cc_sign_blocks;
+    const HashTab T = table_of(c, c->cc_cap);
+    const int nbe = c->cc_sweep.waves;
     hipLaunchKernelGGL(mn_cc_tail, dim3(1), dim3(MN_FIN2_THREADS), MN_FIN2_MAXR * 12, A.st, P, S, T, (const int*)c->cc_tcount,
                        A.cur, c->cc_lcount, c->label, c->fin_lists, c->cnt, max_steps, c->scalars, pl.finish_limit,
                        (const unsigned char*)c->cls0, (const int*)c->mate, (const int*)c->cc_roots, nbe,
@@ -1957,7 +1938,7 @@ static int launch_certificate(mn_context* c, const ImgParams& P, const Plan& pl,
   } else if (A.cc_certificate()) {
     // no further sweep over the sameness planes: the edge sweep of the contraction left the sums
     // for the components and the finisher what the merged records moved (mn_cc_certificate)
-    const int nbe = c->cc_sign_blocks;
+    const int nbe = c->cc_sweep.waves;
     hipLaunchKernelGGL(mn_cc_certificate, dim3(1), dim3(MN_CC_CERT_THREADS), 0, A.st, P, S, (const unsigned char*)c->cls0,
                        (const int*)c->mate, (const int*)c->cc_roots, (const int*)(c->scalars + 8), nbe,
                        (const double*)c->partial, (const Counters*)c->cnt, c->lp_out, c->scalars);
@@ -1992,11 +1973,9 @@ static int close_attempt(mn_context* c, const ImageCall& call, const Plan& pl, A
     A.post.launch(st);
     c->cc_clean = 1;
   }
-  if (c->replay.capturing) {
-    MN_HIP(hipStreamEndCapture(c->replay.cap, &c->replay.gB));
-    MN_HIP(hipGraphInstantiate(&c->replay.eB, c->replay.gB, nullptr, nullptr, 0));
-    MN_HIP(hipGraphLaunch(c->replay.eB, c->side));
-    st = c->side;
+  if (c->replay.capturing) {       // (graph B: on the side stream, where the image forked)
+    const int rc = replay_end(c, &c->replay.gB, &c->replay.eB, st);
+    if (rc != MN_OK) return rc;
     c->replay.capturing = 0;
     c->replay.state = 2;
     c->replay.queued = q;
@@ -2024,7 +2003,7 @@ static int segment_attempt(mn_context* c, const ImageCall& call, mn_stats* stats
   //  test run can be put through an opt-in code path)
   static const int env_flags = getenv("MN_DEBUG_FLAGS_OR") ? atoi(getenv("MN_DEBUG_FLAGS_OR")) : 0;
   c->debug_flags = call.opts.debug_flags | env_flags;
-  c->ext_events = !(call.opts.debug_flags & 2) && !(call.opts.debug_flags & 128);
+  c->ext_events = !(call.opts.debug_flags & (MN_DEBUG_NO_EVENTS | MN_DEBUG_SWEEP_EVENT_PACKETS));
   c->core_radius = call.opts.core_radius != 0 ? call.opts.core_radius : MN_DEFAULT_CORE_RADIUS;
   const Plan pl = make_plan(call, force_mode, speculate);
   c->tie_ref = pl.xengine ? call.opts.tie_order : MN_TIES_LOWEST_ID;
@@ -2051,12 +2030,12 @@ static int replay_launch(mn_context* c, const ImageCall& call) {
   if (rc != MN_OK) return rc;
   const hipStream_t st = call.stream;
   c->debug_flags = call.opts.debug_flags;      // (deliberate carry-over: without MN_DEBUG_FLAGS_OR, unlike segment_attempt)
-  c->ext_events = !(call.opts.debug_flags & 2) && !(call.opts.debug_flags & 128);
+  c->ext_events = !(call.opts.debug_flags & (MN_DEBUG_NO_EVENTS | MN_DEBUG_SWEEP_EVENT_PACKETS));
   c->cores_used = 0;
-  const bool timed = !(call.opts.debug_flags & 2) && !c->ext_events;
+  const bool timed = !(call.opts.debug_flags & MN_DEBUG_NO_EVENTS) && !c->ext_events;
   if (timed) MN_HIP(hipEventRecord(c->ev[0], st));
   // (the key holds buffers, dtype and options: the recorded form, lean or full as the graphs expect it)
-  launch_sweep(c, P, st, sweep_px(c, P), true, true, c->replay.lean_form != 0);
+  launch_sweep(c, P, st, c->replay.sweep);
   if (timed) MN_HIP(hipEventRecord(c->ev[10], st));
   MN_HIP(hipGraphLaunch(c->replay.eA, st));
   MN_HIP(hipEventRecord(c->ev_fork, st));
@@ -2068,6 +2047,23 @@ static int replay_launch(mn_context* c, const ImageCall& call) {
   memset(&c->pend.stats, 0, sizeof(c->pend.stats));
   c->pend.active = 1;
   return MN_OK;
+}
+
+// What two calls must share for the second to replay the first: buffers, stream, shape, element type (with
+// MN_MAPS_LOGITS: a logits call never replays a probability call's graphs), options, offsets.  Bytes used of
+// key[256]; 0: an offset list too long for it (no replay).
+static size_t replay_key(const ImageCall& call, unsigned char* key) {
+  memset(key, 0, 256);
+  const void* ptrs[6] = {call.d_class, call.d_adj, call.d_mask, call.d_objcls, call.d_part, call.stream};
+  const int dims[6] = {call.class_dim, call.offset_dim, call.W, call.H, call.num_classes, call.dtype};
+  size_t kb = 0;
+  memcpy(key + kb, ptrs, sizeof(ptrs)); kb += sizeof(ptrs);
+  memcpy(key + kb, dims, sizeof(dims)); kb += sizeof(dims);
+  memcpy(key + kb, &call.opts, sizeof(call.opts)); kb += sizeof(call.opts);
+  const size_t ob = sizeof(int) * 2 * (size_t)call.offset_dim;
+  if (kb + ob > 256) return 0;
+  memcpy(key + kb, call.offs, ob);
+  return kb + ob;
 }
 
 // First half: queue everything for one image and return.  In components mode (the default for
@@ -2084,22 +2080,12 @@ extern "C" int mn_segment_launch_t(mn_context* c, const void* d_class_pred, int 
   q.call = ImageCall{d_class_pred, d_adj_pred, dtype, class_dim, offset_dim, W, H, num_classes, d_mask, d_object_class, d_partition};
   image_call(&q.call, offset_list, opts, stream);
   const mn_options& o = q.call.opts;
-  // ---- replay (debug_flags bit 5, with bit 4): see mn_context::Replay ----
+  // ---- replay (MN_DEBUG_REPLAY, with MN_DEBUG_LEAN_EVENTS): see mn_context::Replay ----
   mn_context::Replay& rp = c->replay;
-  const bool want_replay = (o.debug_flags & 32) && (o.debug_flags & 16) && offset_list &&
+  const bool want_replay = (o.debug_flags & MN_DEBUG_REPLAY) && (o.debug_flags & MN_DEBUG_LEAN_EVENTS) && offset_list &&
                            offset_dim > 0 && offset_dim <= MN_MAX_OFFSETS && W % 4 == 0;
   unsigned char key[256];
-  size_t kb = 0;
-  if (want_replay) {
-    memset(key, 0, sizeof(key));
-    const void* ptrs[6] = {d_class_pred, d_adj_pred, d_mask, d_object_class, d_partition, stream};
-    const int dims[6] = {class_dim, offset_dim, W, H, num_classes, dtype};      // (dtype with MN_MAPS_LOGITS: a logits call never replays a probability call's graphs)
-    memcpy(key + kb, ptrs, sizeof(ptrs)); kb += sizeof(ptrs);
-    memcpy(key + kb, dims, sizeof(dims)); kb += sizeof(dims);
-    memcpy(key + kb, &o, sizeof(o)); kb += sizeof(o);
-    const size_t ob = sizeof(int) * 2 * (size_t)offset_dim;
-    if (kb + ob <= sizeof(key)) { memcpy(key + kb, q.call.offs, ob); kb += ob; } else kb = 0;
-  }
+  const size_t kb = want_replay ? replay_key(q.call, key) : 0;
   const bool same_key = want_replay && kb && rp.state >= 1 && rp.key_bytes == kb && memcmp(rp.key, key, kb) == 0;
   if (same_key && rp.state == 2 && c->cc_clean) return replay_launch(c, q.call);
   if (want_replay && kb && !same_key) drop_replay_graphs(rp);      // a new key: forget the graphs of the old one
@@ -2107,13 +2093,7 @@ extern "C" int mn_segment_launch_t(mn_context* c, const void* d_class_pred, int 
   rp.capturing = (same_key && rp.state == 1 && c->cc_clean) ? 1 : 0;
   const int was_clean = c->cc_clean;
   const int rc = segment_attempt(c, q.call, &q.stats, 0, true, true);
-  if (rp.capturing) {              // the attempt did not take the fused path after all, or failed half-way
-    hipGraph_t open_graph = nullptr;
-    if (hipStreamEndCapture(rp.cap, &open_graph) == hipSuccess && open_graph) (void)hipGraphDestroy(open_graph);
-    (void)hipGetLastError();
-    rp.capturing = 0;
-    rp.state = 0;
-  }
+  if (rp.capturing) replay_abandon(rp);      // the attempt did not take the fused path after all, or failed half-way
   if (want_replay && kb && rp.state == 0 && rc == MN_PENDING && was_clean && c->cc_clean &&
       o.variant == MN_VARIANT_CSEGMENT && (W * H) % 4 == 0) {
     memcpy(rp.key, key, kb);       // a fused speculative attempt in the steady state: the next one records
@@ -2392,23 +2372,20 @@ extern "C" int mn_sweep_device_t(mn_context* c, const void* d_class_pred, int cl
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int N = P.N;
   if (ensure_fast(c) != MN_OK) return MN_ERR_NO_DEVICE;      // (deliberate carry-over: any failure reads as "no device" here)
-  c->debug_flags = call.opts.debug_flags | 2;      // (no events)
+  c->debug_flags = call.opts.debug_flags | MN_DEBUG_NO_EVENTS;
   c->ext_events = 0;
   c->cc_clean = 0;
-  const int px = sweep_px(c, P);                // (4 pixels per lane: also with W % 4 != 0, see run_components)
-  const bool four = px >= 4;
-  const bool fused_cls = four;
-  const size_t sign_blocks = grid_for((size_t)(N / px), MN_CC_SIGN_THREADS);
-  const size_t sign_waves = sign_blocks * (MN_CC_SIGN_THREADS / 64);
+  const SweepForm F = sweep_form_of(c, P, SWEEP_EXPORT);
+  const size_t sign_waves = (size_t)F.waves;
   MN_HIP(hipMemsetAsync(c->scalars, 0, MN_NSCALARS * sizeof(int), st));
-  launch_sweep(c, P, st, px, fused_cls, false);
+  launch_sweep(c, P, st, F);
   MN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_neg_out), 0x7FC00000, (size_t)P.O * N, st));
   hipLaunchKernelGGL(mn_cc_export_neg, dim3((unsigned)grid_for((size_t)N, 256)), dim3(256), 0, st, P,
                      (const unsigned*)c->cc_negbits, d_neg_out);
   MN_HIP(hipMemcpyAsync(d_bits_out, c->cc_bits, (size_t)N * sizeof(unsigned), hipMemcpyDeviceToDevice, st));
-  if (d_cls_out && fused_cls) MN_HIP(hipMemcpyAsync(d_cls_out, c->cls0, (size_t)N, hipMemcpyDeviceToDevice, st));
-  if (d_gsum_out && fused_cls)          // (plane c of the sweep's products starts at c * N ints and holds N / 4 of them)
-    MN_HIP(hipMemcpy2DAsync(d_gsum_out, (size_t)(N / 4) * sizeof(int), c->lpsum, gsum_stride(N) * sizeof(int),
+  if (d_cls_out && F.cls) MN_HIP(hipMemcpyAsync(d_cls_out, c->cls0, (size_t)N, hipMemcpyDeviceToDevice, st));
+  if (d_gsum_out && F.cls)              // (plane c of the sweep's products starts at c * N ints and holds N / 4 of them)
+    MN_HIP(hipMemcpy2DAsync(d_gsum_out, (size_t)(N / 4) * sizeof(int), c->lpsum, (size_t)N * sizeof(int),
                             (size_t)(N / 4) * sizeof(int), (size_t)P.C, hipMemcpyDeviceToDevice, st));
   HostBuf<double> hp(sign_waves * 2);
   if (!hp.ok()) return MN_ERR_INTERNAL;
@@ -2418,7 +2395,7 @@ extern "C" int mn_sweep_device_t(mn_context* c, const void* d_class_pred, int cl
   double t = 0.0;
   for (size_t b = 0; b < sign_waves; b++) t += hp[2 * b];
   if (logsum_out) *logsum_out = t;
-  if (info_out) { info_out[0] = px; info_out[1] = fused_cls ? 1 : 0; info_out[2] = c->h_scalars[6]; }
+  if (info_out) { info_out[0] = F.px; info_out[1] = F.cls ? 1 : 0; info_out[2] = c->h_scalars[6]; }
   MN_HIP(hipGetLastError());
   g_last_status = MN_OK;
   return MN_OK;
@@ -2449,7 +2426,7 @@ extern "C" int mn_sweep_time_device_t(mn_context* c, const void* const* d_class_
   if (rc != MN_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (ensure_fast(c) != MN_OK) return MN_ERR_NO_DEVICE;      // (deliberate carry-over: any failure reads as "no device" here)
-  c->debug_flags = call.opts.debug_flags | 2;      // (no events inside)
+  c->debug_flags = call.opts.debug_flags | MN_DEBUG_NO_EVENTS;
   c->ext_events = 0;
   c->cc_clean = 0;
   MN_HIP(hipMemsetAsync(c->scalars, 0, MN_NSCALARS * sizeof(int), st));
@@ -2459,8 +2436,7 @@ extern "C" int mn_sweep_time_device_t(mn_context* c, const void* const* d_class_
     for (int i = 0; i < n; i++) {
       call.d_class = d_class_pred[i % n_inputs]; call.d_adj = d_adj_pred[i % n_inputs];
       fill_params(&P, call);
-      const int px = sweep_px(c, P);
-      launch_sweep(c, P, st, px, true, true, sweep_lean_form(c, P, px));      // (debug_flags bit 9: the full form)
+      launch_sweep(c, P, st, sweep_form_of(c, P, SWEEP_TIMING));      // (per launch: the alignment of the maps may alternate)
     }
     if (phase == 1) MN_HIP(hipEventRecord(c->ev[1], st));
   }

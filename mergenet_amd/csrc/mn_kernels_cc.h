@@ -44,6 +44,7 @@ static_assert(MN_MAX_OFFSETS <= 32, "edge masks are 32-bit words: one bit per of
 
 #include "mn_device.h"
 #include "mn_kernels_merge.h"
+#include "mn_sweep_form.h"      /* LeanOut, MN_CC_SIGN_THREADS: what the host decides about a launch of the sweep */
 
 #define MN_LP_FIX 16777216.0     /* 2^24: fixed-point scale of class log-prob sums.  |log p| <= 16, so a
                                     value fits an int32 (ONE v_cvt_i32_f32; a float -> int64 conversion
@@ -87,21 +88,14 @@ __device__ __forceinline__ int4 mn_ld_int4_unaligned(const int* __restrict__ p) 
 //    on a separable map, taken as the log of a PRODUCT per lane (factors in [0.5, 1], folded
 //    every 80 factors): one max and one multiply per value instead of a log.
 // PLAIN: no clip and no same_different_bias (the production setting), decided at compile time.
-#define MN_CC_SIGN_THREADS 256
 #define MN_CC_SIGN_G 5           /* offsets whose loads are in flight together */
 #define MN_CC_EDGE_PIXBITS 26    /* components mode serves N <= 2^26 */
 
-// Streaming accesses of the sweep: every plane value is read once and every output written once, so the
-// loads / stores may carry the non-temporal hint (-DMN_NT_LOADS / -DMN_NT_STORES: measured)
-typedef float mn_f4v __attribute__((ext_vector_type(4)));
+// Streaming accesses of the sweep: every plane value is read once and every output written once.  (The
+// non-temporal hint on these loads / stores was measured and removed: DESIGN.md section 4.1.)
 typedef unsigned mn_u4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 mn_ld_stream4(const float* p) {
-#ifdef MN_NT_LOADS
-  const mn_f4v t = __builtin_nontemporal_load(reinterpret_cast<const mn_f4v*>(p));
-  return make_float4(t.x, t.y, t.z, t.w);
-#else
   return *reinterpret_cast<const float4*>(p);
-#endif
 }
 // The 16-bit maps (DT = MN_DTYPE_F16 / MN_DTYPE_BF16): a lane's 4 values are one 8-byte load, its 8 values one
 // 16-byte load; DT = MN_DTYPE_F32 is the float load above, unchanged.
@@ -116,11 +110,7 @@ __device__ __forceinline__ float4 mn_ld_stream4_t(const void* base, size_t i) {
     return mn_ld_stream4(static_cast<const float*>(base) + i);
   } else {
     const mn_u2v* q = reinterpret_cast<const mn_u2v*>(static_cast<const mn_u16*>(base) + i);
-#ifdef MN_NT_LOADS
-    const mn_u2v t = __builtin_nontemporal_load(q);
-#else
     const mn_u2v t = *q;
-#endif
     const float2 a = mn_widen2<DT>(t.x), b = mn_widen2<DT>(t.y);
     return make_float4(a.x, a.y, b.x, b.y);
   }
@@ -129,11 +119,7 @@ template <int DT, bool LG = false>
 __device__ __forceinline__ void mn_ld_stream8_t(const void* base, size_t i, float* v) {
   static_assert(DT != MN_DTYPE_F32, "8 values per load: 16-bit maps only");
   const mn_u4v* q = reinterpret_cast<const mn_u4v*>(static_cast<const mn_u16*>(base) + i);
-#ifdef MN_NT_LOADS
-  const mn_u4v t = __builtin_nontemporal_load(q);
-#else
   const mn_u4v t = *q;
-#endif
   const float2 a = mn_widen2<DT>(t.x), b = mn_widen2<DT>(t.y), c = mn_widen2<DT>(t.z), d = mn_widen2<DT>(t.w);
   v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y; v[4] = c.x; v[5] = c.y; v[6] = d.x; v[7] = d.y;
   if constexpr (LG) {
@@ -148,19 +134,10 @@ __device__ __forceinline__ float mn_ld_stream1_t(const void* base, size_t i) {
   else return mn_widen<DT>(static_cast<const mn_u16*>(base)[i]);
 }
 __device__ __forceinline__ void mn_st_stream(int* p, int v) {
-#ifdef MN_NT_STORES
-  __builtin_nontemporal_store(v, p);
-#else
   *p = v;
-#endif
 }
 __device__ __forceinline__ void mn_st_stream(uint4* p, uint4 v) {
-#ifdef MN_NT_STORES
-  mn_u4v t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
-  __builtin_nontemporal_store(t, reinterpret_cast<mn_u4v*>(p));
-#else
   *p = v;
-#endif
 }
 
 // (a 16-bit map is always clipped on load: its PLAIN form is the clip alone, no same_different_bias; so are
@@ -193,13 +170,10 @@ struct ClsOut {
 //    the word  1 | lowest arg-max class << 8 | highest << 16  at int flag0 + g of plane 0.  Its lanes write no
 //    per-lane products.  Every other group writes the word 0 and its per-lane products as ever.  The records
 //    live in the part of the planes the per-lane products leave free (N / 4 of N ints per plane).
-struct LeanOut { int kh; int packed; int rec0; int flag0; };
-#ifndef MN_CC_LEAN_FLAT
-#define MN_CC_LEAN_FLAT 1      /* 1: mn_cc_sums_lean leaves parent[] flat, as mn_cc_sums does; 0: it only reads parent[]
-                                  and mn_cc_cross chases at both ends of its edges.  Step of the benchmark loop, three
-                                  runs each, alternating: 0.1252-0.1264 ms (1) against 0.1269-0.1275 (0) -- the 8 MB
-                                  read once more here cost less than the chases in mn_cc_cross and mn_write_mask4 */
-#endif
+// (struct LeanOut: mn_sweep_form.h, where the host fills it.)  mn_cc_sums_lean leaves parent[] flat, as mn_cc_sums
+// does.  The form in which it only reads parent[] and mn_cc_cross chases at both ends of its edges was measured and
+// removed: step of the benchmark loop, three runs each, alternating, 0.1252-0.1264 ms (flat) against 0.1269-0.1275
+// -- the 8 MB read once more here cost less than the chases in mn_cc_cross and mn_write_mask4.
 
 // Sum / minimum of a 32-bit value over the GL = 16 | 8 lanes of a group (all of them get it): quad_perm xor 1,
 // xor 2, row_half_mirror and (16 lanes) row_mirror -- moves on the VALU, no LDS crossbar.
@@ -576,9 +550,7 @@ __global__ __launch_bounds__(256) void mn_cc_export_neg(ImgParams P, const unsig
 //     pair of roots in a wave);
 //  3. the flattened labels go to `parent` as pixel ids.  Local order (row, column) is the global
 //     pixel order, so "larger root under smaller" keeps holding across stages.
-#ifndef MN_CC_TILE_ROWS
 #define MN_CC_TILE_ROWS 16    /* rows of a labelling tile (x 64 columns = the block of mn_cc_tiles) */
-#endif
 //  4. every pixel's component size starts at 0 and the accumulators of the TILE roots are cleared
 //     (class sums -- only the roots' slots of the C planes are ever used -- and class range): the
 //     stages that follow only remove roots, so the final roots are among them.
@@ -925,21 +897,10 @@ __global__ __launch_bounds__(256) void mn_count_cross_edges(ImgParams P, const i
 // table (root -> C+1 fixed-point sums); the block then issues ONE global atomic per root and class:
 // a 1.6 M-pixel background is a hot word for every wave of the image, and one word takes only ~88
 // atomics/us.  64-bit fixed-point sums (2^-32) are order-independent.
-#ifndef MN_CC_SUM_THREADS
 #define MN_CC_SUM_THREADS 1024
-#endif
-#ifndef MN_CC_SUMS_G
 #define MN_CC_SUMS_G 9         /* class sums of a lane requested together (mn_cc_sums) */
-#endif
-#ifndef MN_CC_SUMS_ITERS
 #define MN_CC_SUMS_ITERS 1     /* chunks of 4096 pixels per block of mn_cc_sums */
-#endif
-#ifndef MN_CC_SUM_AHEAD
 #define MN_CC_SUM_AHEAD 1   /* planes in flight ahead of the one in use: 1 at 1024 threads measured best (37.3 us by events; 2: 41.4, 3: 42.4; 512 threads: 43.7 / 40.8; 256: 47.6) -- occupancy matters more */
-#endif
-#ifndef MN_CC_SUMS_WAVE
-#define MN_CC_SUMS_WAVE 1     /* a wave inside one component: ONE LDS atomic per class (0: one per 16-lane row) */
-#endif
 #define MN_CC_SUM_SLOTS 64
 __device__ __forceinline__ int mn_lds_root_slot(int* s_root, int root) {
   unsigned h = ((unsigned)root * 2654435761u) >> 26;             // 6 bits
@@ -1279,13 +1240,9 @@ __global__ __launch_bounds__(MN_CC_SUM_THREADS) void mn_cc_sums(
         for (int a = 0; a < G; a++) {
           if (c0 + a >= P.C) break;
           if (uni) {
-#if MN_CC_SUMS_WAVE
+            // a wave inside one component: ONE LDS atomic per class
             const i64 ws = mn_rows4_sum(mn_row16_sum((i64)g[a]));
             if (lane == 0) mn_cc_add(P, S, s_root, s_val, lp_acc, r.x, c0 + a, s0, ws);
-#else
-            const i64 rs = mn_row16_sum((i64)g[a]);
-            if ((lane & 15) == 0) mn_cc_add(P, S, s_root, s_val, lp_acc, r.x, c0 + a, s0, rs);
-#endif
           } else {
             mn_cc_add(P, S, s_root, s_val, lp_acc, r.x, c0 + a, s0, (i64)g[a]);
           }
@@ -1294,7 +1251,6 @@ __global__ __launch_bounds__(MN_CC_SUM_THREADS) void mn_cc_sums(
       const int lo1 = min(min((int)b.x, (int)b.y), min((int)b.z, (int)b.w));
       const int hi1 = max(max((int)b.x, (int)b.y), max((int)b.z, (int)b.w));
       if (uni) {
-#if MN_CC_SUMS_WAVE
         int lo = mn_row16_min(lo1), hi = -mn_row16_min(-hi1);
         lo = min(min(__builtin_amdgcn_readlane(lo, 0), __builtin_amdgcn_readlane(lo, 16)),
                  min(__builtin_amdgcn_readlane(lo, 32), __builtin_amdgcn_readlane(lo, 48)));
@@ -1304,11 +1260,6 @@ __global__ __launch_bounds__(MN_CC_SUM_THREADS) void mn_cc_sums(
           mn_cc_add(P, S, s_root, s_val, lp_acc, r.x, P.C, s0, 256);
           mn_cc_cls(s_min, s_max, clsmin, clsmax, r.x, s0, lo, hi);
         }
-#else
-        if ((lane & 15) == 0) mn_cc_add(P, S, s_root, s_val, lp_acc, r.x, P.C, s0, 64);
-        const int lo = mn_row16_min(lo1), hi = -mn_row16_min(-hi1);
-        if ((lane & 15) == 0) mn_cc_cls(s_min, s_max, clsmin, clsmax, r.x, s0, lo, hi);
-#endif
       } else {
         mn_cc_add(P, S, s_root, s_val, lp_acc, r.x, P.C, s0, 4);
         mn_cc_cls(s_min, s_max, clsmin, clsmax, r.x, s0, lo1, hi1);
@@ -1362,10 +1313,8 @@ __global__ __launch_bounds__(MN_CC_SUM_THREADS) void mn_cc_sums(
 //  2. The listed groups are worked off 16 lanes each, by all lanes of the block, the way every lane of
 //     mn_cc_sums goes; lanes across a component boundary are queued and
 //  3. worked off one (lane, class) item each.
-//  (MN_CC_LEAN_FLAT, the default: between 2 and 3 every lane of the block's pixels re-roots its four `parent`
-//  entries and writes back those the hook left one or two steps from their root, as mn_cc_sums does.  Without it
-//  `parent` is only read here and mn_cc_cross chases at both ends of its edges, as mn_write_mask4 always does:
-//  measured slower, see the macro.)
+//  (Between 2 and 3 every lane of the block's pixels re-roots its four `parent` entries and writes back those the
+//  hook left one or two steps from their root, as mn_cc_sums does.)
 // With five groups in six uniform, 16 lanes per group would leave most of a wide block idle: 256 lanes, of
 // which stage 1 uses 64 and stage 2 about 160 at the benchmark's maps.
 #define MN_CC_LEAN_THREADS 256
@@ -1446,7 +1395,6 @@ __global__ __launch_bounds__(MN_CC_LEAN_THREADS) void mn_cc_sums_lean(
       s_q[atomicAdd(&s_qn, 1)] = i;
     }
   }
-#if MN_CC_LEAN_FLAT
   for (int t = threadIdx.x; t < MN_CC_LEAN_GROUPS * 16; t += MN_CC_LEAN_THREADS) {      // every lane of the block's pixels
     const int i = g0 * 16 + t;
     if (i >= n4) continue;
@@ -1459,7 +1407,6 @@ __global__ __launch_bounds__(MN_CC_LEAN_THREADS) void mn_cc_sums_lean(
     if (r.x != r_in.x || r.y != r_in.y || r.z != r_in.z || r.w != r_in.w)
       *reinterpret_cast<int4*>(S.parent + 4 * (size_t)i) = r;
   }
-#endif
   __syncthreads();
   const int nq = s_qn;
   for (int t = threadIdx.x; t < nq * P.C; t += MN_CC_LEAN_THREADS) {

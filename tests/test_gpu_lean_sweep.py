@@ -1,5 +1,5 @@
 """The lean form of what the sweep leaves (packed edge masks, one record per uniform 64-pixel group) against the full
-form inside one build: ``debug_flags |= 512`` keeps the full form on the components path, and everything a call
+form inside one build: ``debug_flags |= MN_DEBUG_SWEEP_FULL_FORM`` keeps the full form on the components path, and everything a call
 returns -- mask, class table with its -1 padding, partition, every counter of the stats, ``total_logprob`` -- must be
 equal, bit for bit.  The class sums are integer sums, so there is no tolerance anywhere in this file.
 
@@ -21,7 +21,7 @@ from test_gpu_lowp import STATS
 
 pytestmark = pytest.mark.gpu
 
-FULL = 512                                    # debug_flags bit 9: the full form on the product path
+FULL = seg.MN_DEBUG_SWEEP_FULL_FORM            # the full form on the product path
 OFFS10 = [tuple(int(x) for x in o) for o in synth.generate_offsets(40, 10)]
 
 

@@ -20,7 +20,7 @@ m = seg.Merger(H, W, C, len(offs))
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 res = {"lean": [], "full": []}
 for r in range(rounds):
-    for name, flags in (("lean", 0), ("full", 512)):
+    for name, flags in (("lean", 0), ("full", seg.MN_DEBUG_SWEEP_FULL_FORM)):
         o = seg.default_options(merge_logprob_bias=0.03, debug_flags=flags)
         res[name].append(m.sweep_time(ins, offs, o, reps=400))
 nbytes = (4.0 if dtype == torch.float32 else 2.0) * (C + len(offs)) * H * W
