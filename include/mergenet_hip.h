@@ -478,6 +478,52 @@ int mn_filter_instances_device(mn_context* ctx, const int* d_mask, int height, i
                                int* d_table_out, int* d_object_class_out, float* d_scores_out,
                                int* d_new_count, void* stream);
 
+/* A label mask against the ground-truth label mask, on the device.  The reference's caller ends by handing its
+ * results to COCOeval (egs/cityscape/local/evaluate.py:67-73), which computes per image the IoU of every detection
+ * with every ground-truth instance and matches greedily once per IoU threshold; the ground truth is the label mask
+ * anns_to_mask builds (utils/dataset.py:486-506), what mn_sameness_targets_device takes.  The two calls below are
+ * that per-image part; accumulate, summarize and the annotation files stay on the host.
+ *
+ * mn_overlap_table_device: d_table int32 [num_pred + 1][num_truth + 1], row-major; table[p][g] = number of pixels
+ * with prediction label p and truth label g (p in 0..K, g in 0..G).  A label outside its range (negative, above K
+ * or above G) counts as 0 in either mask.  Row 0 and column 0 are kept: row sums are the prediction areas, column
+ * sums the truth areas, all entries sum to height * width.  ONE pass over both masks: 16-byte loads where
+ * width % 4 == 0 and BOTH masks are 16-byte aligned, 4-byte loads otherwise.  Any image size (not held to the
+ * context's capacity); K == 0 and G == 0 are legal.  MN_ERR_ARGUMENT: a null pointer, a non-positive size,
+ * height * width > INT_MAX, a negative count, (K + 1) * (G + 1) > 2^28.  The call clears the table on `stream`
+ * and launches; it only enqueues: no host synchronisation, no copies. */
+int mn_overlap_table_device(mn_context* ctx, const int* d_pred, const int* d_truth,
+                            int height, int width, int num_pred, int num_truth,
+                            int* d_table, void* stream);
+
+/* IoU and matching from that table: COCOeval.evaluateImg with maxDets >= K, for all thresholds at once.
+ * Arrays per instance are indexed label - 1.  With area_p[k] the sum of row k and area_g[j] the sum of column j:
+ *   iou[k][j] = table[k][j] / (area_p[k] + area_g[j] - table[k][j]); for a crowd truth instance table[k][j] /
+ *   area_p[k]; 0 where the denominator is 0.  float64, ONE IEEE division of exact integers.
+ *   truth_ignore[j] = crowd[j] || area_g[j] < area_lo || area_g[j] > area_hi.
+ *   Order: detections by descending score, equal scores in ascending label, a NaN score last; in label order
+ *   without scores.  Truth instances: the non-ignored, then the ignored, each group in ascending label.
+ *   Per threshold t and detection d in that order, with lo = min(t, 1 - 1e-10): the candidates are the truth
+ *   instances of d's class that are unmatched at this t or crowd and have iou[d][j] >= lo.  d takes the
+ *   non-ignored candidate of greatest IoU if there is one, else the ignored candidate of greatest IoU; among equal
+ *   IoUs the LAST in truth order (the greatest label of the group).  On a match with m: pred_match[t][d] = m (a
+ *   truth label 1..G), truth_match[t][m] = d (a prediction label; a crowd instance keeps the last d),
+ *   pred_ignore[t][d] = truth_ignore[m].  A detection without a match is ignored iff area_p[d] < area_lo or
+ *   area_p[d] > area_hi.  Unmatched entries are 0.
+ * thresholds: HOST array of num_thresholds (1..16) values; they travel as kernel arguments.  d_pred_score and
+ * d_truth_crowd may be NULL (label order; no crowd), d_iou ([K][G]) and d_truth_ignore ([G]) too (not wanted).
+ * d_pred_match, d_pred_ignore: [T][K]; d_truth_match: [T][G].  K, G <= MN_MATCH_MAX_INSTANCES, else
+ * MN_ERR_CAPACITY; with K == 0 or G == 0 there is nothing to match and every output is zero.  Calls on one context
+ * share its scratch (allocated by the first call): keep them on one stream.  Enqueues only. */
+#define MN_MATCH_MAX_INSTANCES 4096
+int mn_match_overlaps_device(mn_context* ctx, const int* d_table, int num_pred, int num_truth,
+                              const int* d_pred_class, const float* d_pred_score,
+                              const int* d_truth_class, const unsigned char* d_truth_crowd,
+                              const double* thresholds, int num_thresholds,
+                              double area_lo, double area_hi,
+                              double* d_iou, int* d_pred_match, int* d_truth_match,
+                              unsigned char* d_pred_ignore, unsigned char* d_truth_ignore, void* stream);
+
 /* Wire format of the multi-GPU mask exchange (the all-gather of final instance masks the north
  * star asks for; the reference has no exchange, its jobs write files: segment.py:59-61).  d_wire is
  * int16 [n_pixels + 1 + max_instances + 4]: the labels (0..K), K, the classes of labels 1..K

@@ -21,6 +21,7 @@
 #include "mn_kernels_output.h"
 #include "mn_kernels_prepare.h"
 #include "mn_kernels_instances.h"
+#include "mn_kernels_match.h"
 #include "mn_kernels_cc.h"
 #include "mn_sweep_form.h"
 #include "mn_kernels_tail.h"
@@ -158,6 +159,7 @@ struct mn_context {
   hipEvent_t ev_fork;
   ImgParams last_params;  // of the most recent mn_segment_device call (for mn_instance_scores_device)
   int last_valid;
+  MnMatchWork* match_work;  // scratch of mn_match_overlaps_device (mn_kernels_match.h): allocated on first use
   // workspace of the exact engine (mn_kernels_exact.h): allocated on first use, for the largest
   // image seen so far
   struct XWork {
@@ -499,7 +501,8 @@ extern "C" void mn_destroy(mn_context* c) {
   void* dev[] = {c->ocls, c->cls0, c->lpvalid, c->matched, c->pruned, c->osize, c->parent, c->mate, c->root,
                  c->label, c->mapbuf, c->lpsum, c->lp_acc, c->ball, c->bsub, c->fin_lists, c->cc_tcount, c->cc_lcount, c->cc_bits, c->cc_roots, c->cc_negbits,
                  c->block_count, c->wire_counts, c->partial, c->statblk,
-                 c->bg_key, c->gmax, c->touch, c->theta, c->progress, c->d_class, c->d_same, c->d_mask, c->d_objcls, c->d_part};
+                 c->bg_key, c->gmax, c->touch, c->theta, c->progress, c->d_class, c->d_same, c->d_mask, c->d_objcls, c->d_part,
+                 c->match_work};
   for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); i++)
     if (dev[i]) (void)hipFree(dev[i]);
   x_free(c);
@@ -2737,6 +2740,87 @@ extern "C" int mn_filter_instances_device(mn_context* c, const int* d_mask, int 
   else
     hipLaunchKernelGGL(mn_relabel_mask, dim3(grid_for(N, 256)), dim3(256), 0, st, d_mask, N, num_instances,
                        (const int*)d_remap, d_mask_out);
+  MN_HIP(hipGetLastError());
+  g_last_status = MN_OK;
+  return MN_OK;
+}
+
+// ---- overlap table, IoU and matching against the ground truth (mn_kernels_match.h) ------------------
+// Both entry points only enqueue: no host synchronisation, no copy.  Nothing of the segmentation path runs here.
+extern "C" int mn_overlap_table_device(mn_context* c, const int* d_pred, const int* d_truth, int height, int width,
+                                       int num_pred, int num_truth, int* d_table, void* stream) {
+  if (!c || !d_pred || !d_truth || !d_table || height <= 0 || width <= 0 || num_pred < 0 || num_truth < 0 ||
+      (size_t)height * (size_t)width > (size_t)INT_MAX ||
+      ((long long)num_pred + 1) * ((long long)num_truth + 1) > (1LL << 28)) {
+    g_last_status = MN_ERR_ARGUMENT;
+    return MN_ERR_ARGUMENT;
+  }
+  MN_HIP(hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t entries = (size_t)(num_pred + 1) * (size_t)(num_truth + 1);
+  MN_HIP(hipMemsetAsync(d_table, 0, entries * sizeof(int), st));
+  const bool vec = width % 4 == 0 &&
+                   ((reinterpret_cast<uintptr_t>(d_pred) | reinterpret_cast<uintptr_t>(d_truth)) & 15) == 0;
+  const int per_chunk = vec ? 256 : 64;                          // pixels of one 64-lane load
+  const int chunks_per_row = (width + per_chunk - 1) / per_chunk;
+  const int total = height * chunks_per_row;                     // <= H * W
+  const int waves = MN_OVL_WORKGROUPS * (MN_OVL_THREADS / 64);
+  const int chunks_per_wave = (total + waves - 1) / waves;       // >= 1
+  const dim3 g(grid_for(total, (unsigned)(MN_OVL_THREADS / 64) * (unsigned)chunks_per_wave)), b(MN_OVL_THREADS);
+  if (vec)
+    hipLaunchKernelGGL(mn_overlap_table_runs<4>, g, b, 0, st, d_pred, d_truth, height, width, num_pred, num_truth,
+                       chunks_per_row, total, chunks_per_wave, d_table);
+  else
+    hipLaunchKernelGGL(mn_overlap_table_runs<1>, g, b, 0, st, d_pred, d_truth, height, width, num_pred, num_truth,
+                       chunks_per_row, total, chunks_per_wave, d_table);
+  MN_HIP(hipGetLastError());
+  g_last_status = MN_OK;
+  return MN_OK;
+}
+
+extern "C" int mn_match_overlaps_device(mn_context* c, const int* d_table, int num_pred, int num_truth,
+                                         const int* d_pred_class, const float* d_pred_score,
+                                         const int* d_truth_class, const unsigned char* d_truth_crowd,
+                                         const double* thresholds, int num_thresholds, double area_lo,
+                                         double area_hi, double* d_iou, int* d_pred_match, int* d_truth_match,
+                                         unsigned char* d_pred_ignore, unsigned char* d_truth_ignore, void* stream) {
+  const int K = num_pred, G = num_truth, T = num_thresholds;
+  if (!c || !d_table || !thresholds || T < 1 || T > 16 || K < 0 || G < 0 ||
+      (K > 0 && (!d_pred_class || !d_pred_match || !d_pred_ignore)) || (G > 0 && (!d_truth_class || !d_truth_match))) {
+    g_last_status = MN_ERR_ARGUMENT;
+    return MN_ERR_ARGUMENT;
+  }
+  if (K > MN_MATCH_MAX_INSTANCES || G > MN_MATCH_MAX_INSTANCES) {
+    g_last_status = MN_ERR_CAPACITY;
+    return MN_ERR_CAPACITY;
+  }
+  MN_HIP(hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (K == 0 || G == 0) {                                        // nothing to match: every output is zero
+    if (K > 0) {
+      MN_HIP(hipMemsetAsync(d_pred_match, 0, (size_t)T * K * sizeof(int), st));
+      MN_HIP(hipMemsetAsync(d_pred_ignore, 0, (size_t)T * K, st));
+    }
+    if (G > 0) {
+      MN_HIP(hipMemsetAsync(d_truth_match, 0, (size_t)T * G * sizeof(int), st));
+      if (d_truth_ignore) MN_HIP(hipMemsetAsync(d_truth_ignore, 0, (size_t)G, st));
+    }
+    g_last_status = MN_OK;
+    return MN_OK;
+  }
+  if (!c->match_work) MN_HIP(dev_alloc(c, &c->match_work, 1));
+  MnThresholds th;
+  for (int i = 0; i < 16; i++) th.t[i] = thresholds[i < T ? i : T - 1];
+  hipLaunchKernelGGL(mn_match_areas, dim3((unsigned)((K + 3) / 4 + (G + 63) / 64)), dim3(MN_MATCH_THREADS), 0, st,
+                     d_table, K, G, d_truth_crowd, area_lo, area_hi, c->match_work, d_truth_ignore);
+  hipLaunchKernelGGL(mn_match_rank, dim3(grid_for(K, MN_MATCH_THREADS)), dim3(MN_MATCH_THREADS), 0, st, K,
+                     d_pred_score, c->match_work);
+  if (d_iou)
+    hipLaunchKernelGGL(mn_match_iou, dim3(grid_for((size_t)K * G, MN_MATCH_THREADS)), dim3(MN_MATCH_THREADS), 0, st,
+                       d_table, K, G, d_truth_crowd, (const MnMatchWork*)c->match_work, d_iou);
+  hipLaunchKernelGGL(mn_match_greedy, dim3(T), dim3(MN_MATCH_THREADS), 0, st, d_table, K, G,
+                     (const MnMatchWork*)c->match_work, d_pred_class, d_truth_class, d_truth_crowd, th, area_lo,
+                     area_hi, d_pred_match, d_truth_match, d_pred_ignore);
   MN_HIP(hipGetLastError());
   g_last_status = MN_OK;
   return MN_OK;

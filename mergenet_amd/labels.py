@@ -5,7 +5,9 @@ order (``utils/csegment/segment.cc:503``), this library in ascending surviving p
 are therefore compared as partitions plus per-instance class.
 
 Also the numpy statements of the instance table and the small-instance filter (``instance_table``,
-``filter_instances``), the checkers of ``Merger.instance_table`` / ``Merger.filter_instances``.
+``filter_instances``), the checkers of ``Merger.instance_table`` / ``Merger.filter_instances``, and those of the
+comparison with the ground truth (``overlap_table``, ``instance_iou``, ``match_instances``), the checkers of
+``Merger.overlap_table`` / ``Merger.match_instances``.
 """
 
 from __future__ import annotations
@@ -133,6 +135,127 @@ def filter_instances(mask: np.ndarray, class_table, num_instances: int, table: n
     if scores is not None:
         new_scores = np.asarray([scores[k - 1] for k in kept], np.float32)
     return out, new_classes, new_scores, new_table, len(kept), remap
+
+
+# ---- overlap table, IoU and matching against the ground truth: the numpy statements of the device path ------
+# (Merger.overlap_table / Merger.match_instances; COCOeval.computeIoU and evaluateImg with maxDets >= K, restated:
+# pycocotools is not needed.  Arrays per instance are indexed label - 1, table rows and columns by the label.)
+
+COCO_THRESHOLDS = np.linspace(0.5, 0.95, 10)
+
+
+def overlap_table(pred: np.ndarray, truth: np.ndarray, num_pred: int, num_truth: int) -> np.ndarray:
+    """int32 [K+1, G+1]: entry [p][g] = number of pixels with prediction label p and truth label g.  A label outside
+    0..K (prediction) or 0..G (truth) counts as 0.  Row sums are the prediction areas, column sums the truth areas."""
+    K, G = int(num_pred), int(num_truth)
+    p = np.asarray(pred).astype(np.int64).reshape(-1)
+    g = np.asarray(truth).astype(np.int64).reshape(-1)
+    if p.shape != g.shape:
+        raise ValueError("the two masks differ in size")
+    p = np.where((p < 0) | (p > K), 0, p)
+    g = np.where((g < 0) | (g > G), 0, g)
+    table = np.zeros((K + 1, G + 1), np.int64)
+    np.add.at(table, (p, g), 1)
+    return table.astype(np.int32)
+
+
+def _crowd_flags(crowd, G):
+    return np.zeros(G, bool) if crowd is None else np.asarray(crowd).astype(bool).reshape(-1)[:G]
+
+
+def instance_iou(table: np.ndarray, crowd=None) -> np.ndarray:
+    """float64 [K, G]: iou[k-1][j-1] = inter / (area_p[k] + area_g[j] - inter) with inter = table[k][j], area_p the
+    row sums and area_g the column sums; inter / area_p[k] for a crowd truth instance; 0 where the denominator is 0.
+    One division of exact integers."""
+    t = np.asarray(table).astype(np.int64)
+    K, G = t.shape[0] - 1, t.shape[1] - 1
+    area_p = t.sum(axis=1)[1:].astype(np.float64)
+    area_g = t.sum(axis=0)[1:].astype(np.float64)
+    inter = t[1:, 1:].astype(np.float64)
+    den = area_p[:, None] + area_g[None, :] - inter
+    den = np.where(_crowd_flags(crowd, G)[None, :], np.broadcast_to(area_p[:, None], (K, G)), den)
+    out = np.zeros((K, G), np.float64)
+    np.divide(inter, den, out=out, where=den != 0)
+    return out
+
+
+def detection_order(scores, K: int):
+    """Labels - 1 of the detections in the order they are taken: descending score, equal scores in ascending label, a
+    NaN score last; label order without scores."""
+    if scores is None:
+        return list(range(K))
+    s = [float(v) for v in np.asarray(scores).reshape(-1)[:K]]
+    return sorted(range(K), key=lambda k: (1, 0.0, k) if s[k] != s[k] else (0, -s[k], k))
+
+
+def match_instances(table, pred_classes, truth_classes, scores=None, crowd=None, thresholds=None,
+                    area_range=(0.0, 1e10), form: str = "closed") -> dict:
+    """COCO's greedy matching of one image for every IoU threshold (``None``: the ten of COCO), from the overlap
+    table.  Returns ``{"pred_match": int32 [T,K] (truth label or 0), "truth_match": int32 [T,G] (prediction label
+    or 0), "pred_ignore": bool [T,K], "truth_ignore": bool [G], "iou": float64 [K,G]}``.
+
+    ``form="loop"`` is COCOeval.evaluateImg's loop over the truth instances in truth order (non-ignored first, then
+    ignored, each in ascending label; ``if iou < best: continue`` keeps the LAST of equals; it stops at the first
+    ignored instance once a non-ignored one is held).  ``form="closed"`` states its outcome: of the candidates --
+    d's class, unmatched at this threshold or crowd, IoU >= min(t, 1 - 1e-10) -- the non-ignored one of greatest IoU
+    if there is any, else the ignored one of greatest IoU, the greatest label among equals.  With K == 0 or G == 0
+    there is nothing to match and every output is zero."""
+    t = np.asarray(table).astype(np.int64)
+    K, G = t.shape[0] - 1, t.shape[1] - 1
+    th = COCO_THRESHOLDS if thresholds is None else np.asarray(thresholds, np.float64).reshape(-1)
+    T = len(th)
+    area_lo, area_hi = float(area_range[0]), float(area_range[1])
+    res = {"pred_match": np.zeros((T, K), np.int32), "truth_match": np.zeros((T, G), np.int32),
+           "pred_ignore": np.zeros((T, K), bool), "truth_ignore": np.zeros(G, bool),
+           "iou": np.zeros((K, G), np.float64)}
+    if K == 0 or G == 0:
+        return res
+    pc = np.asarray(pred_classes).reshape(-1)[:K]
+    tc = np.asarray(truth_classes).reshape(-1)[:G]
+    is_crowd = _crowd_flags(crowd, G)
+    area_p = t.sum(axis=1)[1:].astype(np.float64)
+    area_g = t.sum(axis=0)[1:].astype(np.float64)
+    ign = is_crowd | (area_g < area_lo) | (area_g > area_hi)
+    iou = instance_iou(t, is_crowd)
+    order = detection_order(scores, K)
+    pm, tm, pi = res["pred_match"], res["truth_match"], res["pred_ignore"]
+    truth_order = [j for j in range(G) if not ign[j]] + [j for j in range(G) if ign[j]]
+    for ti in range(T):
+        lo = min(float(th[ti]), 1 - 1e-10)
+        for d in order:
+            m = -1
+            if form == "loop":
+                best = lo
+                for j in truth_order:
+                    if tc[j] != pc[d]:
+                        continue
+                    if tm[ti, j] > 0 and not is_crowd[j]:
+                        continue
+                    if m > -1 and not ign[m] and ign[j]:
+                        break
+                    if iou[d, j] < best:
+                        continue
+                    best = iou[d, j]
+                    m = j
+            elif form == "closed":
+                cand = (tc == pc[d]) & ((tm[ti] == 0) | is_crowd) & (iou[d] >= lo)
+                for group in (~ign, ign):
+                    c = np.flatnonzero(cand & group)
+                    if c.size:
+                        m = int(c[iou[d, c] == iou[d, c].max()].max())
+                        break
+            else:
+                raise ValueError("form: 'loop' or 'closed'")
+            if m == -1:
+                continue
+            pm[ti, d] = m + 1
+            tm[ti, m] = d + 1
+            pi[ti, d] = ign[m]
+    outside = (area_p < area_lo) | (area_p > area_hi)
+    pi |= (pm == 0) & outside[None, :]
+    res["truth_ignore"] = ign
+    res["iou"] = iou
+    return res
 
 
 # ---- uniform groups of the sweep's lean form: the numpy twin of the rule in mn_cc_sign ----------------------

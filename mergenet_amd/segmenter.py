@@ -40,6 +40,8 @@ MN_DEBUG_SWEEP_FULL_FORM = 512   # the sweep of components mode leaves the full 
 MN_DTYPE_F32, MN_DTYPE_F16, MN_DTYPE_BF16 = 0, 1, 2   # enum mn_dtype: element type of the maps (*_t entry points)
 MN_MAPS_LOGITS = 0x100   # or-ed into that dtype: both maps hold logits, the kernels take the sigmoid on load
 MN_ERR_ARGUMENT = -1
+MN_ERR_CAPACITY = -4
+MN_MATCH_MAX_INSTANCES = 4096   # most prediction / truth instances of Merger.match_instances
 MN_PROVE_ALWAYS, MN_PROVE_BY_MODE, MN_PROVE_NEVER = 1, 0, -1   # mn_options.require_proof
 MN_TIES_DEFAULT, MN_TIES_REFERENCE, MN_TIES_LOWEST_ID = 0, 1, 2   # mn_options.tie_order
 MN_PROOF_NONE, MN_PROOF_CERTIFICATE, MN_PROOF_SEQUENTIAL, MN_PROOF_SEQUENTIAL_TIES = 0, 1, 2, 3   # mn_stats.proof
@@ -88,12 +90,12 @@ EXPORTS = ["mn_default_options", "mn_create", "mn_destroy", "mn_workspace_bytes"
            "mn_segment_device", "mn_segment_launch", "mn_segment_finish", "mn_segment_exact_batch", "mn_score_device", "mn_exact_phase_a_device", "mn_sweep_device", "mn_sweep_time_device", "mn_segment_host", "c_run_segmentation",
            "mn_prepare_device", "mn_upsample_mask_device", "mn_rle_points_device", "mn_rle_encode_host", "mn_sameness_targets_device", "mn_instance_scores_device",
            "mn_instance_table_device", "mn_filter_instances_device",
+           "mn_overlap_table_device", "mn_match_overlaps_device",
            "mn_pack_wire_device", "mn_runs_wire_words", "mn_pack_runs_device", "mn_unpack_runs_device",
            "mn_unpack_runs_batch_device",
            "mn_segment_device_t", "mn_segment_launch_t", "mn_segment_exact_batch_t", "mn_score_device_t",
            "mn_exact_phase_a_device_t", "mn_sweep_device_t", "mn_sweep_time_device_t", "mn_prepare_device_t",
            "mn_last_status", "mn_status_string", "mn_version"]
-
 
 def load_library() -> ctypes.CDLL:
     """Load libmergenet_hip.so (built in-tree by ``__graft_entry__.build``); fail loudly."""
@@ -212,6 +214,18 @@ def load_library() -> ctypes.CDLL:
                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_void_p]
         lib.mn_filter_instances_device.restype = ctypes.c_int
+    if hasattr(lib, "mn_overlap_table_device"):          # (absent from older variant builds: MN_LIB)
+        lib.mn_overlap_table_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                ctypes.c_void_p]
+        lib.mn_overlap_table_device.restype = ctypes.c_int
+    if hasattr(lib, "mn_match_overlaps_device"):
+        lib.mn_match_overlaps_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_double,
+                                                  ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        lib.mn_match_overlaps_device.restype = ctypes.c_int
     lib.mn_pack_wire_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
                                         ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     lib.mn_pack_wire_device.restype = ctypes.c_int
@@ -883,6 +897,88 @@ class Merger:
                         "score": float(fscores[k]) if fscores is not None else 1,
                         "segmentation": {"size": rles[k]["size"], "counts": rles[k]["counts"]},
                         "bbox": [float(x0), float(y0), float(x1 - x0 + 1), float(y1 - y0 + 1)], "area": area})
+        return res
+
+    def overlap_table(self, pred, truth, num_pred: int, num_truth: int):
+        """int32 [K+1, G+1] tensor on the masks' device: entry [p][g] = number of pixels with prediction label p and
+        truth label g; a label outside its range counts as 0 (``labels.overlap_table`` is the numpy statement).  Row
+        sums are the prediction areas, column sums the truth areas.  ``truth`` is the label mask of the ground truth
+        (utils/dataset.py:486-506, what :meth:`sameness_targets` takes).  One pass over both masks on the current
+        stream; nothing is synchronised or copied.  Any image size."""
+        torch = self.torch
+        fn = self._entry("mn_overlap_table_device")
+        H, W = self._check_mask(pred)
+        if self._check_mask(truth) != (H, W) or truth.device != pred.device:
+            raise ValueError("truth: a mask of the prediction's shape on the prediction's GPU")
+        K, G = int(num_pred), int(num_truth)
+        if K < 0 or G < 0:
+            raise ValueError("num_pred and num_truth must not be negative")
+        if (K + 1) * (G + 1) > 2 ** 28:
+            raise ValueError("(num_pred + 1) * (num_truth + 1) must not exceed 2^28")
+        table = torch.empty((K + 1, G + 1), dtype=torch.int32, device=pred.device)
+        stream = torch.cuda.current_stream(pred.device).cuda_stream
+        rc = fn(self.handle, pred.data_ptr(), truth.data_ptr(), H, W, K, G, table.data_ptr(), ctypes.c_void_p(stream))
+        if rc != 0:
+            raise MergeNetError(rc)
+        return table
+
+    def match_instances(self, table, pred_classes, truth_classes, scores=None, crowd=None, thresholds=None,
+                        area_range=(0.0, 1e10), return_iou: bool = False):
+        """COCO's per-image evaluation from the overlap table (egs/cityscape/local/evaluate.py:67-73:
+        ``COCOeval.evaluateImg`` with maxDets >= K), for every IoU threshold at once.  ``table``: what
+        :meth:`overlap_table` gave, int32 [K+1, G+1]; ``pred_classes`` / ``truth_classes``: int32, at least K / G
+        entries; ``scores``: float32 [K] or None (label order); ``crowd``: uint8 or bool [G] or None;
+        ``thresholds``: None for COCO's ten (``np.linspace(0.5, 0.95, 10)``) or up to 16 values; ``area_range``: truth
+        instances outside it are ignored, as are unmatched detections outside it.  K, G <= 4096.
+        Returns a dict of tensors on the table's device: ``pred_match`` int32 [T,K] (the truth label, 0 = none),
+        ``truth_match`` int32 [T,G] (the prediction label, 0 = none), ``pred_ignore`` bool [T,K], ``truth_ignore``
+        bool [G], and ``iou`` float64 [K,G] with ``return_iou``; entry k-1 belongs to label k.
+        ``labels.match_instances`` is the numpy statement and gives the definitions.  Nothing is synchronised."""
+        torch = self.torch
+        fn = self._entry("mn_match_overlaps_device")
+        if not (table.is_cuda and table.dtype == torch.int32 and table.is_contiguous() and table.dim() == 2
+                and table.shape[0] >= 1 and table.shape[1] >= 1):
+            raise ValueError("table: the contiguous int32 [K+1, G+1] tensor of overlap_table()")
+        dev = table.device
+        K, G = int(table.shape[0]) - 1, int(table.shape[1]) - 1
+
+        def checked(x, name, dtypes, n):
+            if x is None:
+                return None
+            if not (x.is_cuda and x.dtype in dtypes and x.is_contiguous() and x.numel() >= n and x.device == dev):
+                raise ValueError("%s: a contiguous %s tensor of at least %d entries on the table's GPU"
+                                 % (name, " / ".join(str(d) for d in dtypes), n))
+            return x
+
+        checked(pred_classes, "pred_classes", (torch.int32,), K)
+        checked(truth_classes, "truth_classes", (torch.int32,), G)
+        if pred_classes is None or truth_classes is None:
+            raise ValueError("pred_classes and truth_classes are needed")
+        checked(scores, "scores", (torch.float32,), K)
+        checked(crowd, "crowd", (torch.uint8, torch.bool), G)
+        th = np.ascontiguousarray(np.linspace(0.5, 0.95, 10) if thresholds is None else
+                                  np.asarray(thresholds, np.float64).reshape(-1))
+        T = int(th.size)
+        if not 1 <= T <= 16:
+            raise ValueError("thresholds: 1 to 16 values")
+        pred_match = torch.empty((T, K), dtype=torch.int32, device=dev)
+        truth_match = torch.empty((T, G), dtype=torch.int32, device=dev)
+        pred_ignore = torch.empty((T, K), dtype=torch.uint8, device=dev)
+        truth_ignore = torch.empty((G,), dtype=torch.uint8, device=dev)
+        iou = torch.empty((K, G), dtype=torch.float64, device=dev) if return_iou else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = fn(self.handle, table.data_ptr(), K, G, pred_classes.data_ptr(),
+                scores.data_ptr() if scores is not None else None, truth_classes.data_ptr(),
+                crowd.data_ptr() if crowd is not None else None, th.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), T,
+                float(area_range[0]), float(area_range[1]), iou.data_ptr() if iou is not None else None,
+                pred_match.data_ptr(), truth_match.data_ptr(), pred_ignore.data_ptr(), truth_ignore.data_ptr(),
+                ctypes.c_void_p(stream))
+        if rc != 0:
+            raise MergeNetError(rc)
+        res = {"pred_match": pred_match, "truth_match": truth_match, "pred_ignore": pred_ignore.view(torch.bool),
+               "truth_ignore": truth_ignore.view(torch.bool)}
+        if return_iou:
+            res["iou"] = iou
         return res
 
 
