@@ -524,6 +524,52 @@ int mn_match_overlaps_device(mn_context* ctx, const int* d_table, int num_pred, 
                               double* d_iou, int* d_pred_match, int* d_truth_match,
                               unsigned char* d_pred_ignore, unsigned char* d_truth_ignore, void* stream);
 
+/* The network's maps themselves against the ground truth, on the device.  The reference scores both networks in
+ * every validation pass (runningScore and offsetIoU of utils/score.py:20-32,77-86, driven from utils/train_utils.py:
+ * 84-121,183-219 and utils/inference_utils.py:46-47,98-99): it argmaxes the class planes into a confusion matrix
+ * and, per offset, forms the soft intersection and union of "different instance" between prediction and target --
+ * after copying every plane of every image to the host, one `.cpu()` per offset, and after materialising the
+ * targets of utils/dataset.py:259-277.  Here ONE pass reads each map element once, in the layout and element types
+ * the sweep reads (`dtype`: MN_DTYPE_*, | MN_MAPS_LOGITS for logits), and looks the truth up in the label mask that
+ * mn_sameness_targets_device and mn_overlap_table_device take; no target plane is written.
+ *   p: the element widened exactly to float32; for logits 1.0f / (1.0f + expf(-x)) of that, in float32.  No clip and
+ *   no same_different_bias: this scores the network, not the merger's view of it.
+ *   Predicted class of a pixel: the LOWEST index among the greatest p over the num_classes class planes (numpy's
+ *   argmax; it is taken on p, so logits of 18, 20 and 25 -- all exactly 1.0 as float32 probabilities -- tie).
+ *   NaN in a map is undefined, as for every other entry point (the running maximum here never takes one, numpy's
+ *   argmax takes the first).
+ *   Truth class of a pixel: 0 for truth label 0, d_truth_classes[g - 1] for label g in 1..num_truth; a label outside
+ *   0..num_truth reads as 0, as in mn_overlap_table_device.  A pixel whose truth class lies outside 0..C-1 is left
+ *   out of the confusion matrix (the mask of runningScore._fast_hist: an ignore class for the caller).
+ *   d_confusion int64 [C][C], row-major: confusion[t][q] = number of the remaining pixels with truth class t and
+ *   predicted class q.
+ *   Per offset k = (di, dj): a pixel (r, c) is DIFFERENT when (r + di, c + dj) is inside the image and carries another
+ *   truth label -- the labels as they stand in the mask, the rule of mn_sameness_targets_device; a neighbour outside
+ *   the image is "same".  With d = 1.0f - p of plane k, in float32 (the reference's 1 - pred):
+ *     d_sums[0 * O + k] = sum of d over the different pixels     (the reference's intersection)
+ *     d_sums[1 * O + k] = sum of d over all pixels
+ *     d_sums[2 * O + k] = the number of different pixels
+ *   each summed in float64; the reference's union is sums[1] + sums[2] - sums[0].  d_sums is float64 [3][O].
+ * The sums of a call are bit-identical from run to run: no floating-point atomic is used, every workgroup writes its
+ * partial sums to its own slot of a buffer of the context and a second launch adds the slots in a fixed order; the
+ * grid follows (height, width, element type) only.  accumulate != 0: the counts and the image's three totals per
+ * offset are ADDED to what d_confusion / d_sums hold (one IEEE addition per total) -- the running totals of a
+ * validation loop, with no synchronisation between images; accumulate == 0: they are stored.
+ * Loads: 4 pixels per lane and 16-byte load for float32, 8 for 16-bit maps, where the width is a multiple of that
+ * and BOTH maps are 16-byte aligned; 4 per lane and 8-byte load for 16-bit maps of width % 4 == 0 aligned to 8;
+ * single elements otherwise.  The truth mask is read through the cache, offset_dim + 1 times and more.
+ * Any image size (not held to the context's capacity).  1 <= num_classes <= MN_MAX_CLASSES (class_dim >= num_classes
+ * is accepted and not used: the planes are height * width apart), 1 <= offset_dim <= MN_MAX_OFFSETS, num_truth >= 0;
+ * d_truth_classes may be NULL when num_truth == 0.  offset_list is a HOST array of (di, dj) pairs, any values, (0, 0)
+ * and duplicates included.  MN_ERR_ARGUMENT: a null pointer, a non-positive size, height * width > INT_MAX, img_width
+ * > 2^30, a count out of range, an unknown dtype; nothing is launched then.  Calls on one context share its partials buffer
+ * (allocated by the first call): keep them on one stream.  Enqueues on `stream` only: no host synchronisation. */
+int mn_map_scores_device(mn_context* ctx, const void* d_class_pred, int class_dim, const void* d_adj_pred,
+                         int offset_dim, int dtype /* MN_DTYPE_* | MN_MAPS_LOGITS */, int img_width, int img_height,
+                         int num_classes, const int* offset_list, const int* d_truth, int num_truth,
+                         const int* d_truth_classes, long long* d_confusion /* [C*C] */,
+                         double* d_sums /* [3*O] */, int accumulate, void* stream);
+
 /* Wire format of the multi-GPU mask exchange (the all-gather of final instance masks the north
  * star asks for; the reference has no exchange, its jobs write files: segment.py:59-61).  d_wire is
  * int16 [n_pixels + 1 + max_instances + 4]: the labels (0..K), K, the classes of labels 1..K

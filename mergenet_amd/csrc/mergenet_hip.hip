@@ -23,6 +23,7 @@
 #include "mn_kernels_instances.h"
 #include "mn_kernels_match.h"
 #include "mn_kernels_cc.h"
+#include "mn_kernels_mapscore.h"
 #include "mn_sweep_form.h"
 #include "mn_kernels_tail.h"
 #include "mn_kernels_exact.h"
@@ -160,6 +161,7 @@ struct mn_context {
   ImgParams last_params;  // of the most recent mn_segment_device call (for mn_instance_scores_device)
   int last_valid;
   MnMatchWork* match_work;  // scratch of mn_match_overlaps_device (mn_kernels_match.h): allocated on first use
+  double* ms_partials;      // [MN_MS_VALUES][MN_MS_WORKGROUPS] partial sums of mn_map_scores_device: allocated on first use
   // workspace of the exact engine (mn_kernels_exact.h): allocated on first use, for the largest
   // image seen so far
   struct XWork {
@@ -502,7 +504,7 @@ extern "C" void mn_destroy(mn_context* c) {
                  c->label, c->mapbuf, c->lpsum, c->lp_acc, c->ball, c->bsub, c->fin_lists, c->cc_tcount, c->cc_lcount, c->cc_bits, c->cc_roots, c->cc_negbits,
                  c->block_count, c->wire_counts, c->partial, c->statblk,
                  c->bg_key, c->gmax, c->touch, c->theta, c->progress, c->d_class, c->d_same, c->d_mask, c->d_objcls, c->d_part,
-                 c->match_work};
+                 c->match_work, c->ms_partials};
   for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); i++)
     if (dev[i]) (void)hipFree(dev[i]);
   x_free(c);
@@ -2821,6 +2823,79 @@ extern "C" int mn_match_overlaps_device(mn_context* c, const int* d_table, int n
   hipLaunchKernelGGL(mn_match_greedy, dim3(T), dim3(MN_MATCH_THREADS), 0, st, d_table, K, G,
                      (const MnMatchWork*)c->match_work, d_pred_class, d_truth_class, d_truth_crowd, th, area_lo,
                      area_hi, d_pred_match, d_truth_match, d_pred_ignore);
+  MN_HIP(hipGetLastError());
+  g_last_status = MN_OK;
+  return MN_OK;
+}
+
+// ---- the maps against the ground truth (mn_kernels_mapscore.h) ---------------------------------------
+// Enqueues only: no host synchronisation, no copy.  Nothing of the segmentation path runs here.
+template <int DT, bool LG>
+static void map_scores_launch(int v, dim3 g, hipStream_t st, const MnMapScoreArgs& A) {
+  const dim3 b(MN_MS_THREADS);
+  if (v == 8) {
+    if constexpr (DT != MN_DTYPE_F32) hipLaunchKernelGGL((mn_map_scores_pass<DT, LG, 8>), g, b, 0, st, A);
+  } else if (v == 4) {
+    hipLaunchKernelGGL((mn_map_scores_pass<DT, LG, 4>), g, b, 0, st, A);
+  } else {
+    hipLaunchKernelGGL((mn_map_scores_pass<DT, LG, 1>), g, b, 0, st, A);
+  }
+}
+
+extern "C" int mn_map_scores_device(mn_context* c, const void* d_class_pred, int class_dim, const void* d_adj_pred,
+                                    int offset_dim, int dtype, int img_width, int img_height, int num_classes,
+                                    const int* offset_list, const int* d_truth, int num_truth,
+                                    const int* d_truth_classes, long long* d_confusion, double* d_sums,
+                                    int accumulate, void* stream) {
+  const int H = img_height, W = img_width, C = num_classes, O = offset_dim, G = num_truth;
+  if (!c || !d_class_pred || !d_adj_pred || !offset_list || !d_truth || !d_confusion || !d_sums || H <= 0 || W <= 0 ||
+      C < 1 || C > MN_MAX_CLASSES || class_dim < C || O < 1 || O > MN_MAX_OFFSETS || G < 0 ||
+      (G > 0 && !d_truth_classes) || (size_t)H * (size_t)W > (size_t)INT_MAX || W > MN_MS_MAX_WIDTH ||
+      !dtype_ok(dtype, true)) {
+    g_last_status = MN_ERR_ARGUMENT;
+    return MN_ERR_ARGUMENT;
+  }
+  const int dt = dtype & 0xFF, logits = (dtype & MN_MAPS_LOGITS) ? 1 : 0;
+  MN_HIP(hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (!c->ms_partials) MN_HIP(dev_alloc(c, &c->ms_partials, (size_t)MN_MS_VALUES * MN_MS_WORKGROUPS));
+  if (!accumulate) MN_HIP(hipMemsetAsync(d_confusion, 0, (size_t)C * C * sizeof(long long), st));
+
+  MnMapScoreArgs A;
+  memset(&A, 0, sizeof(A));
+  A.cls = d_class_pred; A.same = d_adj_pred; A.truth = d_truth; A.truth_classes = d_truth_classes;
+  A.H = H; A.W = W; A.C = C; A.O = O; A.G = G;
+  A.confusion = reinterpret_cast<unsigned long long*>(d_confusion);
+  A.partials = c->ms_partials;
+  for (int k = 0; k < O; k++) {   // an offset of H rows or W columns or more leaves the image whatever its size: held
+    A.di[k] = std::max(-H, std::min(H, offset_list[2 * k]));       // to that, so that row + di and column + dj stay ints
+    A.dj[k] = std::max(-W, std::min(W, offset_list[2 * k + 1]));
+  }
+  // The grid is a function of (H, W, element type) alone: it is sized for the widest loads of the element type.
+  // Pixels per lane follow the width and BOTH maps' base addresses; fewer of them mean more chunks per wave.
+  const int elem = dt == MN_DTYPE_F32 ? 4 : 2;
+  const int widest = 16 / elem;
+  const long long nominal = (long long)H * ((W + 64 * widest - 1) / (64 * widest));
+  const long long want = (nominal + MN_MS_WAVES * MN_MS_MIN_CHUNKS - 1) / (MN_MS_WAVES * MN_MS_MIN_CHUNKS);
+  A.slots = (int)std::min<long long>(MN_MS_WORKGROUPS, want);
+  const uintptr_t bases = reinterpret_cast<uintptr_t>(d_class_pred) | reinterpret_cast<uintptr_t>(d_adj_pred);
+  int v = 1;
+  if (W % widest == 0 && (bases & 15) == 0) v = widest;
+  else if (elem == 2 && W % 4 == 0 && (bases & 7) == 0) v = 4;
+  A.chunks_per_row = (W + 64 * v - 1) / (64 * v);
+  A.total_chunks = H * A.chunks_per_row;                         // <= H * W
+  const int waves = A.slots * MN_MS_WAVES;
+  A.chunks_per_wave = (A.total_chunks + waves - 1) / waves;
+  const dim3 g((unsigned)A.slots);
+  if (dt == MN_DTYPE_F32) {
+    if (logits) map_scores_launch<MN_DTYPE_F32, true>(v, g, st, A); else map_scores_launch<MN_DTYPE_F32, false>(v, g, st, A);
+  } else if (dt == MN_DTYPE_F16) {
+    if (logits) map_scores_launch<MN_DTYPE_F16, true>(v, g, st, A); else map_scores_launch<MN_DTYPE_F16, false>(v, g, st, A);
+  } else {
+    if (logits) map_scores_launch<MN_DTYPE_BF16, true>(v, g, st, A); else map_scores_launch<MN_DTYPE_BF16, false>(v, g, st, A);
+  }
+  hipLaunchKernelGGL(mn_map_scores_finish, dim3(3 * O), dim3(64), 0, st, (const double*)c->ms_partials, A.slots,
+                     d_sums, accumulate);
   MN_HIP(hipGetLastError());
   g_last_status = MN_OK;
   return MN_OK;

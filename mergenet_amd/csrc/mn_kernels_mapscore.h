@@ -1,0 +1,265 @@
+// mn_kernels_mapscore.h -- the network's maps themselves against the ground truth, on the device: the confusion
+// matrix of the argmax class and, per offset, the soft intersection / union sums of "different instance".
+//
+// Reference work replaced (every validation pass, on the host, one plane copy per offset):
+//   runningScore.update / _fast_hist   utils/score.py:20-32     argmax of the class planes -> confusion matrix
+//   offsetIoU.update                   utils/score.py:77-86     sum((1-pred)*(1-gt)), sum(1-pred) + sum(1-gt) - that
+//   their callers                      utils/train_utils.py:84-121,183-219, utils/inference_utils.py:46-47,98-99
+//   the targets they are fed           utils/dataset.py:259-277 (mn_sameness_targets: never materialised here)
+// Definitions (mergenet_hip.h gives them in full; labels.map_scores is the numpy statement):
+//   p                = the element widened to float32 (mn_sigmoid of it for logits); no clip, no bias;
+//   predicted class  = lowest index among the greatest p over the C class planes;
+//                      (a NaN is outside the contract, as in every other pass: it is never greater, numpy takes it)
+//   truth class      = 0 for truth label 0 (and any label outside 0..G), truth_classes[g - 1] for label g;
+//                      pixels whose truth class is outside 0..C-1 are left out of the confusion matrix;
+//   per offset k     = (di, dj): a pixel is DIFFERENT when (r + di, c + dj) is inside the image and carries another
+//                      truth label (the raw labels are compared, as mn_sameness_targets does); d = 1.0f - p;
+//                      sums[0][k] = sum of d over the different pixels, sums[1][k] = sum of d over all pixels,
+//                      sums[2][k] = the number of different pixels; float64 sums.
+#pragma once
+
+#include "mn_device.h"
+#include "mn_kernels_cc.h"        // the streaming typed loaders (mn_ld_stream*_t), mn_ld_int4_unaligned
+
+#ifndef MN_MS_WORKGROUPS
+#define MN_MS_WORKGROUPS 1024     /* most workgroups of the pass = most slots of the partials buffer (4 per CU) */
+#endif
+#ifndef MN_MS_MIN_CHUNKS
+#define MN_MS_MIN_CHUNKS 2        /* a wave takes at least this many chunks before the grid grows */
+#endif
+#define MN_MS_THREADS 256
+#define MN_MS_WAVES (MN_MS_THREADS / 64)
+#define MN_MS_OG 5                /* offsets whose loads are in flight together (and whose sums a lane holds) */
+#define MN_MS_CG 4                /* class planes whose loads are in flight together */
+#define MN_MS_LDS_CLASSES 32      /* C <= this: the confusion counts of a workgroup gather in LDS (C * C ints, 4 KB
+                                     at most -- no occupancy lost); above it every count is a global atomic */
+#define MN_MS_VALUES (3 * MN_MAX_OFFSETS)
+#define MN_MS_MAX_WIDTH (1 << 30) /* widest image taken: a row's chunks are counted in ints, chunk * 64 * V + lane * V
+                                     stays below W + 512 (the entry point refuses a wider image) */
+
+struct MnMapScoreArgs {
+  const void* cls;                // [C][N]
+  const void* same;               // [O][N]
+  const int* truth;               // [N] label mask
+  const int* truth_classes;       // [G] (may be null when G == 0)
+  int H, W, C, O, G;
+  int chunks_per_row, total_chunks, chunks_per_wave, slots;
+  unsigned long long* confusion;  // [C][C], added to
+  double* partials;               // [3 * O][slots]
+  int di[MN_MAX_OFFSETS];
+  int dj[MN_MAX_OFFSETS];
+};
+
+__device__ __forceinline__ void mn_ms_count(int* sh, bool lds, unsigned long long* confusion, int key, int n) {
+  if (lds) atomicAdd(&sh[key], n);
+  else atomicAdd(confusion + key, (unsigned long long)n);
+}
+
+// V consecutive values of one plane, from element i: V = 8 one 16-byte load of 16-bit values, V = 4 one 16-byte
+// (float32) or 8-byte load, V = 1 one element.
+template <int DT, bool LG, int V>
+__device__ __forceinline__ void mn_ms_load(const void* base, size_t i, float* v) {
+  if constexpr (V == 8) {
+    mn_ld_stream8_t<DT, LG>(base, i, v);
+  } else if constexpr (V == 4) {
+    const float4 t = mn_ld_stream4_t<DT, LG>(base, i);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+    v[0] = mn_ld_stream1_t<DT, LG>(base, i);
+  }
+}
+
+// The walk of mn_overlap_table_runs: a wave takes `chunks_per_wave` consecutive chunks; a chunk is 64 * V consecutive
+// pixels of ONE row, lane l holds pixels V*l .. V*l + V-1 of it (V > 1: W % V == 0, so a lane is wholly inside the
+// row or wholly past it).  Two passes over the wave's chunks, so that every map element is loaded once:
+//   1. the class planes, MN_MS_CG in flight: the running argmax per pixel (a later plane wins only when greater:
+//      the lowest index among equals), then one count per pixel at (truth class, predicted class);
+//   2. the sameness planes in groups of MN_MS_OG offsets: per offset of the group a lane keeps its two float64 sums
+//      and its count in registers over all its chunks; the wave adds them up with a fixed butterfly of shuffles.
+// The truth mask is read through the cache: a pixel's own label once per pass and group, its neighbour once per offset.
+// Neighbour reads stay inside the neighbour's ROW of the mask: the 16-byte form only where all four columns are
+// inside 0..W-1, single reads under a column test otherwise; a neighbour row outside the image is not read at all.
+// The workgroup's sums go to its slot of the partials buffer (all 3 * O values are written by every workgroup, so
+// the buffer needs no clearing); mn_map_scores_finish adds the slots up.  No floating-point atomic anywhere.
+template <int DT, bool LG, int V>
+__global__ __launch_bounds__(MN_MS_THREADS) void mn_map_scores_pass(const MnMapScoreArgs A) {
+  __shared__ int sh_conf[MN_MS_LDS_CLASSES * MN_MS_LDS_CLASSES];
+  __shared__ double sh_part[MN_MS_WAVES][MN_MS_VALUES];
+  const int H = A.H, W = A.W, C = A.C, O = A.O, G = A.G;
+  const size_t N = (size_t)H * (size_t)W;
+  const bool lds = C <= MN_MS_LDS_CLASSES;
+  if (lds) {
+    for (int i = threadIdx.x; i < C * C; i += MN_MS_THREADS) sh_conf[i] = 0;
+    __syncthreads();
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long long wave = (long long)blockIdx.x * MN_MS_WAVES + wv;
+  const long long c0 = min(wave * (long long)A.chunks_per_wave, (long long)A.total_chunks);
+  const long long c1 = min(c0 + (long long)A.chunks_per_wave, (long long)A.total_chunks);
+
+  // ---- 1. class planes -> confusion counts ----
+  for (long long c = c0; c < c1; c++) {
+    const int y = (int)(c / A.chunks_per_row);
+    const int x = ((int)(c - (long long)y * A.chunks_per_row) * 64 + lane) * V;
+    const bool in = x < W;
+    const size_t at = (size_t)y * W + (size_t)(in ? x : 0);
+    float best[V];
+    int arg[V], key[V];
+#pragma unroll
+    for (int j = 0; j < V; j++) { best[j] = 0.0f; arg[j] = 0; key[j] = -1; }
+    if (in) {
+      for (int q0 = 0; q0 < C; q0 += MN_MS_CG) {
+        float v[MN_MS_CG][V];
+#pragma unroll
+        for (int q = 0; q < MN_MS_CG; q++)
+          if (q0 + q < C) mn_ms_load<DT, LG, V>(A.cls, (size_t)(q0 + q) * N + at, v[q]);
+#pragma unroll
+        for (int q = 0; q < MN_MS_CG; q++) {
+          if (q0 + q >= C) continue;
+#pragma unroll
+          for (int j = 0; j < V; j++)
+            if (q0 + q == 0 || v[q][j] > best[j]) { best[j] = v[q][j]; arg[j] = q0 + q; }
+        }
+      }
+      int t[V];
+      if constexpr (V >= 4) {
+#pragma unroll
+        for (int h = 0; h < V / 4; h++) {
+          const int4 u = mn_ld_int4_unaligned(A.truth + at + 4 * h);
+          t[4 * h] = u.x; t[4 * h + 1] = u.y; t[4 * h + 2] = u.z; t[4 * h + 3] = u.w;
+        }
+      } else {
+        t[0] = A.truth[at];
+      }
+#pragma unroll
+      for (int j = 0; j < V; j++) {
+        // the label is held to 1..G BEFORE it forms an address: the mask is the caller's memory
+        const int tc = ((unsigned)t[j] - 1u < (unsigned)G) ? A.truth_classes[(unsigned)t[j] - 1u] : 0;
+        key[j] = ((unsigned)tc < (unsigned)C) ? tc * C + arg[j] : -1;
+      }
+    }
+    // A chunk that lies in one (truth class, predicted class) cell -- most of an image -- is ONE count; any other
+    // chunk counts per lane, equal neighbours within the lane joined.
+    const int k0 = __shfl(key[0], 0);
+    bool same = true;
+#pragma unroll
+    for (int j = 0; j < V; j++) same = same && key[j] == k0;
+    if (__ballot(same) == ~0ull) {
+      if (lane == 0 && k0 >= 0) mn_ms_count(sh_conf, lds, A.confusion, k0, 64 * V);
+    } else {
+      int run = 0;
+#pragma unroll
+      for (int j = 0; j < V; j++) {
+        run++;
+        const int next = j + 1 < V ? key[j + 1 < V ? j + 1 : j] : -2;      // (-2: no key, the lane's last run ends)
+        if (next != key[j]) {
+          if (key[j] >= 0) mn_ms_count(sh_conf, lds, A.confusion, key[j], run);
+          run = 0;
+        }
+      }
+    }
+  }
+
+  // ---- 2. sameness planes -> the three sums per offset ----
+  for (int g0 = 0; g0 < O; g0 += MN_MS_OG) {
+    double s_diff[MN_MS_OG], s_all[MN_MS_OG];
+    int n_diff[MN_MS_OG];
+#pragma unroll
+    for (int g = 0; g < MN_MS_OG; g++) { s_diff[g] = 0.0; s_all[g] = 0.0; n_diff[g] = 0; }
+    for (long long c = c0; c < c1; c++) {
+      const int y = (int)(c / A.chunks_per_row);
+      const int x = ((int)(c - (long long)y * A.chunks_per_row) * 64 + lane) * V;
+      if (x >= W) continue;                          // (no shuffle or barrier inside this loop)
+      const size_t at = (size_t)y * W + (size_t)x;
+      float v[MN_MS_OG][V];
+#pragma unroll
+      for (int g = 0; g < MN_MS_OG; g++)
+        if (g0 + g < O) mn_ms_load<DT, LG, V>(A.same, (size_t)(g0 + g) * N + at, v[g]);
+      int t[V];
+      if constexpr (V >= 4) {
+#pragma unroll
+        for (int h = 0; h < V / 4; h++) {
+          const int4 u = mn_ld_int4_unaligned(A.truth + at + 4 * h);
+          t[4 * h] = u.x; t[4 * h + 1] = u.y; t[4 * h + 2] = u.z; t[4 * h + 3] = u.w;
+        }
+      } else {
+        t[0] = A.truth[at];
+      }
+#pragma unroll
+      for (int g = 0; g < MN_MS_OG; g++) {
+        if (g0 + g >= O) continue;
+        // row + di and column + dj in unsigned arithmetic: |di| <= H and |dj| <= W (the entry point holds them to
+        // that), so a sum below 0 wraps to 2^31 or more and fails the same test as one past the edge
+        const unsigned yy = (unsigned)y + (unsigned)A.di[g0 + g], xx = (unsigned)x + (unsigned)A.dj[g0 + g];
+        int nb[V];
+#pragma unroll
+        for (int j = 0; j < V; j++) nb[j] = t[j];    // outside the image: "same"
+        if (yy < (unsigned)H) {
+          const int* row = A.truth + (size_t)yy * W;
+          if (V >= 4 && xx < (unsigned)W && xx + V <= (unsigned)W) {
+#pragma unroll
+            for (int h = 0; h < V / 4; h++) {
+              const int4 u = mn_ld_int4_unaligned(row + xx + 4 * h);
+              nb[4 * h] = u.x; nb[4 * h + 1] = u.y; nb[4 * h + 2] = u.z; nb[4 * h + 3] = u.w;
+            }
+          } else {
+#pragma unroll
+            for (int j = 0; j < V; j++)
+              if (xx + j < (unsigned)W) nb[j] = row[xx + j];
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < V; j++) {
+          const double d = (double)(1.0f - v[g][j]);
+          const bool diff = nb[j] != t[j];
+          s_all[g] += d;
+          s_diff[g] += diff ? d : 0.0;
+          n_diff[g] += diff ? 1 : 0;
+        }
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < MN_MS_OG; g++) {
+      if (g0 + g >= O) continue;
+      double a = s_diff[g], b = s_all[g];
+      long long n = n_diff[g];
+      for (int s = 32; s > 0; s >>= 1) {             // a fixed butterfly: the same grouping on every run
+        a += __shfl_xor(a, s);
+        b += __shfl_xor(b, s);
+        n += __shfl_xor(n, s);
+      }
+      if (lane == 0) {
+        sh_part[wv][g0 + g] = a;
+        sh_part[wv][O + g0 + g] = b;
+        sh_part[wv][2 * O + g0 + g] = (double)n;     // (an integer below 2^53: exact)
+      }
+    }
+  }
+
+  __syncthreads();
+  for (int i = threadIdx.x; i < 3 * O; i += MN_MS_THREADS) {
+    double s = sh_part[0][i];
+#pragma unroll
+    for (int q = 1; q < MN_MS_WAVES; q++) s += sh_part[q][i];
+    A.partials[(size_t)i * A.slots + blockIdx.x] = s;
+  }
+  if (lds)
+    for (int i = threadIdx.x; i < C * C; i += MN_MS_THREADS) {
+      const int n = sh_conf[i];
+      if (n) atomicAdd(A.confusion + i, (unsigned long long)n);
+    }
+}
+
+// One wave per value (3 * O of them): lane l adds the slots l*per .. l*per + per-1 in ascending order, the lanes'
+// sums meet in the fixed butterfly.  The image's total is then stored, or -- accumulate -- added to what the
+// caller's buffer holds in ONE IEEE addition: the running total of a validation loop.
+__global__ __launch_bounds__(64) void mn_map_scores_finish(const double* __restrict__ partials, int slots,
+                                                            double* __restrict__ sums, int accumulate) {
+  const int lane = threadIdx.x;
+  const int per = (slots + 63) / 64;
+  const double* p = partials + (size_t)blockIdx.x * slots;
+  double s = 0.0;
+  for (int i = lane * per; i < min(slots, (lane + 1) * per); i++) s += p[i];
+  for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+  if (lane == 0) sums[blockIdx.x] = accumulate ? sums[blockIdx.x] + s : s;
+}

@@ -7,10 +7,14 @@ are therefore compared as partitions plus per-instance class.
 Also the numpy statements of the instance table and the small-instance filter (``instance_table``,
 ``filter_instances``), the checkers of ``Merger.instance_table`` / ``Merger.filter_instances``, and those of the
 comparison with the ground truth (``overlap_table``, ``instance_iou``, ``match_instances``), the checkers of
-``Merger.overlap_table`` / ``Merger.match_instances``.
+``Merger.overlap_table`` / ``Merger.match_instances``, and of the scores of the network's maps themselves
+(``map_scores``, the checker of ``Merger.map_scores``, with the reference's summaries ``class_scores`` and
+``offset_iou``).
 """
 
 from __future__ import annotations
+
+import math
 
 import numpy as np
 
@@ -278,3 +282,86 @@ def uniform_groups(pos_bits: np.ndarray, offsets) -> np.ndarray:
     full = n // 64
     flags[:full] = link[: full * 64].reshape(full, 64)[:, :63].all(axis=1)
     return flags
+
+
+# ---- the network's maps against the ground truth: the numpy statement of Merger.map_scores ----------------------
+# (what runningScore.update and offsetIoU.update of utils/score.py accumulate per image, from the label mask instead of
+# target planes; class_scores and offset_iou are their get_scores)
+
+def map_scores(class_probs, same_probs, offsets, truth, truth_classes, num_truth: int, logits: bool = False):
+    """(confusion int64 [C,C], sums float64 [3,O]) of one image.
+
+    p is the element widened exactly to float32; with ``logits`` the float32 sigmoid ``1 / (1 + exp(-x))`` of that.
+    No clip, no same_different_bias.  Predicted class: ``argmax`` of p over the C class planes (the lowest index among
+    the greatest; NaN in a map is outside the contract -- numpy takes the first NaN, the device never takes one).  Truth class: 0 for truth label 0 and for a label outside 0..num_truth, ``truth_classes[g - 1]``
+    for label g; a pixel whose truth class lies outside 0..C-1 is left out of the confusion matrix
+    (``runningScore._fast_hist``); ``confusion[t][q]`` counts the others by truth class t and predicted class q.
+    Per offset k = (di, dj) a pixel is different when (r + di, c + dj) is inside the image and carries another truth
+    label (the labels as they stand, utils/dataset.py:259-277; outside the image is "same"); with d = 1 - p in float32:
+    ``sums[0][k]`` = sum of d over the different pixels, ``sums[1][k]`` = sum of d over all pixels, ``sums[2][k]`` =
+    the number of different pixels.  The sums are float64: the correctly rounded sum of the terms (``math.fsum``),
+    which any float64 summation of these n non-negative terms meets within n * 2^-53, relative."""
+    cp = np.asarray(class_probs).astype(np.float32)
+    sp = np.asarray(same_probs).astype(np.float32)
+    if logits:
+        with np.errstate(over="ignore"):
+            one = np.float32(1.0)
+            cp = (one / (one + np.exp(-cp, dtype=np.float32))).astype(np.float32)
+            sp = (one / (one + np.exp(-sp, dtype=np.float32))).astype(np.float32)
+    C, H, W = cp.shape
+    offs = np.asarray(offsets, np.int64).reshape(-1, 2)
+    O = offs.shape[0]
+    t = np.asarray(truth).astype(np.int64)
+    if t.shape != (H, W) or sp.shape != (O, H, W):
+        raise ValueError("the maps, the offsets and the truth mask differ in size")
+    G = int(num_truth)
+    by_label = np.zeros(G + 1, np.int64)
+    if G:
+        by_label[1:] = np.asarray(truth_classes).astype(np.int64).reshape(-1)[:G]
+    tcls = by_label[np.where((t < 0) | (t > G), 0, t)]
+    pred = cp.argmax(axis=0)
+    keep = (tcls >= 0) & (tcls < C)
+    confusion = np.bincount(C * tcls[keep] + pred[keep], minlength=C * C).reshape(C, C).astype(np.int64)
+    sums = np.zeros((3, O), np.float64)
+    for k, (di, dj) in enumerate(offs.tolist()):
+        d = (np.float32(1.0) - sp[k]).astype(np.float64)
+        diff = np.zeros((H, W), bool)
+        r0, r1 = max(0, -di), min(H, H - di)
+        c0, c1 = max(0, -dj), min(W, W - dj)
+        if r0 < r1 and c0 < c1:
+            diff[r0:r1, c0:c1] = t[r0:r1, c0:c1] != t[r0 + di:r1 + di, c0 + dj:c1 + dj]
+        sums[0, k] = math.fsum(d[diff].tolist())
+        sums[1, k] = math.fsum(d.reshape(-1).tolist())
+        sums[2, k] = float(diff.sum())
+    return confusion, sums
+
+
+def class_scores(confusion):
+    """The summaries ``runningScore.get_scores`` reports (utils/score.py:34-55) from a confusion matrix whose rows are
+    the truth classes: ``({"overall_acc", "mean_acc", "freq_acc", "mean_IU"}, per-class IoU float64 [C])``.
+
+    With ``hit[c]`` the diagonal, ``truth[c]`` the row totals, ``pred[c]`` the column totals and ``n`` their total:
+    recall[c] = hit / truth, IoU[c] = hit / (truth + pred - hit); ``overall_acc`` = sum(hit) / n, ``mean_acc`` and
+    ``mean_IU`` average recall and IoU over the classes where they are defined (0 / 0 is NaN and left out),
+    ``freq_acc`` weighs the IoU of every class that occurs in the truth by its share truth / n."""
+    m = np.asarray(confusion).astype(np.float64)
+    hit, truth, pred = m.diagonal(), m.sum(axis=1), m.sum(axis=0)
+    n = truth.sum()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        recall = hit / truth
+        iou = hit / (truth + pred - hit)
+        overall = hit.sum() / n
+        share = truth / n
+        occurs = share > 0
+        summary = {"overall_acc": overall, "mean_acc": np.nanmean(recall),
+                   "freq_acc": float(np.dot(share[occurs], iou[occurs])), "mean_IU": np.nanmean(iou)}
+    return summary, iou
+
+
+def offset_iou(sums):
+    """``offsetIoU.get_scores`` (utils/score.py:93-96) of the totals: (iou float64 [O], their mean), with
+    intersection = sums[0] and union = sums[1] + sums[2] - sums[0]; 0 / 0 is NaN, as the reference leaves it."""
+    s = np.asarray(sums, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        iou = s[0] / (s[1] + s[2] - s[0])
+    return iou, iou.mean()

@@ -90,7 +90,7 @@ EXPORTS = ["mn_default_options", "mn_create", "mn_destroy", "mn_workspace_bytes"
            "mn_segment_device", "mn_segment_launch", "mn_segment_finish", "mn_segment_exact_batch", "mn_score_device", "mn_exact_phase_a_device", "mn_sweep_device", "mn_sweep_time_device", "mn_segment_host", "c_run_segmentation",
            "mn_prepare_device", "mn_upsample_mask_device", "mn_rle_points_device", "mn_rle_encode_host", "mn_sameness_targets_device", "mn_instance_scores_device",
            "mn_instance_table_device", "mn_filter_instances_device",
-           "mn_overlap_table_device", "mn_match_overlaps_device",
+           "mn_overlap_table_device", "mn_match_overlaps_device", "mn_map_scores_device",
            "mn_pack_wire_device", "mn_runs_wire_words", "mn_pack_runs_device", "mn_unpack_runs_device",
            "mn_unpack_runs_batch_device",
            "mn_segment_device_t", "mn_segment_launch_t", "mn_segment_exact_batch_t", "mn_score_device_t",
@@ -226,6 +226,12 @@ def load_library() -> ctypes.CDLL:
                                                   ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         lib.mn_match_overlaps_device.restype = ctypes.c_int
+    if hasattr(lib, "mn_map_scores_device"):             # (absent from older variant builds: MN_LIB)
+        lib.mn_map_scores_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             _i32p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        lib.mn_map_scores_device.restype = ctypes.c_int
     lib.mn_pack_wire_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
                                         ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     lib.mn_pack_wire_device.restype = ctypes.c_int
@@ -980,6 +986,53 @@ class Merger:
         if return_iou:
             res["iou"] = iou
         return res
+
+    def map_scores(self, class_probs, same_probs, offsets, truth, truth_classes, logits: bool = False, into=None):
+        """The network's maps themselves against the ground truth: what ``runningScore.update`` and
+        ``offsetIoU.update`` (utils/score.py:20-32,77-86) accumulate per image, in one pass over the maps on the
+        device -- no host copy of a plane, no target planes.  ``class_probs`` [C,H,W] and ``same_probs`` [O,H,W] as
+        for :meth:`segment` (float32, float16 or bfloat16; ``logits=True`` for logits); ``truth``: the int32 [H,W]
+        label mask of the ground truth (what :meth:`sameness_targets` and :meth:`overlap_table` take);
+        ``truth_classes``: int32, entry g-1 the class of truth label g, or None for no instances -- its length is the
+        number of truth labels.  Returns ``{"confusion": int64 [C,C], "sums": float64 [3,O]}`` on the maps' device:
+        ``confusion[t][q]`` counts the pixels of truth class t predicted q (pixels whose truth class is outside
+        0..C-1 are left out), ``sums[0]`` / ``sums[1]`` are the sums of ``1 - p`` over the pixels whose neighbour at
+        the offset carries another truth label / over all pixels, ``sums[2]`` the number of the former
+        (``labels.map_scores`` is the numpy statement and gives the definitions; ``labels.class_scores`` and
+        ``labels.offset_iou`` turn the totals into the reference's summaries).  ``into``: a previous result of the
+        same shapes, to which this image is added -- the running totals of a validation loop.  The sums of a call are
+        bit-identical from run to run.  Any image size; nothing is synchronised or copied.  The calls of one Merger
+        share a buffer of partial sums: keep them on ONE stream (a second stream needs a Merger of its own).  NaN in a
+        map is undefined, as everywhere."""
+        torch = self.torch
+        fn = self._entry("mn_map_scores_device")
+        C, H, W, O, off = self._check(class_probs, same_probs, offsets)
+        dev = class_probs.device
+        if self._check_mask(truth) != (H, W) or truth.device != dev:
+            raise ValueError("truth: a mask of the maps' height and width on the maps' GPU")
+        G = 0
+        if truth_classes is not None:
+            if not (truth_classes.is_cuda and truth_classes.dtype == torch.int32 and truth_classes.is_contiguous()
+                    and truth_classes.dim() == 1 and truth_classes.device == dev):
+                raise ValueError("truth_classes: a contiguous int32 [G] tensor on the maps' GPU, or None")
+            G = int(truth_classes.numel())
+        if into is None:
+            confusion = torch.empty((C, C), dtype=torch.int64, device=dev)
+            sums = torch.empty((3, O), dtype=torch.float64, device=dev)
+        else:
+            confusion, sums = into["confusion"], into["sums"]
+            for t, dt, shape in ((confusion, torch.int64, (C, C)), (sums, torch.float64, (3, O))):
+                if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
+                    raise ValueError("into: a previous result of map_scores for %d classes and %d offsets on the maps' GPU"
+                                     % (C, O))
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = fn(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(), O,
+                self._dtype(class_probs) | (MN_MAPS_LOGITS if logits else 0), W, H, C, off.ctypes.data_as(_i32p),
+                truth.data_ptr(), G, truth_classes.data_ptr() if G else None, confusion.data_ptr(), sums.data_ptr(),
+                1 if into is not None else 0, ctypes.c_void_p(stream))
+        if rc != 0:
+            raise MergeNetError(rc)
+        return {"confusion": confusion, "sums": sums}
 
 
 class PendingSegment:
