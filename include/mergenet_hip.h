@@ -415,6 +415,39 @@ int mn_prepare_device(mn_context* ctx, const float* d_in, int channels, int in_h
                       float* d_out, int out_height, int out_width, int apply_sigmoid, int clip,
                       void* stream);
 
+/* Class maps from a TILED semantic network, assembled on the device.  The production recipe's class maps do not
+ * come from a sigmoid network but from a Cn-class semantic network run by tile_predict (models/pspnet_caffe.py:
+ * 492-560, switched on in egs/cityscape/local/class_infer.py:58-64): overlapping tiles, each run plain and
+ * horizontally flipped, softmax, the two passes averaged, the "stuff" classes folded into one background plane by a
+ * maximum, the tiles summed into the image, divided by a per-pixel cover count and renormalised -- in numpy on the
+ * host, with a .cpu() and a .cuda() per tile.  Here ONE gather kernel reads every tile logit once and writes the C
+ * planes of the image: no atomics, no scratch buffer, no second launch.
+ *   d_tiles       [T][net_classes][tile_height][tile_width], contiguous, elements of `dtype` (MN_DTYPE_*, widened
+ *                 exactly on load): the network's LOGITS for tile t = i * num_cols + j, whose top-left pixel is
+ *                 (row_starts[i], col_starts[j]) -- the reference's loop order, rows outer
+ *   d_flip_tiles  the same shape, or NULL: the network's logits on the horizontally flipped slice, as they come
+ *                 out (not flipped back)
+ *   row_starts [num_rows], col_starts [num_cols]   HOST arrays; duplicates are legal (the reference's geometry
+ *                 gives {0, 0, 0} where the image is exactly one tile high); they travel as kernel arguments
+ *   num_classes   C, the planes written, 1 <= C <= net_classes (Cn); the first Cn - C + 1 network classes are the
+ *                 stuff classes
+ * float32 arithmetic throughout.  Per tile pixel: p1 = softmax over the Cn logits, as expf(x - max) / sum; with a
+ * flip tensor p2 the same at tile column tile_width - 1 - x and p = (p1 + p2) * 0.5f, else p = p1; q[0] = the maximum
+ * of p over the stuff classes (taken AFTER the average: not simply the probability of the greatest logit), q[k] =
+ * p[Cn - C + k] for k = 1..C-1.  Per image pixel: acc[k] = the sum of q[k] over the covering tiles in ascending t,
+ * s[k] = acc[k] / (float)count, out[k] = s[k] / (s[0] + ... + s[C-1]) summed in ascending k; with clip != 0 the
+ * merger's clip to [2^-23, 1 - 2^-23] comes last.  d_out is [C][img_height][img_width] of out_dtype, a 16-bit
+ * output being the float32 value rounded to nearest even.  NaN and +-inf logits are undefined.
+ * Any image size (not held to the context's capacity).  MN_ERR_ARGUMENT, with nothing launched: a null pointer other
+ * than d_flip_tiles, a non-positive size, num_rows or num_cols > 32, net_classes > 64, num_classes outside 1..Cn, a
+ * tile that leaves the image, a row or column of the image that no start covers, an unknown dtype, MN_MAPS_LOGITS in
+ * either dtype (the tiles are logits by definition).  Enqueues only: no host synchronisation, no copies. */
+int mn_tile_class_maps_device(mn_context* ctx, const void* d_tiles, const void* d_flip_tiles, int dtype,
+                              int net_classes, int tile_height, int tile_width,
+                              const int* row_starts, int num_rows, const int* col_starts, int num_cols,
+                              int img_height, int img_width, int num_classes,
+                              void* d_out, int out_dtype, int clip, void* stream);
+
 /* Nearest-neighbour resize of the instance mask back to the image size, cv2 INTER_NEAREST
  * coordinates (egs/cityscape/local/segment.py:146-149). */
 int mn_upsample_mask_device(mn_context* ctx, const int* d_mask, int in_height, int in_width,

@@ -24,6 +24,7 @@
 #include "mn_kernels_match.h"
 #include "mn_kernels_cc.h"
 #include "mn_kernels_mapscore.h"
+#include "mn_kernels_tiles.h"
 #include "mn_sweep_form.h"
 #include "mn_kernels_tail.h"
 #include "mn_kernels_exact.h"
@@ -2896,6 +2897,69 @@ extern "C" int mn_map_scores_device(mn_context* c, const void* d_class_pred, int
   }
   hipLaunchKernelGGL(mn_map_scores_finish, dim3(3 * O), dim3(64), 0, st, (const double*)c->ms_partials, A.slots,
                      d_sums, accumulate);
+  MN_HIP(hipGetLastError());
+  g_last_status = MN_OK;
+  return MN_OK;
+}
+
+// ---- class maps from a tiled semantic network (mn_kernels_tiles.h) -------------------------------------
+// Enqueues only: no host synchronisation, no copy, no allocation.  The geometry is checked here, on the host arrays,
+// so that the kernel never meets a pixel without a covering tile or a tile that leaves the image.
+static bool tile_axis_ok(const int* starts, int n, int side, int size) {
+  if (!starts || n < 1 || n > MN_TILES_MAX_STARTS || side <= 0 || size <= 0) return false;
+  int sorted[MN_TILES_MAX_STARTS];
+  for (int i = 0; i < n; i++) {
+    if (starts[i] < 0 || starts[i] > size - side) return false;   // the tile leaves the image (side > size: every start)
+    int k = i;
+    for (; k > 0 && sorted[k - 1] > starts[i]; k--) sorted[k] = sorted[k - 1];
+    sorted[k] = starts[i];
+  }
+  int reach = 0;                                                  // rows (columns) 0 .. reach - 1 are covered
+  for (int i = 0; i < n; i++) {
+    if (sorted[i] > reach) return false;
+    reach = std::max(reach, sorted[i] + side);
+  }
+  return reach >= size;
+}
+
+template <int DT>
+static void tile_class_maps_launch(int cn, dim3 g, hipStream_t st, const MnTileArgs& A) {
+  const dim3 b(MN_TILES_THREADS);
+  if (cn <= 8) hipLaunchKernelGGL((mn_tile_class_maps<DT, 8>), g, b, 0, st, A);
+  else if (cn <= 20) hipLaunchKernelGGL((mn_tile_class_maps<DT, 20>), g, b, 0, st, A);
+  else if (cn <= 32) hipLaunchKernelGGL((mn_tile_class_maps<DT, 32>), g, b, 0, st, A);
+  else hipLaunchKernelGGL((mn_tile_class_maps<DT, MN_TILES_MAX_CLASSES>), g, b, 0, st, A);
+}
+
+extern "C" int mn_tile_class_maps_device(mn_context* c, const void* d_tiles, const void* d_flip_tiles, int dtype,
+                                         int net_classes, int tile_height, int tile_width,
+                                         const int* row_starts, int num_rows, const int* col_starts, int num_cols,
+                                         int img_height, int img_width, int num_classes,
+                                         void* d_out, int out_dtype, int clip, void* stream) {
+  const int H = img_height, W = img_width, Cn = net_classes, C = num_classes;
+  bool ok = c && d_tiles && d_out && row_starts && col_starts && H > 0 && W > 0 && tile_height > 0 && tile_width > 0 &&
+            Cn >= 1 && Cn <= MN_TILES_MAX_CLASSES && C >= 1 && C <= Cn && dtype_ok(dtype, false) &&
+            dtype_ok(out_dtype, false);
+  ok = ok && tile_axis_ok(row_starts, num_rows, tile_height, H) && tile_axis_ok(col_starts, num_cols, tile_width, W);
+  const long long blocks_per_row = ok ? ((long long)W + MN_TILES_THREADS - 1) / MN_TILES_THREADS : 0;
+  if (!ok || blocks_per_row * (long long)H > (long long)INT_MAX) {
+    g_last_status = MN_ERR_ARGUMENT;
+    return MN_ERR_ARGUMENT;
+  }
+  MN_HIP(hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  MnTileArgs A;
+  memset(&A, 0, sizeof(A));
+  A.tiles = d_tiles; A.flip = d_flip_tiles; A.out = d_out;
+  A.Cn = Cn; A.C = C; A.th = tile_height; A.tw = tile_width; A.nr = num_rows; A.nc = num_cols; A.H = H; A.W = W;
+  A.blocks_per_row = (int)blocks_per_row;
+  A.out_dtype = out_dtype; A.clip = clip ? 1 : 0;
+  for (int i = 0; i < num_rows; i++) A.rs[i] = row_starts[i];
+  for (int j = 0; j < num_cols; j++) A.cs[j] = col_starts[j];
+  const dim3 g((unsigned)(blocks_per_row * H));
+  if (dtype == MN_DTYPE_F32) tile_class_maps_launch<MN_DTYPE_F32>(Cn, g, st, A);
+  else if (dtype == MN_DTYPE_F16) tile_class_maps_launch<MN_DTYPE_F16>(Cn, g, st, A);
+  else tile_class_maps_launch<MN_DTYPE_BF16>(Cn, g, st, A);
   MN_HIP(hipGetLastError());
   g_last_status = MN_OK;
   return MN_OK;

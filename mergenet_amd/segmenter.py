@@ -90,7 +90,7 @@ EXPORTS = ["mn_default_options", "mn_create", "mn_destroy", "mn_workspace_bytes"
            "mn_segment_device", "mn_segment_launch", "mn_segment_finish", "mn_segment_exact_batch", "mn_score_device", "mn_exact_phase_a_device", "mn_sweep_device", "mn_sweep_time_device", "mn_segment_host", "c_run_segmentation",
            "mn_prepare_device", "mn_upsample_mask_device", "mn_rle_points_device", "mn_rle_encode_host", "mn_sameness_targets_device", "mn_instance_scores_device",
            "mn_instance_table_device", "mn_filter_instances_device",
-           "mn_overlap_table_device", "mn_match_overlaps_device", "mn_map_scores_device",
+           "mn_overlap_table_device", "mn_match_overlaps_device", "mn_map_scores_device", "mn_tile_class_maps_device",
            "mn_pack_wire_device", "mn_runs_wire_words", "mn_pack_runs_device", "mn_unpack_runs_device",
            "mn_unpack_runs_batch_device",
            "mn_segment_device_t", "mn_segment_launch_t", "mn_segment_exact_batch_t", "mn_score_device_t",
@@ -232,6 +232,12 @@ def load_library() -> ctypes.CDLL:
                                              _i32p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         lib.mn_map_scores_device.restype = ctypes.c_int
+    if hasattr(lib, "mn_tile_class_maps_device"):        # (absent from older variant builds: MN_LIB)
+        lib.mn_tile_class_maps_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int,
+                                                  _i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                  ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+        lib.mn_tile_class_maps_device.restype = ctypes.c_int
     lib.mn_pack_wire_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
                                         ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     lib.mn_pack_wire_device.restype = ctypes.c_int
@@ -1033,6 +1039,53 @@ class Merger:
         if rc != 0:
             raise MergeNetError(rc)
         return {"confusion": confusion, "sums": sums}
+
+    def tile_class_maps(self, tiles, flip_tiles, row_starts, col_starts, height: int, width: int, num_classes: int,
+                        out_dtype=None, clip: bool = False):
+        """The image's class planes from the LOGITS of a semantic network run on overlapping tiles: what the
+        reference's ``tile_predict`` (models/pspnet_caffe.py:492-560) assembles in numpy on the host, in one kernel.
+        ``tiles`` [T,Cn,th,tw] (float32, float16 or bfloat16, contiguous, on the GPU): tile t = i * len(col_starts) + j
+        has its top-left pixel at (row_starts[i], col_starts[j]); ``flip_tiles``: the same shape and dtype or None,
+        the network's output on the horizontally flipped slice as it came out.  ``row_starts`` / ``col_starts``:
+        sequences of at most 32 ints (``tiles.tile_starts`` gives the reference's); duplicates are legal.  Per tile
+        pixel the softmax over the Cn classes, the two passes averaged, plane 0 = the maximum over the first
+        Cn - C + 1 classes, planes 1..C-1 = the rest; per image pixel the sum over the covering tiles, divided by
+        their number, renormalised over the C planes, then the merger's clip if ``clip`` -- float32 throughout
+        (``tiles.tile_class_maps_reference`` is the numpy statement).  Returns [C,height,width] on the tiles' device in
+        ``out_dtype`` (None: the tiles' dtype; a 16-bit output is the float32 value rounded to nearest even).  Runs
+        on the current stream; nothing is synchronised or copied.  Any image size; Cn <= 64.  A tile that leaves the
+        image or a pixel that no tile covers raises MergeNetError before anything is launched."""
+        torch = self.torch
+        fn = self._entry("mn_tile_class_maps_device")
+        if not (tiles.is_cuda and tiles.is_contiguous() and tiles.dim() == 4):
+            raise ValueError("tiles: a contiguous %s [T,Cn,th,tw] tensor on the GPU" % self.DTYPE_NAMES)
+        if tiles.device.index != self.device:
+            raise ValueError("tiles live on %s, this Merger on GPU %d" % (tiles.device, self.device))
+        code = self._dtype(tiles)
+        if flip_tiles is not None and not (flip_tiles.is_cuda and flip_tiles.is_contiguous() and
+                                           flip_tiles.shape == tiles.shape and flip_tiles.dtype == tiles.dtype and
+                                           flip_tiles.device == tiles.device):
+            raise ValueError("flip_tiles: a contiguous tensor of the shape, dtype and device of tiles, or None")
+        out_dtype = tiles.dtype if out_dtype is None else out_dtype
+        out_code = {torch.float32: MN_DTYPE_F32, torch.float16: MN_DTYPE_F16, torch.bfloat16: MN_DTYPE_BF16}.get(out_dtype)
+        if out_code is None:
+            raise ValueError("out_dtype: %s, got %s" % (self.DTYPE_NAMES, out_dtype))
+        rows = np.ascontiguousarray(np.asarray(list(row_starts), dtype=np.int32).reshape(-1))
+        cols = np.ascontiguousarray(np.asarray(list(col_starts), dtype=np.int32).reshape(-1))
+        T, Cn, th, tw = (int(v) for v in tiles.shape)
+        if T != len(rows) * len(cols):
+            raise ValueError("%d tiles for %d x %d starts" % (T, len(rows), len(cols)))
+        H, W, C = int(height), int(width), int(num_classes)
+        if H <= 0 or W <= 0 or C <= 0:
+            raise MergeNetError(-1)
+        out = torch.empty((C, H, W), dtype=out_dtype, device=tiles.device)
+        stream = torch.cuda.current_stream(tiles.device).cuda_stream
+        rc = fn(self.handle, tiles.data_ptr(), flip_tiles.data_ptr() if flip_tiles is not None else None, code,
+                Cn, th, tw, rows.ctypes.data_as(_i32p), len(rows), cols.ctypes.data_as(_i32p), len(cols),
+                H, W, C, out.data_ptr(), out_code, int(bool(clip)), ctypes.c_void_p(stream))
+        if rc != 0:
+            raise MergeNetError(rc)
+        return out
 
 
 class PendingSegment:
