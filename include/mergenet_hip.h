@@ -472,6 +472,43 @@ long long mn_rle_encode_host(const int* points, int capacity, int n, int height,
                              int num_instances, unsigned char* out, long long out_capacity,
                              long long* offsets, int* areas);
 
+/* The decoding half of the RLE path: COCO run-length encodings back into ONE int32 label mask, what anns_to_mask
+ * and anns_to_mask_class build on the host (utils/dataset.py:486-522: one maskUtils.decode per annotation, painted
+ * in list order with mask = m * (mask == 0) + mask) and what mn_overlap_table_device, mn_map_scores_device and
+ * mn_sameness_targets_device take as the ground truth.  mergenet_amd/rle.py::label_mask is the numpy statement.
+ *
+ * mn_rle_counts_host (HOST, needs no GPU): unpacks pycocotools' compressed counts string -- 5-bit groups, low
+ * group first, 0x20 = more groups follow, 0x10 of the last group = sign, offset 48; from the fourth count on the
+ * value is the difference to the count two places earlier.  Writes counts[0 .. min(n, capacity)) and returns n,
+ * the number of counts in the string (nothing is written past `capacity`); *total (may be NULL) = their sum.
+ * Negative returns: MN_ERR_ARGUMENT for a string that ends inside a group, a byte outside '0'..'o' or a count that
+ * comes out negative; MN_ERR_CAPACITY for a count that does not fit 31 bits. */
+long long mn_rle_counts_host(const unsigned char* s, long long len, unsigned* counts, long long capacity,
+                             long long* total);
+
+/* mn_rle_decode_device: all pointers are device memory.
+ *   d_counts   uint32 [num_counts]: the counts of all annotations, concatenated; the counts of one annotation are
+ *              the lengths of alternating runs of its binary mask in COLUMN-major order, the first run zeros;
+ *   d_starts   int32 [A + 1], CSR: annotation a owns d_counts[d_starts[a] .. d_starts[a + 1]);
+ *   d_values   int32 [A] or NULL: annotation a paints d_values[a], or a + 1; the value 0 paints nothing;
+ *   d_mask     int32 [height][width], row-major, written completely (zeros included: it needs no clearing):
+ *              a pixel holds the value of the first annotation in list order with a nonzero value that covers it;
+ *   d_area     int32 [A] or NULL: the sum of a's odd-indexed counts (maskUtils.area), visible or not;
+ *   scratch of the call, the caller's: d_scratch_ends uint32 [num_counts] (4 bytes per count) and
+ *              d_scratch_records int32 [A][MN_RLE_RECORD_INTS] (16 bytes per annotation, 16-byte aligned).
+ * Zero-length runs are legal anywhere.  The counts of an annotation should sum to height * width; whatever they
+ * hold, every run end is clamped to height * width and no scan position forms an address (a d_starts entry is
+ * held to 0..num_counts), and every loop is bounded by num_counts.  Two launches (one when A == 0, which writes
+ * zeros); integer work only, bit-identical from run to run.  Any image size with height * width < 2^31 (not held
+ * to the context's capacity); A <= MN_RLE_MAX_ANNOTATIONS (the reference's mask is uint16).  MN_ERR_ARGUMENT: a
+ * null pointer that is needed, a non-positive size, a negative count, A above the limit.
+ * Enqueues only: no allocation, no copy, no host synchronisation. */
+#define MN_RLE_MAX_ANNOTATIONS 65535
+#define MN_RLE_RECORD_INTS 4
+int mn_rle_decode_device(mn_context* ctx, const unsigned* d_counts, const int* d_starts, int num_annotations,
+                         int num_counts, const int* d_values, int height, int width, unsigned* d_scratch_ends,
+                         int* d_scratch_records, int* d_mask, int* d_area, void* stream);
+
 /* Sameness targets of an instance mask: out[k][r][c] = (mask[r+di][c+dj] == mask[r][c]), 1 outside
  * the image (utils/dataset.py:259-277).  d_out is float32 [offset_dim][H][W]. */
 int mn_sameness_targets_device(mn_context* ctx, const int* d_mask, int height, int width,

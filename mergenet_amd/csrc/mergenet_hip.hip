@@ -24,6 +24,7 @@
 #include "mn_kernels_match.h"
 #include "mn_kernels_cc.h"
 #include "mn_kernels_mapscore.h"
+#include "mn_kernels_rle.h"
 #include "mn_kernels_tiles.h"
 #include "mn_sweep_form.h"
 #include "mn_kernels_tail.h"
@@ -3117,4 +3118,66 @@ extern "C" long long mn_rle_encode_host(const int* points, int capacity, int n, 
   free(first);
   free(buf);
   return w;
+}
+
+// ---- COCO RLE back into a label mask (mn_kernels_rle.h; the decoding half of the RLE path) -----------------
+// Host: pycocotools' compressed counts string -> counts (native twin of mergenet_amd/rle.py::string_to_counts).
+extern "C" long long mn_rle_counts_host(const unsigned char* s, long long len, unsigned* counts, long long capacity,
+                                        long long* total) {
+  if ((!s && len > 0) || len < 0 || capacity < 0 || (!counts && capacity > 0)) return MN_ERR_ARGUMENT;
+  long long n = 0, sum = 0, p = 0;
+  long long back1 = 0, back2 = 0;               // the counts one and two places back
+  while (p < len) {
+    unsigned long long bits = 0;
+    int k = 0;
+    bool more = true;
+    while (more) {
+      if (p >= len) return MN_ERR_ARGUMENT;      // the string ends inside a group
+      const int ch = (int)s[p++] - 48;
+      if (ch < 0 || ch > 63) return MN_ERR_ARGUMENT;
+      if (k >= 12) return MN_ERR_CAPACITY;       // more than 60 bits: no count of 31 bits is written so
+      bits |= (unsigned long long)(ch & 0x1F) << (5 * k);
+      more = (ch & 0x20) != 0;
+      k++;
+      if (!more && (ch & 0x10)) bits |= ~0ull << (5 * k);
+    }
+    long long x = (long long)bits;
+    if (n > 2) x += back2;
+    if (x < 0) return MN_ERR_ARGUMENT;
+    if (x > 0x7fffffffLL) return MN_ERR_CAPACITY;
+    if (n < capacity) counts[n] = (unsigned)x;
+    n++;
+    sum += x;
+    back2 = back1;
+    back1 = x;
+  }
+  if (total) *total = sum;
+  return n;
+}
+
+// Enqueues only: no allocation, no copy, no host synchronisation.  Not held to the context's capacity.
+extern "C" int mn_rle_decode_device(mn_context* c, const unsigned* d_counts, const int* d_starts, int num_annotations,
+                                    int num_counts, const int* d_values, int height, int width,
+                                    unsigned* d_scratch_ends, int* d_scratch_records, int* d_mask, int* d_area,
+                                    void* stream) {
+  const int A = num_annotations;
+  if (!c || !d_mask || height <= 0 || width <= 0 || (size_t)height * (size_t)width > (size_t)INT_MAX ||
+      A < 0 || A > MN_RLE_MAX_ANNOTATIONS || num_counts < 0 ||
+      (A > 0 && (!d_starts || !d_scratch_records)) || (num_counts > 0 && (!d_counts || !d_scratch_ends))) {
+    g_last_status = MN_ERR_ARGUMENT;
+    return MN_ERR_ARGUMENT;
+  }
+  static_assert(sizeof(MnRleRecord) == MN_RLE_RECORD_INTS * sizeof(int), "the record size the header states");
+  MN_HIP(hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  MnRleRecord* rec = reinterpret_cast<MnRleRecord*>(d_scratch_records);
+  if (A > 0)
+    hipLaunchKernelGGL(mn_rle_scan, dim3(A), dim3(MN_RLE_SCAN_THREADS), 0, st, d_counts, d_starts, num_counts,
+                       (unsigned)(height * width), d_scratch_ends, rec, d_area);
+  hipLaunchKernelGGL(mn_rle_paint, dim3(grid_for(width, MN_RLE_TILE_COLS), grid_for(height, 64)),
+                     dim3(MN_RLE_PAINT_THREADS), 0, st, (const unsigned*)d_scratch_ends, (const MnRleRecord*)rec,
+                     d_values, A, height, width, d_mask);
+  MN_HIP(hipGetLastError());
+  g_last_status = MN_OK;
+  return MN_OK;
 }

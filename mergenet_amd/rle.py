@@ -12,9 +12,11 @@ offset by 48 into printable ASCII.
 
 from __future__ import annotations
 
-from typing import List
+from typing import List, Optional
 
 import numpy as np
+
+MAX_ANNOTATIONS = 65535      # the reference's label mask is uint16 (utils/dataset.py:486-506)
 
 
 def counts_to_string(counts) -> bytes:
@@ -109,3 +111,64 @@ def from_change_points(pos, prev, cur, H: int, W: int, num_instances: int):
             counts.append(N - last)
         results.append({"size": [H, W], "counts": counts_to_string(counts)})
     return results
+
+
+def item_counts(item, height: int, width: int, parse=string_to_counts):
+    """The counts of one item of an RLE list: a dict ``{"size": [H, W], "counts": ...}``, a bare compressed counts
+    string (``bytes`` or ``str``) or a list of integer counts (COCO's "uncompressed RLE").  ``parse`` turns a
+    ``bytes`` string into counts.  ValueError for a ``size`` other than ``[height, width]``."""
+    if isinstance(item, dict):
+        size = item.get("size")
+        if size is None or [int(v) for v in size] != [int(height), int(width)]:
+            raise ValueError("an RLE of size %r in a mask of %d x %d" % (size, height, width))
+        item = item["counts"]
+    if isinstance(item, str):
+        item = item.encode("ascii")
+    if isinstance(item, (bytes, bytearray, memoryview)):
+        return parse(bytes(item))
+    return item
+
+
+def checked_values(values, num: int) -> Optional[np.ndarray]:
+    """``values`` of :func:`label_mask` as int32 [num], or None; ValueError for a wrong length or a negative value."""
+    if num > MAX_ANNOTATIONS:
+        raise ValueError("%d annotations: at most %d" % (num, MAX_ANNOTATIONS))
+    if values is None:
+        return None
+    v = np.asarray(values, dtype=np.int64).reshape(-1)
+    if v.size != num:
+        raise ValueError("%d values for %d annotations" % (v.size, num))
+    if v.size and (v.min() < 0 or v.max() > 2 ** 31 - 1):
+        raise ValueError("values must lie in 0 .. 2^31 - 1")
+    return v.astype(np.int32)
+
+
+def label_mask(rles, height: int, width: int, values=None, return_area: bool = False):
+    """The label mask of a list of COCO run-length encodings: what ``anns_to_mask`` (utils/dataset.py:486-506)
+    builds -- one ``maskUtils.decode`` per annotation, painted in list order with ``mask = m * (mask == 0) + mask``,
+    so the FIRST annotation to cover a pixel keeps it -- and, with ``values`` set to class ids,
+    ``anns_to_mask_class`` (dataset.py:511-522).  The numpy statement of ``Merger.decode_rle``.
+
+    ``rles``: a sequence of items as :func:`item_counts` takes them.  Annotation ``i`` (0-based) paints
+    ``values[i]``, or ``i + 1`` without ``values``; the value 0 paints nothing (the reference's arithmetic).
+    Zero-length runs are legal anywhere.  Returns int32 [H, W], row-major (the RLE scan is column-major); with
+    ``return_area`` also int32 [A], the sum of each annotation's odd-indexed counts (``maskUtils.area``), whether
+    or not its pixels stay visible.  ValueError: a ``size`` other than ``[height, width]``, counts that are negative
+    or do not sum to ``height * width``, a negative value, ``len(values) != len(rles)``, more than 65535
+    annotations."""
+    H, W = int(height), int(width)
+    rles = list(rles)
+    vals = checked_values(values, len(rles))
+    mask = np.zeros((H, W), np.int32)
+    area = np.zeros(len(rles), np.int32)
+    for i, item in enumerate(rles):
+        counts = [int(c) for c in item_counts(item, H, W)]
+        if any(c < 0 for c in counts):
+            raise ValueError("annotation %d: a negative count" % i)
+        if sum(counts) != H * W:
+            raise ValueError("annotation %d: counts sum to %d, not %d" % (i, sum(counts), H * W))
+        area[i] = sum(counts[1::2])
+        v = int(vals[i]) if vals is not None else i + 1
+        m = decode(counts, H, W)
+        mask = np.where((mask == 0) & (m != 0), np.int32(v), mask)
+    return (mask, area) if return_area else mask

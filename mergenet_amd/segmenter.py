@@ -24,6 +24,8 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import rle as rle_mod
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MN_LIB") or os.path.join(_HERE, "libmergenet_hip.so")   # MN_LIB: a variant build (tuning only)
 
@@ -88,7 +90,7 @@ _lib_handle = None
 
 EXPORTS = ["mn_default_options", "mn_create", "mn_destroy", "mn_workspace_bytes",
            "mn_segment_device", "mn_segment_launch", "mn_segment_finish", "mn_segment_exact_batch", "mn_score_device", "mn_exact_phase_a_device", "mn_sweep_device", "mn_sweep_time_device", "mn_segment_host", "c_run_segmentation",
-           "mn_prepare_device", "mn_upsample_mask_device", "mn_rle_points_device", "mn_rle_encode_host", "mn_sameness_targets_device", "mn_instance_scores_device",
+           "mn_prepare_device", "mn_upsample_mask_device", "mn_rle_points_device", "mn_rle_encode_host", "mn_rle_counts_host", "mn_rle_decode_device", "mn_sameness_targets_device", "mn_instance_scores_device",
            "mn_instance_table_device", "mn_filter_instances_device",
            "mn_overlap_table_device", "mn_match_overlaps_device", "mn_map_scores_device", "mn_tile_class_maps_device",
            "mn_pack_wire_device", "mn_runs_wire_words", "mn_pack_runs_device", "mn_unpack_runs_device",
@@ -197,6 +199,15 @@ def load_library() -> ctypes.CDLL:
                                        ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong,
                                        ctypes.POINTER(ctypes.c_longlong), _i32p]
     lib.mn_rle_encode_host.restype = ctypes.c_longlong
+    if hasattr(lib, "mn_rle_counts_host"):               # (absent from older variant builds: MN_LIB)
+        lib.mn_rle_counts_host.argtypes = [ctypes.c_char_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong,
+                                           ctypes.POINTER(ctypes.c_longlong)]
+        lib.mn_rle_counts_host.restype = ctypes.c_longlong
+        lib.mn_rle_decode_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p]
+        lib.mn_rle_decode_device.restype = ctypes.c_int
     lib.mn_sameness_targets_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                ctypes.c_int, _i32p, ctypes.c_int, ctypes.c_void_p,
                                                ctypes.c_void_p]
@@ -784,6 +795,84 @@ class Merger:
                         "label": k})
         return res
 
+
+    def decode_rle(self, rles, height: int, width: int, values=None, return_area: bool = False):
+        """The int32 [H,W] label mask of a list of COCO run-length encodings, built on this GPU: what
+        ``anns_to_mask`` (utils/dataset.py:486-506) builds on the host -- annotations painted in list order, the
+        first to cover a pixel keeps it -- and what :meth:`overlap_table`, :meth:`map_scores` and
+        :meth:`sameness_targets` take as the ground truth; ``rle.label_mask`` is the numpy statement.
+
+        ``rles``: a sequence whose items are dicts ``{"size": [H, W], "counts": ...}`` (what :meth:`encode_rle` and
+        :meth:`coco_results` write), bare compressed counts strings (``bytes`` or ``str``) or lists of integer
+        counts.  Annotation ``i`` paints ``values[i]`` (``i + 1`` without ``values``; class ids give
+        ``anns_to_mask_class``, dataset.py:511-522); the value 0 paints nothing.  Polygon annotations are not taken:
+        convert them to RLE once on the host, as the reference's ``ann_to_rle`` does (dataset.py:525-542).
+        With ``return_area`` also int32 [A] on the GPU: the sum of each annotation's odd-indexed counts
+        (``maskUtils.area``), hidden or not.
+
+        The strings are unpacked natively (``mn_rle_counts_host``); counts, starts and values travel with one small
+        copy each on the current stream, the scratch stays on the Merger, nothing is synchronised.  ValueError,
+        before anything is launched: an item whose ``size`` is not ``[height, width]``, counts that are negative or
+        do not sum to ``height * width``, a malformed string, a negative value, ``len(values) != len(rles)``, more
+        than 65535 annotations."""
+        torch = self.torch
+        fn = self._entry("mn_rle_decode_device")
+        parse = self._entry("mn_rle_counts_host")
+        H, W = int(height), int(width)
+        if H <= 0 or W <= 0 or H * W >= 2 ** 31:
+            raise ValueError("height and width must be positive, height * width below 2^31")
+        rles = list(rles)
+        A = len(rles)
+        vals = rle_mod.checked_values(values, A)
+        items = [rle_mod.item_counts(item, H, W, parse=lambda b: b) for item in rles]
+        room = 0
+        for i, it in enumerate(items):
+            if not isinstance(it, bytes):
+                it = items[i] = np.asarray(it, dtype=np.int64).reshape(-1)
+                if it.size and (it.min() < 0 or it.max() > 2 ** 31 - 1):
+                    raise ValueError("annotation %d: counts must lie in 0 .. 2^31 - 1" % i)
+            room += len(it)                                   # (a count takes at least one byte of a string)
+        if room >= 2 ** 31:
+            raise ValueError("too many counts")
+        counts = np.empty(max(1, room), np.uint32)
+        starts = np.zeros(A + 1, np.int32)
+        total = ctypes.c_longlong(0)
+        at = 0
+        for i, it in enumerate(items):
+            if isinstance(it, bytes):
+                n = parse(it, len(it), counts[at:].ctypes.data, room - at, ctypes.byref(total))
+                if n < 0:
+                    raise ValueError("annotation %d: a malformed counts string (%s)" %
+                                     (i, "a count beyond 31 bits" if n == -4 else
+                                      "it ends inside a group or holds a negative count"))
+                n, sum_i = int(n), int(total.value)
+            else:
+                n = int(it.size)
+                counts[at:at + n] = it
+                sum_i = int(it.sum())
+            if sum_i != H * W:
+                raise ValueError("annotation %d: counts sum to %d, not %d" % (i, sum_i, H * W))
+            at += n
+            starts[i + 1] = at
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            d_counts = torch.from_numpy(counts[:max(1, at)].view(np.int32)).to(dev, non_blocking=True)
+            d_starts = torch.from_numpy(starts).to(dev, non_blocking=True)
+            d_values = torch.from_numpy(vals).to(dev, non_blocking=True) if vals is not None and A else None
+            if getattr(self, "_rld_ends", None) is None or self._rld_ends.numel() < at:
+                self._rld_ends = torch.empty((max(1024, at),), dtype=torch.int32, device=dev)
+            if getattr(self, "_rld_rec", None) is None or self._rld_rec.shape[0] < A:
+                self._rld_rec = torch.empty((max(64, A), 4), dtype=torch.int32, device=dev)
+            mask = torch.empty((H, W), dtype=torch.int32, device=dev)
+            area = torch.empty((A,), dtype=torch.int32, device=dev) if return_area else None
+            rc = fn(self.handle, d_counts.data_ptr(), d_starts.data_ptr(), A, at,
+                    d_values.data_ptr() if d_values is not None else None, H, W, self._rld_ends.data_ptr(),
+                    self._rld_rec.data_ptr(), mask.data_ptr(), area.data_ptr() if area is not None and A else None,
+                    ctypes.c_void_p(stream))
+        if rc != 0:
+            raise MergeNetError(rc)
+        return (mask, area) if return_area else mask
 
     def sameness_targets(self, mask, offsets):
         """Instance mask int32 [H,W] -> float32 [O,H,W] sameness targets (utils/dataset.py:259-277)."""
