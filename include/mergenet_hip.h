@@ -552,7 +552,8 @@ int mn_filter_instances_device(mn_context* ctx, const int* d_mask, int height, i
  * results to COCOeval (egs/cityscape/local/evaluate.py:67-73), which computes per image the IoU of every detection
  * with every ground-truth instance and matches greedily once per IoU threshold; the ground truth is the label mask
  * anns_to_mask builds (utils/dataset.py:486-506), what mn_sameness_targets_device takes.  The two calls below are
- * that per-image part; accumulate, summarize and the annotation files stay on the host.
+ * that per-image part; the mn_eval_* calls behind them are the dataset-level part (accumulate); the annotation
+ * files stay on the host, and summarize is a few means of the accumulated arrays, taken there too.
  *
  * mn_overlap_table_device: d_table int32 [num_pred + 1][num_truth + 1], row-major; table[p][g] = number of pixels
  * with prediction label p and truth label g (p in 0..K, g in 0..G).  A label outside its range (negative, above K
@@ -593,6 +594,62 @@ int mn_match_overlaps_device(mn_context* ctx, const int* d_table, int num_pred, 
                               double area_lo, double area_hi,
                               double* d_iou, int* d_pred_match, int* d_truth_match,
                               unsigned char* d_pred_ignore, unsigned char* d_truth_ignore, void* stream);
+
+/* The dataset-level half: COCOeval.accumulate over a log of detections that lives on the device.  The caller owns
+ * the log -- num_records records of MN_EVAL_RECORD_BYTES, 16-byte aligned -- and its fill: an append of an image
+ * writes exactly num_pred records, so the host knows where the next image goes without asking the device.  There is
+ * no cursor on the device, no overflow state, and nothing here synchronises.  The contract is pinned to the numpy
+ * statement (labels.eval_records, labels.coco_accumulate) and hand-computed cases; pycocotools is not a dependency.
+ *
+ * A record (eight 32-bit words): class, score (float32 bits; 1.0 without scores), rank, image ordinal, then two
+ * 64-bit words, low half first: matched and ignored, bit a * T + t for area range a and threshold t.
+ *
+ * mn_eval_append_device, one image; the inputs are those of mn_match_overlaps_device:
+ *   1. detection order: descending score, equal scores in ascending label, a NaN score last; label order without
+ *      scores.  rank[d] = number of detections of d's class before d in that order.
+ *   2. a detection with rank >= max_det (the largest maxDets) takes no part in the matching: it matches nothing and
+ *      holds no truth instance (COCOeval cuts to dt[:maxDet] per image and category before it matches).
+ *   3. per area range a (area_ranges: HOST array of num_areas {lo, hi} pairs, 1..MN_EVAL_MAX_AREAS): the matching of
+ *      mn_match_overlaps_device over the remaining detections, truth_ignore_a[j] = crowd[j] || area_g[j] outside
+ *      range a; a detection without a match -- those of 2 included -- is ignored iff its own area is outside range a.
+ *   4. d_records receives num_pred records in detection order; a class outside 0..num_classes-1 (the library's -1
+ *      included) is recorded as it is and never selected.
+ *   5. d_npig (int64 [num_classes][num_areas], a running total the caller zeroes once): += the number of truth
+ *      instances of each class in 0..num_classes-1 that range a does not ignore.
+ *   num_thresholds * num_areas <= 64; K, G <= MN_MATCH_MAX_INSTANCES (MN_ERR_CAPACITY); K == 0 and G == 0 are legal.
+ *   Shares the context's scratch with mn_match_overlaps_device: one stream for all of them.  Enqueues only.
+ *
+ * mn_eval_keys_device: d_keys int64 [num_records], class << 32 | a 32-bit key that ascends as the score DESCENDS,
+ *   NaN last, equal scores equal keys; classes outside 0..num_classes-1 read as num_classes.  A STABLE ascending
+ *   sort of the keys (any; the Python side takes torch's) gives d_sorted_keys and d_sorted_index (int64, the
+ *   permutation) for:
+ * mn_eval_accumulate_device: for every class k, range a, max_dets[m] (HOST array, 1..MN_EVAL_MAX_DETS ascending
+ *   positive values) and threshold t, over the records of class k with rank < max_dets[m] in sorted order (nd of them):
+ *     tp = cumsum(matched & ~ignored), fp = cumsum(~matched & ~ignored), rc = tp / npig[k][a],
+ *     pr = tp / (fp + tp + DBL_EPSILON), pr[i] = max(pr[i:]); per recall threshold r (d_rec_thresholds: DEVICE
+ *     float64 [R], compared as they are) pi = first i with rc[i] >= threshold: precision[t][r][k][a][m] = pr[pi],
+ *     scores[...] = score[pi] if there is one, else both 0; recall[t][k][a][m] = rc[nd-1], 0 if nd == 0; where
+ *     npig[k][a] == 0 every entry of (k, a) is -1.  All float64, each division ONE IEEE division of exact integers.
+ *   Every entry of the three arrays is written exactly once per call.  num_records == 0 is legal (the three sorted
+ *   pointers may then be NULL).  Enqueues only; the sort between the two calls is the caller's. */
+#define MN_EVAL_RECORD_BYTES 32
+#define MN_EVAL_MAX_AREAS 4
+#define MN_EVAL_MAX_DETS 4
+#define MN_EVAL_CHUNK 256          /* records the accumulate pass scans per step (tests place segment lengths around it) */
+int mn_eval_append_device(mn_context* ctx, const int* d_table, int num_pred, int num_truth,
+                          const int* d_pred_class, const float* d_pred_score,
+                          const int* d_truth_class, const unsigned char* d_truth_crowd,
+                          const double* thresholds, int num_thresholds,
+                          const double* area_ranges, int num_areas, int max_det, int num_classes,
+                          int image, void* d_records, long long* d_npig, void* stream);
+int mn_eval_keys_device(mn_context* ctx, const void* d_records, long long num_records, int num_classes,
+                        long long* d_keys, void* stream);
+int mn_eval_accumulate_device(mn_context* ctx, const void* d_records, long long num_records,
+                              const long long* d_sorted_keys, const long long* d_sorted_index,
+                              const long long* d_npig, int num_classes, int num_thresholds,
+                              const double* d_rec_thresholds, int num_rec_thresholds, int num_areas,
+                              const int* max_dets, int num_max_dets,
+                              double* d_precision, double* d_recall, double* d_scores, void* stream);
 
 /* The network's maps themselves against the ground truth, on the device.  The reference scores both networks in
  * every validation pass (runningScore and offsetIoU of utils/score.py:20-32,77-86, driven from utils/train_utils.py:

@@ -22,6 +22,7 @@
 #include "mn_kernels_prepare.h"
 #include "mn_kernels_instances.h"
 #include "mn_kernels_match.h"
+#include "mn_kernels_eval.h"
 #include "mn_kernels_cc.h"
 #include "mn_kernels_mapscore.h"
 #include "mn_kernels_rle.h"
@@ -163,6 +164,7 @@ struct mn_context {
   ImgParams last_params;  // of the most recent mn_segment_device call (for mn_instance_scores_device)
   int last_valid;
   MnMatchWork* match_work;  // scratch of mn_match_overlaps_device (mn_kernels_match.h): allocated on first use
+  MnEvalWork* eval_work;    // scratch of mn_eval_append_device (mn_kernels_eval.h): allocated on first use
   double* ms_partials;      // [MN_MS_VALUES][MN_MS_WORKGROUPS] partial sums of mn_map_scores_device: allocated on first use
   // workspace of the exact engine (mn_kernels_exact.h): allocated on first use, for the largest
   // image seen so far
@@ -506,7 +508,7 @@ extern "C" void mn_destroy(mn_context* c) {
                  c->label, c->mapbuf, c->lpsum, c->lp_acc, c->ball, c->bsub, c->fin_lists, c->cc_tcount, c->cc_lcount, c->cc_bits, c->cc_roots, c->cc_negbits,
                  c->block_count, c->wire_counts, c->partial, c->statblk,
                  c->bg_key, c->gmax, c->touch, c->theta, c->progress, c->d_class, c->d_same, c->d_mask, c->d_objcls, c->d_part,
-                 c->match_work, c->ms_partials};
+                 c->match_work, c->eval_work, c->ms_partials};
   for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); i++)
     if (dev[i]) (void)hipFree(dev[i]);
   x_free(c);
@@ -2782,6 +2784,32 @@ extern "C" int mn_overlap_table_device(mn_context* c, const int* d_pred, const i
   return MN_OK;
 }
 
+static MnThresholds match_thresholds(const double* thresholds, int T) {
+  MnThresholds th;
+  for (int i = 0; i < 16; i++) th.t[i] = thresholds[i < T ? i : T - 1];
+  return th;
+}
+
+// The launches of one matching, K > 0 and G > 0, on the context's scratch (allocated by the caller).  `ordered`: the
+// caller has written the scratch's order_p itself (mn_eval_append_device: its order passes over some detections).
+static void match_launch(mn_context* c, hipStream_t st, const int* d_table, int K, int G, const int* d_pred_class,
+                         const float* d_pred_score, const int* d_truth_class, const unsigned char* d_truth_crowd,
+                         const MnThresholds& th, int T, double area_lo, double area_hi, double* d_iou,
+                         int* d_pred_match, int* d_truth_match, unsigned char* d_pred_ignore,
+                         unsigned char* d_truth_ignore, bool ordered) {
+  hipLaunchKernelGGL(mn_match_areas, dim3((unsigned)((K + 3) / 4 + (G + 63) / 64)), dim3(MN_MATCH_THREADS), 0, st,
+                     d_table, K, G, d_truth_crowd, area_lo, area_hi, c->match_work, d_truth_ignore);
+  if (!ordered)
+    hipLaunchKernelGGL(mn_match_rank, dim3(grid_for(K, MN_MATCH_THREADS)), dim3(MN_MATCH_THREADS), 0, st, K,
+                       d_pred_score, c->match_work);
+  if (d_iou)
+    hipLaunchKernelGGL(mn_match_iou, dim3(grid_for((size_t)K * G, MN_MATCH_THREADS)), dim3(MN_MATCH_THREADS), 0, st,
+                       d_table, K, G, d_truth_crowd, (const MnMatchWork*)c->match_work, d_iou);
+  hipLaunchKernelGGL(mn_match_greedy, dim3(T), dim3(MN_MATCH_THREADS), 0, st, d_table, K, G,
+                     (const MnMatchWork*)c->match_work, d_pred_class, d_truth_class, d_truth_crowd, th, area_lo,
+                     area_hi, d_pred_match, d_truth_match, d_pred_ignore);
+}
+
 extern "C" int mn_match_overlaps_device(mn_context* c, const int* d_table, int num_pred, int num_truth,
                                          const int* d_pred_class, const float* d_pred_score,
                                          const int* d_truth_class, const unsigned char* d_truth_crowd,
@@ -2813,18 +2841,116 @@ extern "C" int mn_match_overlaps_device(mn_context* c, const int* d_table, int n
     return MN_OK;
   }
   if (!c->match_work) MN_HIP(dev_alloc(c, &c->match_work, 1));
-  MnThresholds th;
-  for (int i = 0; i < 16; i++) th.t[i] = thresholds[i < T ? i : T - 1];
-  hipLaunchKernelGGL(mn_match_areas, dim3((unsigned)((K + 3) / 4 + (G + 63) / 64)), dim3(MN_MATCH_THREADS), 0, st,
-                     d_table, K, G, d_truth_crowd, area_lo, area_hi, c->match_work, d_truth_ignore);
-  hipLaunchKernelGGL(mn_match_rank, dim3(grid_for(K, MN_MATCH_THREADS)), dim3(MN_MATCH_THREADS), 0, st, K,
-                     d_pred_score, c->match_work);
-  if (d_iou)
-    hipLaunchKernelGGL(mn_match_iou, dim3(grid_for((size_t)K * G, MN_MATCH_THREADS)), dim3(MN_MATCH_THREADS), 0, st,
-                       d_table, K, G, d_truth_crowd, (const MnMatchWork*)c->match_work, d_iou);
-  hipLaunchKernelGGL(mn_match_greedy, dim3(T), dim3(MN_MATCH_THREADS), 0, st, d_table, K, G,
-                     (const MnMatchWork*)c->match_work, d_pred_class, d_truth_class, d_truth_crowd, th, area_lo,
-                     area_hi, d_pred_match, d_truth_match, d_pred_ignore);
+  match_launch(c, st, d_table, K, G, d_pred_class, d_pred_score, d_truth_class, d_truth_crowd,
+               match_thresholds(thresholds, T), T, area_lo, area_hi, d_iou, d_pred_match, d_truth_match, d_pred_ignore,
+               d_truth_ignore, /* ordered */ false);
+  MN_HIP(hipGetLastError());
+  g_last_status = MN_OK;
+  return MN_OK;
+}
+
+// ---- the dataset-level evaluation: a log of records, accumulate (mn_kernels_eval.h) ----------------------
+// All three only enqueue.  The log and its fill are the caller's; nothing here reads anything back.
+extern "C" int mn_eval_append_device(mn_context* c, const int* d_table, int num_pred, int num_truth,
+                                      const int* d_pred_class, const float* d_pred_score, const int* d_truth_class,
+                                      const unsigned char* d_truth_crowd, const double* thresholds,
+                                      int num_thresholds, const double* area_ranges, int num_areas, int max_det,
+                                      int num_classes, int image, void* d_records, long long* d_npig, void* stream) {
+  const int K = num_pred, G = num_truth, T = num_thresholds, A = num_areas;
+  if (!c || !d_table || !thresholds || !area_ranges || !d_npig || T < 1 || T > 16 || A < 1 || A > MN_EVAL_MAX_AREAS ||
+      K < 0 || G < 0 || max_det < 1 || num_classes < 1 || image < 0 || (K > 0 && (!d_pred_class || !d_records)) ||
+      (G > 0 && !d_truth_class) || (reinterpret_cast<uintptr_t>(d_records) & 15) != 0) {
+    g_last_status = MN_ERR_ARGUMENT;
+    return MN_ERR_ARGUMENT;
+  }
+  if (K > MN_MATCH_MAX_INSTANCES || G > MN_MATCH_MAX_INSTANCES) {
+    g_last_status = MN_ERR_CAPACITY;
+    return MN_ERR_CAPACITY;
+  }
+  if (K == 0 && G == 0) {                                        // an image without anything: no record, no count
+    g_last_status = MN_OK;
+    return MN_OK;
+  }
+  MN_HIP(hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (!c->match_work) MN_HIP(dev_alloc(c, &c->match_work, 1));
+  if (!c->eval_work) MN_HIP(dev_alloc(c, &c->eval_work, 1));
+  MnEvalWork* e = c->eval_work;
+  MnAreaRanges ar;
+  for (int a = 0; a < MN_EVAL_MAX_AREAS; a++) {
+    ar.lo[a] = area_ranges[2 * (a < A ? a : A - 1)];
+    ar.hi[a] = area_ranges[2 * (a < A ? a : A - 1) + 1];
+  }
+  const dim3 b(MN_EVAL_THREADS);
+  if (K > 0)
+    hipLaunchKernelGGL(mn_eval_rank, dim3(grid_for(K, MN_EVAL_THREADS)), b, 0, st, K, d_pred_class, d_pred_score,
+                       max_det, c->match_work, e);
+  if (K > 0 && G > 0) {
+    const MnThresholds th = match_thresholds(thresholds, T);
+    for (int a = 0; a < A; a++)
+      match_launch(c, st, d_table, K, G, d_pred_class, d_pred_score, d_truth_class, d_truth_crowd, th, T, ar.lo[a],
+                   ar.hi[a], nullptr, e->pred_match + (size_t)a * T * K, e->truth_match,
+                   e->pred_ignore + (size_t)a * T * K, nullptr, /* ordered */ true);
+  } else {                                                       // nothing to match: the areas alone
+    hipLaunchKernelGGL(mn_match_areas, dim3((unsigned)((K + 3) / 4 + (G + 63) / 64)), dim3(MN_MATCH_THREADS), 0, st,
+                       d_table, K, G, d_truth_crowd, ar.lo[0], ar.hi[0], c->match_work, (unsigned char*)nullptr);
+  }
+  if (G > 0)
+    hipLaunchKernelGGL(mn_eval_npig, dim3(grid_for(G, MN_EVAL_THREADS)), b, 0, st, G, d_truth_class, d_truth_crowd,
+                       (const MnMatchWork*)c->match_work, num_classes, A, ar, reinterpret_cast<u64*>(d_npig));
+  if (K > 0)
+    hipLaunchKernelGGL(mn_eval_pack, dim3(grid_for(K, MN_EVAL_THREADS)), b, 0, st, K, T, A, ar, max_det,
+                       G > 0 ? 1 : 0, d_pred_class, d_pred_score, (const MnMatchWork*)c->match_work,
+                       (const MnEvalWork*)e, image, static_cast<uint4*>(d_records));
+  MN_HIP(hipGetLastError());
+  g_last_status = MN_OK;
+  return MN_OK;
+}
+
+extern "C" int mn_eval_keys_device(mn_context* c, const void* d_records, long long num_records, int num_classes,
+                                    long long* d_keys, void* stream) {
+  if (!c || num_records < 0 || num_records > (long long)INT_MAX || num_classes < 1 ||
+      (num_records > 0 && (!d_records || !d_keys)) || (reinterpret_cast<uintptr_t>(d_records) & 15) != 0) {
+    g_last_status = MN_ERR_ARGUMENT;
+    return MN_ERR_ARGUMENT;
+  }
+  if (num_records > 0) {
+    MN_HIP(hipSetDevice(c->device));
+    hipLaunchKernelGGL(mn_eval_keys, dim3(grid_for((size_t)num_records, MN_EVAL_THREADS)), dim3(MN_EVAL_THREADS), 0,
+                       static_cast<hipStream_t>(stream), static_cast<const uint4*>(d_records), (int)num_records,
+                       num_classes, d_keys);
+    MN_HIP(hipGetLastError());
+  }
+  g_last_status = MN_OK;
+  return MN_OK;
+}
+
+extern "C" int mn_eval_accumulate_device(mn_context* c, const void* d_records, long long num_records,
+                                          const long long* d_sorted_keys, const long long* d_sorted_index,
+                                          const long long* d_npig, int num_classes, int num_thresholds,
+                                          const double* d_rec_thresholds, int num_rec_thresholds, int num_areas,
+                                          const int* max_dets, int num_max_dets, double* d_precision,
+                                          double* d_recall, double* d_scores, void* stream) {
+  const int C = num_classes, T = num_thresholds, R = num_rec_thresholds, A = num_areas, M = num_max_dets;
+  bool ok = c && d_npig && max_dets && d_precision && d_recall && d_scores && C >= 1 && T >= 1 && T <= 16 && R >= 0 &&
+            (R == 0 || d_rec_thresholds) && A >= 1 && A <= MN_EVAL_MAX_AREAS && M >= 1 && M <= MN_EVAL_MAX_DETS &&
+            num_records >= 0 && num_records <= (long long)INT_MAX &&
+            (num_records == 0 || (d_records && d_sorted_keys && d_sorted_index)) &&
+            (reinterpret_cast<uintptr_t>(d_records) & 15) == 0 && (long long)C * A * M <= (long long)INT_MAX;
+  MnMaxDets md;
+  for (int m = 0; ok && m < MN_EVAL_MAX_DETS; m++) {
+    md.m[m] = max_dets[m < M ? m : M - 1];
+    ok = md.m[m] >= 1 && (m == 0 || m >= M || md.m[m] > md.m[m - 1]);
+  }
+  if (!ok) {
+    g_last_status = MN_ERR_ARGUMENT;
+    return MN_ERR_ARGUMENT;
+  }
+  MN_HIP(hipSetDevice(c->device));
+  hipLaunchKernelGGL(mn_eval_scan, dim3((unsigned)(C * A * M), (unsigned)T), dim3(MN_EVAL_THREADS), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const uint4*>(d_records), (int)num_records,
+                     d_sorted_keys, d_sorted_index, d_npig, C, T, R, A, M, md, d_rec_thresholds, d_precision, d_recall,
+                     d_scores);
   MN_HIP(hipGetLastError());
   g_last_status = MN_OK;
   return MN_OK;

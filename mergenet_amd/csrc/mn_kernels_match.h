@@ -4,7 +4,7 @@
 // Reference work replaced (the Cityscapes caller's last stage and the ground truth it is held to):
 //   COCOeval(...).evaluate()          egs/cityscape/local/evaluate.py:67-73    computeIoU + evaluateImg per image
 //   anns_to_mask                      utils/dataset.py:486-506                 the truth label mask compared with
-//   (accumulate and summarize, the dataset-level part, stay on the host: they are not here)
+//   (accumulate, the dataset-level part, is mn_kernels_eval.h)
 // Definitions, the whole of both computations (mergenet_hip.h gives them in full):
 //   table[p][g] = number of pixels with prediction label p and truth label g, p in 0..K, g in 0..G; a label
 //                 outside its range counts as 0;
@@ -251,9 +251,13 @@ __global__ __launch_bounds__(MN_MATCH_THREADS) void mn_match_greedy(const int* _
   const int t = blockIdx.x, tid = threadIdx.x;
   const double lo = fmin(th.t[t], 1.0 - 1e-10);
   for (int j = tid; j < G; j += MN_MATCH_THREADS) tm[j] = 0;   // (each lane its own entries: no barrier)
+  int taken = 0;                                      // detections that went through the barrier below
   for (int r = 0; r < K; r++) {
     const int d = w->order_p[r];
-    if ((unsigned)(d - 1) >= (unsigned)K) continue;   // (the ranks are a permutation; d forms addresses, so it is held to 1..K)
+    // d forms addresses, so it is held to 1..K.  mn_match_rank's ranks are a permutation; mn_eval_rank enters the
+    // detections it leaves out of the matching as 0.  An entry passed over runs no barrier, so the slots below
+    // alternate on the count of detections taken, not on r: two taken in a row never share a set of slots.
+    if ((unsigned)(d - 1) >= (unsigned)K) continue;
     const double ap = w->area_p[d - 1];
     const int cls = pred_class[d - 1];
     const int* row = table + (size_t)d * (size_t)(G + 1);
@@ -277,7 +281,7 @@ __global__ __launch_bounds__(MN_MATCH_THREADS) void mn_match_greedy(const int* _
       const int g0 = key >> 13, g1 = okey >> 13;
       if (g1 > g0 || (g1 == g0 && (obest > best || (obest == best && okey > key)))) { key = okey; best = obest; }
     }
-    const int buf = r & 1;
+    const int buf = taken++ & 1;
     if ((tid & 63) == 0) { s_key[buf][tid >> 6] = key; s_iou[buf][tid >> 6] = best; }
     __syncthreads();
     key = s_key[buf][0]; best = s_iou[buf][0];

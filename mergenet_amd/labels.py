@@ -7,7 +7,8 @@ are therefore compared as partitions plus per-instance class.
 Also the numpy statements of the instance table and the small-instance filter (``instance_table``,
 ``filter_instances``), the checkers of ``Merger.instance_table`` / ``Merger.filter_instances``, and those of the
 comparison with the ground truth (``overlap_table``, ``instance_iou``, ``match_instances``), the checkers of
-``Merger.overlap_table`` / ``Merger.match_instances``, and of the scores of the network's maps themselves
+``Merger.overlap_table`` / ``Merger.match_instances``, of the dataset-level evaluation (``eval_records``,
+``coco_accumulate``, ``coco_summarize``: the checkers of ``Merger.dataset_eval``), and of the scores of the network's maps themselves
 (``map_scores``, the checker of ``Merger.map_scores``, with the reference's summaries ``class_scores`` and
 ``offset_iou``).
 """
@@ -260,6 +261,199 @@ def match_instances(table, pred_classes, truth_classes, scores=None, crowd=None,
     res["truth_ignore"] = ign
     res["iou"] = iou
     return res
+
+
+# ---- the dataset-level evaluation: the numpy statements of Merger.dataset_eval -------------------------------
+# (COCOeval.evaluate's per-image cut to maxDets, accumulate and summarize, restated.  The contract is pinned to these
+# statements and to hand-computed cases, not to pycocotools, which is not a dependency.)
+
+COCO_AREA_RANGES = ((0.0, 1e10), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e10))   # all, small, medium, large
+COCO_MAX_DETS = (1, 10, 100)
+COCO_REC_THRESHOLDS = np.linspace(0.0, 1.0, 101)
+
+
+def _eval_params(thresholds, area_ranges, max_dets):
+    th = COCO_THRESHOLDS if thresholds is None else np.asarray(thresholds, np.float64).reshape(-1)
+    ar = np.asarray(COCO_AREA_RANGES if area_ranges is None else area_ranges, np.float64).reshape(-1, 2)
+    md = [int(m) for m in max_dets]
+    if not 1 <= len(th) <= 16:
+        raise ValueError("thresholds: 1 to 16 values")
+    if not 1 <= len(ar) <= 4:
+        raise ValueError("area_ranges: 1 to 4 (lo, hi) pairs")
+    if not 1 <= len(md) <= 4 or md[0] < 1 or any(b <= a for a, b in zip(md, md[1:])):
+        raise ValueError("max_dets: 1 to 4 ascending positive values")
+    return th, ar, md
+
+
+def eval_records(table, pred_classes, truth_classes, scores=None, crowd=None, thresholds=None, area_ranges=None,
+                 max_det: int = 100, num_classes=None, image: int = 0) -> dict:
+    """What one image adds to the evaluation log.  The detections are taken in ``detection_order``; ``rank[d]`` is the
+    number of detections of d's class before d; a detection with ``rank >= max_det`` (the largest maxDets) takes no
+    part in the matching -- it is given a class that no truth instance has, which is how it matches nothing and
+    holds no truth instance (COCOeval cuts to ``dt[:maxDet]`` per image and category before it matches).  One
+    ``match_instances`` per area range: a truth instance is ignored when it is crowd or its area is outside the
+    range, a detection without a match when its own area is.
+    Returns, per detection IN DETECTION ORDER: ``classes`` int32 [K], ``scores`` float32 [K] (1 without scores,
+    egs/cityscape/local/segment.py:181), ``rank`` int32 [K], ``image`` int32 [K], ``matched`` and ``ignored`` bool
+    [A,T,K]; and ``npig`` int64 [C,A]: the truth instances of each class in 0..C-1 that the range does not ignore
+    (``None`` without ``num_classes``)."""
+    t = np.asarray(table).astype(np.int64)
+    K, G = t.shape[0] - 1, t.shape[1] - 1
+    th, ar, _ = _eval_params(thresholds, area_ranges, (max_det,))
+    T, A = len(th), len(ar)
+    pc = np.asarray(pred_classes).reshape(-1)[:K].astype(np.int64)
+    tc = np.asarray(truth_classes).reshape(-1)[:G].astype(np.int64)
+    order = detection_order(scores, K)
+    rank = np.zeros(K, np.int32)
+    seen = {}
+    for d in order:
+        rank[d] = seen.get(int(pc[d]), 0)
+        seen[int(pc[d])] = int(rank[d]) + 1
+    unused = min([int(v) for v in pc] + [int(v) for v in tc] + [0]) - 1
+    matching_classes = np.where(rank >= max_det, unused, pc)
+    area_p = t.sum(axis=1)[1:].astype(np.float64)
+    area_g = t.sum(axis=0)[1:].astype(np.float64)
+    is_crowd = _crowd_flags(crowd, G)
+    matched = np.zeros((A, T, K), bool)
+    ignored = np.zeros((A, T, K), bool)
+    npig = None if num_classes is None else np.zeros((int(num_classes), A), np.int64)
+    for a, (lo, hi) in enumerate(ar):
+        if K and G:
+            res = match_instances(t, matching_classes, tc, scores=scores, crowd=crowd, thresholds=th,
+                                  area_range=(lo, hi))
+            matched[a] = res["pred_match"][:, order] > 0
+            ignored[a] = res["pred_ignore"][:, order]
+        else:
+            ignored[a] = ((area_p < lo) | (area_p > hi))[order][None, :]
+        if npig is not None:
+            counted = ~(is_crowd | (area_g < lo) | (area_g > hi)) & (tc >= 0) & (tc < npig.shape[0])
+            np.add.at(npig[:, a], tc[counted], 1)
+    sc = np.ones(K, np.float32) if scores is None else np.asarray(scores, np.float32).reshape(-1)[:K]
+    return {"classes": pc[order].astype(np.int32), "scores": sc[order], "rank": rank[order],
+            "image": np.full(K, int(image), np.int32), "matched": matched, "ignored": ignored, "npig": npig}
+
+
+def coco_accumulate(images, num_classes: int, rec_thresholds=None, max_dets=COCO_MAX_DETS, num_thresholds=None,
+                    num_area_ranges=None, form: str = "closed") -> dict:
+    """COCOeval.accumulate over the ``eval_records`` of the images, in the order they were added.  Returns
+    ``{"precision": float64 [T,R,C,A,M], "recall": float64 [T,C,A,M], "scores": float64 [T,R,C,A,M], "npig": int64
+    [C,A]}``.  T and A are those of the records (``num_thresholds`` / ``num_area_ranges`` say them for an empty list:
+    10 and 4 by default).  Per class k, range a and ``max_dets[m]``: the records of class k with ``rank < max_dets[m]``,
+    sorted stably by descending score, NaN last; ``tp = cumsum(matched & ~ignored)``, ``fp = cumsum(~matched &
+    ~ignored)``, ``rc = tp / npig[k][a]``, ``pr = tp / (fp + tp + np.spacing(1))``, ``pr[i] = max(pr[i:])``; per recall
+    threshold the ``pr`` and score at the first index with ``rc >= threshold``, 0 where there is none; ``recall`` is
+    the last ``rc``, 0 without records; everything of (k, a) is -1 where ``npig[k][a] == 0``.
+
+    ``form="loop"`` is written the way COCOeval.accumulate is: concatenate, ``argsort(-scores, kind="mergesort")``,
+    cumsum, the envelope ``for``, ``searchsorted`` (whose index is taken per threshold: where pycocotools stops at
+    the first threshold out of reach, every later one is out of reach too when the thresholds ascend).
+    ``form="closed"`` states the outcome: suffix maximum, first index with ``rc >= threshold``."""
+    if form not in ("loop", "closed"):
+        raise ValueError("form: 'loop' or 'closed'")
+    images = list(images)
+    C = int(num_classes)
+    rec = COCO_REC_THRESHOLDS if rec_thresholds is None else np.asarray(rec_thresholds, np.float64).reshape(-1)
+    _, _, md = _eval_params(None, None, max_dets)
+    if images:
+        A, T = images[0]["matched"].shape[:2]
+    else:
+        T = 10 if num_thresholds is None else int(num_thresholds)
+        A = 4 if num_area_ranges is None else int(num_area_ranges)
+    if any(img["matched"].shape[:2] != (A, T) or img["npig"].shape != (C, A) for img in images):
+        raise ValueError("the records differ in their thresholds, area ranges or classes")
+    R, M = len(rec), len(md)
+    npig = np.zeros((C, A), np.int64)
+    for img in images:
+        npig += img["npig"]
+    precision = -np.ones((T, R, C, A, M))
+    recall = -np.ones((T, C, A, M))
+    scores = -np.ones((T, R, C, A, M))
+    for k in range(C):
+        for a in range(A):
+            if npig[k, a] == 0:
+                continue
+            for m, max_det in enumerate(md):
+                sel = [(img["classes"] == k) & (img["rank"] < max_det) for img in images]
+                sc = np.concatenate([img["scores"][s] for img, s in zip(images, sel)] + [np.zeros(0, np.float32)])
+                dtm = np.concatenate([img["matched"][a][:, s] for img, s in zip(images, sel)] +
+                                     [np.zeros((T, 0), bool)], axis=1)
+                dtig = np.concatenate([img["ignored"][a][:, s] for img, s in zip(images, sel)] +
+                                      [np.zeros((T, 0), bool)], axis=1)
+                nd = len(sc)
+                if form == "loop":
+                    inds = np.argsort(-sc, kind="mergesort")
+                else:
+                    inds = np.asarray(sorted(range(nd), key=lambda i: (1, 0.0) if sc[i] != sc[i] else (0, -float(sc[i]))),
+                                      np.int64)
+                sc, dtm, dtig = sc[inds], dtm[:, inds], dtig[:, inds]
+                tp_sum = np.cumsum(dtm & ~dtig, axis=1).astype(np.float64)
+                fp_sum = np.cumsum(~dtm & ~dtig, axis=1).astype(np.float64)
+                for t in range(T):
+                    tp, fp = tp_sum[t], fp_sum[t]
+                    rc = tp / npig[k, a]
+                    pr = tp / (fp + tp + np.spacing(1))
+                    recall[t, k, a, m] = rc[-1] if nd else 0
+                    q, ss = np.zeros(R), np.zeros(R)
+                    if form == "loop":
+                        pr = pr.tolist()
+                        for i in range(nd - 1, 0, -1):
+                            if pr[i] > pr[i - 1]:
+                                pr[i - 1] = pr[i]
+                        for ri, pi in enumerate(np.searchsorted(rc, rec, side="left")):
+                            if pi < nd:
+                                q[ri] = pr[pi]
+                                ss[ri] = sc[pi]
+                    else:
+                        env = np.maximum.accumulate(pr[::-1])[::-1]
+                        for ri, thr in enumerate(rec):
+                            at = np.flatnonzero(rc >= thr)
+                            if at.size:
+                                q[ri] = env[at[0]]
+                                ss[ri] = sc[at[0]]
+                    precision[t, :, k, a, m] = q
+                    scores[t, :, k, a, m] = ss
+    return {"precision": precision, "recall": recall, "scores": scores, "npig": npig}
+
+
+def eval_summary_names(max_dets=COCO_MAX_DETS):
+    """The keys of ``coco_summarize`` in COCOeval.summarize's order: twelve with three maxDets."""
+    return (["AP", "AP50", "AP75", "AP_small", "AP_medium", "AP_large"] + ["AR@%d" % int(m) for m in max_dets] +
+            ["AR_small", "AR_medium", "AR_large"])
+
+
+def coco_summarize(result, thresholds=None, max_dets=COCO_MAX_DETS, classes=None) -> dict:
+    """The numbers of COCOeval.summarize for iouType 'segm' from what ``coco_accumulate`` (or the device) gave: each
+    the mean of the entries greater than -1 over ``classes`` (default 1..C-1: class 0 is the background), -1 where
+    there is none.  AP, AP50, AP75, AP_small / _medium / _large: ``precision`` at the largest maxDets, for area range
+    0 ("all") and ranges 1, 2, 3; AR@m for each of ``max_dets`` at range 0; AR_small / _medium / _large: ``recall`` at
+    the largest maxDets.  AP50 / AP75 take the threshold EQUAL to 0.5 / 0.75 and are -1 without it; the small,
+    medium and large entries are -1 with fewer than four area ranges."""
+    precision, recall = np.asarray(result["precision"]), np.asarray(result["recall"])
+    T, _, C, A, M = precision.shape
+    th = COCO_THRESHOLDS if thresholds is None else np.asarray(thresholds, np.float64).reshape(-1)
+    md = [int(m) for m in max_dets]
+    if len(th) != T or len(md) != M:
+        raise ValueError("thresholds / max_dets: not those of the result")
+    cls = np.arange(1, C) if classes is None else np.asarray(list(classes), np.int64).reshape(-1)
+    if cls.size and (cls.min() < 0 or cls.max() >= C):
+        raise ValueError("classes: within 0..%d" % (C - 1))
+
+    def mean(s):
+        s = s[s > -1]
+        return float(s.mean()) if s.size else -1.0
+
+    def ap(a, at=None):
+        if a >= A or (at is not None and not (th == at).any()):
+            return -1.0
+        s = precision[:, :, cls, a, M - 1]
+        return mean(s if at is None else s[th == at])
+
+    def ar(a, m):
+        return mean(recall[:, cls, a, m]) if a < A else -1.0
+
+    values = ([ap(0), ap(0, 0.5), ap(0, 0.75), ap(1), ap(2), ap(3)] + [ar(0, m) for m in range(M)] +
+              [ar(1, M - 1), ar(2, M - 1), ar(3, M - 1)])
+    return dict(zip(eval_summary_names(md), values))
 
 
 # ---- uniform groups of the sweep's lean form: the numpy twin of the rule in mn_cc_sign ----------------------

@@ -44,6 +44,9 @@ MN_MAPS_LOGITS = 0x100   # or-ed into that dtype: both maps hold logits, the ker
 MN_ERR_ARGUMENT = -1
 MN_ERR_CAPACITY = -4
 MN_MATCH_MAX_INSTANCES = 4096   # most prediction / truth instances of Merger.match_instances
+MN_EVAL_RECORD_BYTES = 32        # a record of the evaluation log (DatasetEval)
+MN_EVAL_MAX_AREAS, MN_EVAL_MAX_DETS = 4, 4
+MN_EVAL_CHUNK = 256              # records the accumulate pass scans per step
 MN_PROVE_ALWAYS, MN_PROVE_BY_MODE, MN_PROVE_NEVER = 1, 0, -1   # mn_options.require_proof
 MN_TIES_DEFAULT, MN_TIES_REFERENCE, MN_TIES_LOWEST_ID = 0, 1, 2   # mn_options.tie_order
 MN_PROOF_NONE, MN_PROOF_CERTIFICATE, MN_PROOF_SEQUENTIAL, MN_PROOF_SEQUENTIAL_TIES = 0, 1, 2, 3   # mn_stats.proof
@@ -93,6 +96,7 @@ EXPORTS = ["mn_default_options", "mn_create", "mn_destroy", "mn_workspace_bytes"
            "mn_prepare_device", "mn_upsample_mask_device", "mn_rle_points_device", "mn_rle_encode_host", "mn_rle_counts_host", "mn_rle_decode_device", "mn_sameness_targets_device", "mn_instance_scores_device",
            "mn_instance_table_device", "mn_filter_instances_device",
            "mn_overlap_table_device", "mn_match_overlaps_device", "mn_map_scores_device", "mn_tile_class_maps_device",
+           "mn_eval_append_device", "mn_eval_keys_device", "mn_eval_accumulate_device",
            "mn_pack_wire_device", "mn_runs_wire_words", "mn_pack_runs_device", "mn_unpack_runs_device",
            "mn_unpack_runs_batch_device",
            "mn_segment_device_t", "mn_segment_launch_t", "mn_segment_exact_batch_t", "mn_score_device_t",
@@ -237,6 +241,22 @@ def load_library() -> ctypes.CDLL:
                                                   ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         lib.mn_match_overlaps_device.restype = ctypes.c_int
+    if hasattr(lib, "mn_eval_append_device"):            # (absent from older variant builds: MN_LIB)
+        _f64p = ctypes.POINTER(ctypes.c_double)
+        lib.mn_eval_append_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              _f64p, ctypes.c_int, _f64p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        lib.mn_eval_append_device.restype = ctypes.c_int
+        lib.mn_eval_keys_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
+                                            ctypes.c_void_p, ctypes.c_void_p]
+        lib.mn_eval_keys_device.restype = ctypes.c_int
+        lib.mn_eval_accumulate_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                  ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _i32p,
+                                                  ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p]
+        lib.mn_eval_accumulate_device.restype = ctypes.c_int
     if hasattr(lib, "mn_map_scores_device"):             # (absent from older variant builds: MN_LIB)
         lib.mn_map_scores_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -1082,6 +1102,16 @@ class Merger:
             res["iou"] = iou
         return res
 
+    def dataset_eval(self, num_classes: int, thresholds=None, rec_thresholds=None, area_ranges=None,
+                     max_dets=(1, 10, 100), capacity: int = 16384):
+        """A :class:`DatasetEval` on this Merger: the evaluation log of a validation pass on the device and, from
+        it, COCOeval's accumulate and summarize (egs/cityscape/local/evaluate.py:67-73).  ``num_classes`` C: the
+        class axis of the results is class 0..C-1; ``thresholds``: None for COCO's ten or 1..16 IoU thresholds;
+        ``rec_thresholds``: None for ``np.linspace(0, 1, 101)`` or float64 values, passed to the device as they are;
+        ``area_ranges``: None for COCO's four (all, small, medium, large) or 1..4 ``(lo, hi)`` pairs; ``max_dets``:
+        1..4 ascending positive values; ``capacity``: records the log holds at first (it grows by doubling)."""
+        return DatasetEval(self, num_classes, thresholds, rec_thresholds, area_ranges, max_dets, capacity)
+
     def map_scores(self, class_probs, same_probs, offsets, truth, truth_classes, logits: bool = False, into=None):
         """The network's maps themselves against the ground truth: what ``runningScore.update`` and
         ``offsetIoU.update`` (utils/score.py:20-32,77-86) accumulate per image, in one pass over the maps on the
@@ -1175,6 +1205,162 @@ class Merger:
         if rc != 0:
             raise MergeNetError(rc)
         return out
+
+
+class DatasetEval:
+    """The evaluation of a whole validation pass on the device (``Merger.dataset_eval``):
+
+        ev = merger.dataset_eval(num_classes=9)
+        for image in validation_set:
+            ...
+            table = merger.overlap_table(mask, truth, K, G)
+            ev.add(table, classes, truth_classes, scores, crowd)      # enqueues only
+        numbers = ev.summarize()                                      # {"AP": ..., "AP50": ..., ...}
+
+    ``add`` appends one record per detection to a log on the device -- class, score, rank among the image's detections
+    of its class, image ordinal, and a matched and an ignored bit per area range and IoU threshold -- and adds the
+    image's non-ignored truth instances to ``npig``.  The host knows the number of records an image adds (K, from the
+    table's shape), so it keeps the fill of the log itself: no counter lives on the device and nothing is ever read
+    back.  ``accumulate`` is COCOeval.accumulate over the log; ``summarize`` makes the one host copy.
+    ``labels.eval_records``, ``labels.coco_accumulate`` and ``labels.coco_summarize`` are the numpy statements and
+    give the definitions; the device arrays equal them bit for bit.  (The contract is pinned to those statements and
+    to hand-computed cases, not to pycocotools, which is not a dependency.)
+    All calls of one evaluator, and the other matching calls of its Merger, belong on ONE stream."""
+
+    def __init__(self, merger, num_classes: int, thresholds=None, rec_thresholds=None, area_ranges=None,
+                 max_dets=(1, 10, 100), capacity: int = 16384):
+        from . import labels
+        torch = merger.torch
+        self._append = merger._entry("mn_eval_append_device")
+        self._keys = merger._entry("mn_eval_keys_device")
+        self._accumulate = merger._entry("mn_eval_accumulate_device")
+        self.merger, self.torch = merger, torch
+        self.num_classes = int(num_classes)
+        if self.num_classes < 1:
+            raise ValueError("num_classes >= 1")
+        th, ar, md = labels._eval_params(thresholds, area_ranges, max_dets)
+        self.thresholds = np.ascontiguousarray(th, np.float64)
+        self.area_ranges = np.ascontiguousarray(ar, np.float64)
+        self.max_dets = tuple(md)
+        self._max_dets_c = (ctypes.c_int * len(md))(*md)
+        rec = labels.COCO_REC_THRESHOLDS if rec_thresholds is None else np.asarray(rec_thresholds, np.float64)
+        self.rec_thresholds = np.ascontiguousarray(rec.reshape(-1), np.float64)
+        if int(capacity) < 1:
+            raise ValueError("capacity >= 1")
+        self.device = torch.device("cuda", merger.device)
+        self._rec_dev = torch.from_numpy(self.rec_thresholds.copy()).to(self.device)
+        self._capacity0 = int(capacity)
+        self.reset()
+
+    def reset(self) -> None:
+        """Empty the log and zero ``npig`` (on the current stream); the capacity goes back to the initial one."""
+        torch = self.torch
+        self._log = torch.empty((self._capacity0, MN_EVAL_RECORD_BYTES // 4), dtype=torch.int32, device=self.device)
+        self._npig = torch.zeros((self.num_classes, len(self.area_ranges)), dtype=torch.int64, device=self.device)
+        self.num_records = 0
+        self.num_images = 0
+
+    @property
+    def capacity(self) -> int:
+        return int(self._log.shape[0])
+
+    def add(self, table, pred_classes, truth_classes, scores=None, crowd=None) -> None:
+        """One image: the arguments of :meth:`Merger.match_instances`.  Enqueues on the current stream; nothing is
+        synchronised.  K, G <= 4096."""
+        torch = self.torch
+        if not (table.is_cuda and table.dtype == torch.int32 and table.is_contiguous() and table.dim() == 2
+                and table.shape[0] >= 1 and table.shape[1] >= 1 and table.device == self.device):
+            raise ValueError("table: the contiguous int32 [K+1, G+1] tensor of overlap_table(), on the evaluator's GPU")
+        K, G = int(table.shape[0]) - 1, int(table.shape[1]) - 1
+        if K > MN_MATCH_MAX_INSTANCES or G > MN_MATCH_MAX_INSTANCES:
+            raise ValueError("at most %d prediction and truth instances per image" % MN_MATCH_MAX_INSTANCES)
+
+        def checked(x, name, dtypes, n):
+            if x is None:
+                return None
+            if not (x.is_cuda and x.dtype in dtypes and x.is_contiguous() and x.numel() >= n
+                    and x.device == self.device):
+                raise ValueError("%s: a contiguous %s tensor of at least %d entries on the table's GPU"
+                                 % (name, " / ".join(str(d) for d in dtypes), n))
+            return x
+
+        if pred_classes is None or truth_classes is None:
+            raise ValueError("pred_classes and truth_classes are needed")
+        checked(pred_classes, "pred_classes", (torch.int32,), K)
+        checked(truth_classes, "truth_classes", (torch.int32,), G)
+        checked(scores, "scores", (torch.float32,), K)
+        checked(crowd, "crowd", (torch.uint8, torch.bool), G)
+        if self.num_records + K > 2 ** 31 - 1:
+            raise ValueError("the log holds at most 2^31 - 1 records")
+        if self.num_records + K > self.capacity:                 # grow by doubling: a copy on the stream, no read-back
+            grown = torch.empty((max(2 * self.capacity, self.num_records + K), self._log.shape[1]),
+                                dtype=torch.int32, device=self.device)
+            grown[:self.num_records].copy_(self._log[:self.num_records])
+            self._log = grown
+        _f64p = ctypes.POINTER(ctypes.c_double)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._append(self.merger.handle, table.data_ptr(), K, G, pred_classes.data_ptr(),
+                          scores.data_ptr() if scores is not None else None, truth_classes.data_ptr(),
+                          crowd.data_ptr() if crowd is not None else None, self.thresholds.ctypes.data_as(_f64p),
+                          len(self.thresholds), self.area_ranges.ctypes.data_as(_f64p), len(self.area_ranges),
+                          self.max_dets[-1], self.num_classes, self.num_images,
+                          self._log.data_ptr() + self.num_records * MN_EVAL_RECORD_BYTES, self._npig.data_ptr(),
+                          ctypes.c_void_p(stream))
+        if rc != 0:
+            raise MergeNetError(rc)
+        self.num_records += K
+        self.num_images += 1
+
+    def accumulate(self) -> dict:
+        """``{"precision": float64 [T,R,C,A,M], "recall": float64 [T,C,A,M], "scores": float64 [T,R,C,A,M], "npig":
+        int64 [C,A]}`` on the device, as ``labels.coco_accumulate`` defines them; -1 where a class has no non-ignored
+        truth instance in an area range (everywhere for an evaluator without images).  A key per record, torch's
+        stable sort of the keys, then one pass over the sorted log.  The log is left as it is: more images may follow."""
+        torch = self.torch
+        T, R, C = len(self.thresholds), len(self.rec_thresholds), self.num_classes
+        A, M, N = len(self.area_ranges), len(self.max_dets), self.num_records
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        keys = index = None
+        if N:
+            raw = torch.empty((N,), dtype=torch.int64, device=self.device)
+            rc = self._keys(self.merger.handle, self._log.data_ptr(), N, C, raw.data_ptr(), stream)
+            if rc != 0:
+                raise MergeNetError(rc)
+            keys, index = torch.sort(raw, stable=True)
+        precision = torch.empty((T, R, C, A, M), dtype=torch.float64, device=self.device)
+        recall = torch.empty((T, C, A, M), dtype=torch.float64, device=self.device)
+        scores = torch.empty((T, R, C, A, M), dtype=torch.float64, device=self.device)
+        rc = self._accumulate(self.merger.handle, self._log.data_ptr() if N else None, N,
+                              keys.data_ptr() if N else None, index.data_ptr() if N else None, self._npig.data_ptr(),
+                              C, T, self._rec_dev.data_ptr() if R else None, R, A, self._max_dets_c, M,
+                              precision.data_ptr(), recall.data_ptr(), scores.data_ptr(), stream)
+        if rc != 0:
+            raise MergeNetError(rc)
+        return {"precision": precision, "recall": recall, "scores": scores, "npig": self._npig.clone()}
+
+    def summarize(self, result=None, classes=None) -> dict:
+        """The twelve numbers of COCOeval.summarize (``labels.coco_summarize``; keys ``labels.eval_summary_names``) over
+        ``classes`` (default 1..C-1).  ``result``: what :meth:`accumulate` gave, or None to run it.  Copies the
+        arrays to the host: the one synchronisation of the evaluation."""
+        from . import labels
+        result = self.accumulate() if result is None else result
+        host = {k: result[k].cpu().numpy() for k in ("precision", "recall")}
+        return labels.coco_summarize(host, self.thresholds, self.max_dets, classes)
+
+    def records(self) -> dict:
+        """The log on the host, for inspection and tests (synchronises): what ``labels.eval_records`` returns for each
+        image, concatenated in ``add`` order -- ``classes``, ``scores``, ``rank``, ``image`` [N], ``matched`` and
+        ``ignored`` bool [A,T,N]."""
+        T, A, N = len(self.thresholds), len(self.area_ranges), self.num_records
+        raw = self._log[:N].cpu().numpy()
+        bits = np.arange(A * T, dtype=np.uint64)
+        words = raw[:, 4:8].copy().view(np.uint64).reshape(N, 2)
+
+        def planes(col):
+            return ((words[:, col][None, :] >> bits[:, None]) & np.uint64(1)).astype(bool).reshape(A, T, N)
+
+        return {"classes": raw[:, 0].copy(), "scores": raw[:, 1].copy().view(np.float32), "rank": raw[:, 2].copy(),
+                "image": raw[:, 3].copy(), "matched": planes(0), "ignored": planes(1)}
 
 
 class PendingSegment:
