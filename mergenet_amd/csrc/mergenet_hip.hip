@@ -2703,19 +2703,13 @@ extern "C" int mn_instance_table_device(mn_context* c, const int* d_mask, int he
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(mn_instance_table_init, dim3(grid_for(num_instances, 256)), dim3(256), 0, st, num_instances,
                      height, width, d_table);
-  const bool vec = width % 4 == 0 && (reinterpret_cast<uintptr_t>(d_mask) & 15) == 0;
-  const int per_chunk = vec ? 256 : 64;                          // pixels of one 64-lane load
-  const int chunks_per_row = (width + per_chunk - 1) / per_chunk;
-  const int total = height * chunks_per_row;                     // <= H * W
-  const int waves = MN_INST_WORKGROUPS * (MN_INST_THREADS / 64);
-  const int chunks_per_wave = (total + waves - 1) / waves;       // >= 1
-  const dim3 g(grid_for(total, (unsigned)(MN_INST_THREADS / 64) * (unsigned)chunks_per_wave)), b(MN_INST_THREADS);
-  if (vec)
-    hipLaunchKernelGGL(mn_instance_table_runs<4>, g, b, 0, st, d_mask, height, width, num_instances,
-                       chunks_per_row, total, chunks_per_wave, d_table);
+  const int v = row_walk_v(width, sizeof(int), d_mask);
+  const RowWalk R = row_walk_aimed(height, width, v, MN_INST_WORKGROUPS, MN_INST_THREADS / 64);
+  const dim3 g((unsigned)R.blocks), b(MN_INST_THREADS);
+  if (v == 4)
+    hipLaunchKernelGGL(mn_instance_table_runs<4>, g, b, 0, st, d_mask, height, width, num_instances, R, d_table);
   else
-    hipLaunchKernelGGL(mn_instance_table_runs<1>, g, b, 0, st, d_mask, height, width, num_instances,
-                       chunks_per_row, total, chunks_per_wave, d_table);
+    hipLaunchKernelGGL(mn_instance_table_runs<1>, g, b, 0, st, d_mask, height, width, num_instances, R, d_table);
   MN_HIP(hipGetLastError());
   return MN_OK;
 }
@@ -2765,20 +2759,15 @@ extern "C" int mn_overlap_table_device(mn_context* c, const int* d_pred, const i
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t entries = (size_t)(num_pred + 1) * (size_t)(num_truth + 1);
   MN_HIP(hipMemsetAsync(d_table, 0, entries * sizeof(int), st));
-  const bool vec = width % 4 == 0 &&
-                   ((reinterpret_cast<uintptr_t>(d_pred) | reinterpret_cast<uintptr_t>(d_truth)) & 15) == 0;
-  const int per_chunk = vec ? 256 : 64;                          // pixels of one 64-lane load
-  const int chunks_per_row = (width + per_chunk - 1) / per_chunk;
-  const int total = height * chunks_per_row;                     // <= H * W
-  const int waves = MN_OVL_WORKGROUPS * (MN_OVL_THREADS / 64);
-  const int chunks_per_wave = (total + waves - 1) / waves;       // >= 1
-  const dim3 g(grid_for(total, (unsigned)(MN_OVL_THREADS / 64) * (unsigned)chunks_per_wave)), b(MN_OVL_THREADS);
-  if (vec)
-    hipLaunchKernelGGL(mn_overlap_table_runs<4>, g, b, 0, st, d_pred, d_truth, height, width, num_pred, num_truth,
-                       chunks_per_row, total, chunks_per_wave, d_table);
+  const int v = row_walk_v(width, sizeof(int), d_pred, d_truth);
+  const RowWalk R = row_walk_aimed(height, width, v, MN_OVL_WORKGROUPS, MN_OVL_THREADS / 64);
+  const dim3 g((unsigned)R.blocks), b(MN_OVL_THREADS);
+  if (v == 4)
+    hipLaunchKernelGGL(mn_overlap_table_runs<4>, g, b, 0, st, d_pred, d_truth, height, width, num_pred, num_truth, R,
+                       d_table);
   else
-    hipLaunchKernelGGL(mn_overlap_table_runs<1>, g, b, 0, st, d_pred, d_truth, height, width, num_pred, num_truth,
-                       chunks_per_row, total, chunks_per_wave, d_table);
+    hipLaunchKernelGGL(mn_overlap_table_runs<1>, g, b, 0, st, d_pred, d_truth, height, width, num_pred, num_truth, R,
+                       d_table);
   MN_HIP(hipGetLastError());
   g_last_status = MN_OK;
   return MN_OK;
@@ -3005,16 +2994,10 @@ extern "C" int mn_map_scores_device(mn_context* c, const void* d_class_pred, int
   const int widest = 16 / elem;
   const long long nominal = (long long)H * ((W + 64 * widest - 1) / (64 * widest));
   const long long want = (nominal + MN_MS_WAVES * MN_MS_MIN_CHUNKS - 1) / (MN_MS_WAVES * MN_MS_MIN_CHUNKS);
-  A.slots = (int)std::min<long long>(MN_MS_WORKGROUPS, want);
-  const uintptr_t bases = reinterpret_cast<uintptr_t>(d_class_pred) | reinterpret_cast<uintptr_t>(d_adj_pred);
-  int v = 1;
-  if (W % widest == 0 && (bases & 15) == 0) v = widest;
-  else if (elem == 2 && W % 4 == 0 && (bases & 7) == 0) v = 4;
-  A.chunks_per_row = (W + 64 * v - 1) / (64 * v);
-  A.total_chunks = H * A.chunks_per_row;                         // <= H * W
-  const int waves = A.slots * MN_MS_WAVES;
-  A.chunks_per_wave = (A.total_chunks + waves - 1) / waves;
-  const dim3 g((unsigned)A.slots);
+  const int slots = (int)std::min<long long>(MN_MS_WORKGROUPS, want);
+  const int v = row_walk_v(W, elem, d_class_pred, d_adj_pred);
+  A.walk = row_walk_fixed(H, W, v, slots, MN_MS_WAVES);
+  const dim3 g((unsigned)slots);
   if (dt == MN_DTYPE_F32) {
     if (logits) map_scores_launch<MN_DTYPE_F32, true>(v, g, st, A); else map_scores_launch<MN_DTYPE_F32, false>(v, g, st, A);
   } else if (dt == MN_DTYPE_F16) {
@@ -3022,7 +3005,7 @@ extern "C" int mn_map_scores_device(mn_context* c, const void* d_class_pred, int
   } else {
     if (logits) map_scores_launch<MN_DTYPE_BF16, true>(v, g, st, A); else map_scores_launch<MN_DTYPE_BF16, false>(v, g, st, A);
   }
-  hipLaunchKernelGGL(mn_map_scores_finish, dim3(3 * O), dim3(64), 0, st, (const double*)c->ms_partials, A.slots,
+  hipLaunchKernelGGL(mn_map_scores_finish, dim3(3 * O), dim3(64), 0, st, (const double*)c->ms_partials, slots,
                      d_sums, accumulate);
   MN_HIP(hipGetLastError());
   g_last_status = MN_OK;

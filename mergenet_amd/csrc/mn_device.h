@@ -84,6 +84,12 @@ __device__ __forceinline__ float4 mn_ld_map4(const void* base, int dtype, size_t
   return make_float4(a.x, a.y, b.x, b.y);
 }
 
+struct __attribute__((packed, aligned(4))) mn_int4u { int x, y, z, w; };
+__device__ __forceinline__ int4 mn_ld_int4_unaligned(const int* __restrict__ p) {
+  const mn_int4u t = *reinterpret_cast<const mn_int4u*>(p);
+  return make_int4(t.x, t.y, t.z, t.w);
+}
+
 // The reference's networks end in this sigmoid (utils/inference_utils.py:44,96), in float32.  One expression
 // for every site: the loaders of logits maps, mn_same_value, mn_prepare_maps.  It is exactly 1.0 from about 17
 // up and exactly 0 below about -104 (expf(+inf) = inf, 1 / inf = 0), which is why logits are always clipped.

@@ -62,12 +62,6 @@ __device__ __forceinline__ int mn_cc_find(int* __restrict__ parent, int x) {
   return x;
 }
 
-struct __attribute__((packed, aligned(4))) mn_int4u { int x, y, z, w; };
-__device__ __forceinline__ int4 mn_ld_int4_unaligned(const int* __restrict__ p) {
-  const mn_int4u t = *reinterpret_cast<const mn_int4u*>(p);
-  return make_int4(t.x, t.y, t.z, t.w);
-}
-
 // ---- the sweep over the class and sameness planes -------------------------------------------------
 // One lane takes PX consecutive pixels (PX = 4 with 16-byte loads whenever N % 4 == 0 and W >= 4 -- with
 // W % 4 != 0 one lane per row runs over the row's end: `straddle` --, else 1).  For every in-bounds

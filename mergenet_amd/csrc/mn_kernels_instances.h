@@ -13,6 +13,7 @@
 #pragma once
 
 #include "mn_device.h"
+#include "mn_row_walk.h"
 
 // Two constants of the pass; a variant build for tools/time_instance_table.py may set them (-D...):
 #ifndef MN_INST_LDS_LABELS
@@ -56,18 +57,15 @@ __device__ __forceinline__ void mn_inst_run(int* sh, int lds_rows, int* __restri
   }
 }
 
-// A wave walks `chunks_per_wave` consecutive chunks; a chunk is 64 * V consecutive pixels of ONE row (the last
-// chunk of a row may reach past W: those pixels count as label 0), lane l holds pixels V*l .. V*l + V-1 of it.
-// V = 4: one 16-byte load per lane (W % 4 == 0 and a 16-byte aligned base), V = 1: 4-byte loads, any W.
+// The walk of mn_row_walk.h over one mask, V = 4 or 1, the next chunk's load in flight over this chunk's work.
 // Masks are piecewise constant along a row, so only the first pixel of a run (its head) updates the table: the
 // heads are found against the pixel before (the lane before for a lane's first pixel; the first pixel of a chunk
-// is always a head), one ballot per pixel slot, and a head reads where its run ends from those ballots: the next
-// head in its own lane, else the first head of the first later lane that has one (__ffsll), else the chunk's end.
-// Label 0 and every label outside 1..K -- the mask is the caller's memory -- are read as 0 and update nothing.
+// is always a head), and a head reads where its run ends from mn_walk_run_end.
+// Label 0 and every label outside 1..K -- the mask is the caller's memory -- are read as 0 and update nothing;
+// so are the pixels of a row's last chunk past W.
 template <int V>
 __global__ __launch_bounds__(MN_INST_THREADS) void mn_instance_table_runs(const int* __restrict__ mask, int H, int W,
-                                                                          int K, int chunks_per_row, int total_chunks,
-                                                                          int chunks_per_wave,
+                                                                          int K, const RowWalk R,
                                                                           int* __restrict__ table) {
   __shared__ int sh[MN_INST_LDS ? 5 * MN_INST_LDS_LABELS : 1];
   const int lds_rows = min(K, MN_INST_LDS_LABELS);
@@ -82,65 +80,39 @@ __global__ __launch_bounds__(MN_INST_THREADS) void mn_instance_table_runs(const 
     __syncthreads();
   }
   const int lane = threadIdx.x & 63;
-  const long long wave = (long long)blockIdx.x * (MN_INST_THREADS / 64) + (threadIdx.x >> 6);
-  const long long c0 = wave * chunks_per_wave;
-  const long long c1 = min(c0 + (long long)chunks_per_wave, (long long)total_chunks);
+  const RowSpan span = row_walk_span(R, (long long)blockIdx.x * (MN_INST_THREADS / 64) + (threadIdx.x >> 6));
 
   auto load = [&](long long c, int* a, int* xo, int* yo) {
-    const int y = (int)(c / chunks_per_row);
-    const int x = ((int)(c - (long long)y * chunks_per_row) * 64 + lane) * V;
-    *xo = x; *yo = y;
+    row_walk_pixel(R, V, c, lane, xo, yo);
+    const int x = *xo, y = *yo;
 #pragma unroll
     for (int j = 0; j < V; j++) a[j] = 0;
-    if (x < W) {                                    // V = 4: W % 4 == 0, so x + 3 < W too
-      const int* p = mask + (size_t)y * W + x;
-      if constexpr (V == 4) {
-        const int4 t = *reinterpret_cast<const int4*>(p);
-        a[0] = t.x; a[1] = t.y; a[2] = t.z; a[3] = t.w;
-      } else {
-        a[0] = *p;
-      }
+    if (x < W) {
+      mn_walk_labels<V, true>(mask + (size_t)y * W + x, a);
 #pragma unroll
       for (int j = 0; j < V; j++) a[j] = ((unsigned)(a[j] - 1) < (unsigned)K) ? a[j] : 0;
     }
   };
 
   int nxt[V], nx = 0, ny = 0;
-  if (c0 < c1) load(c0, nxt, &nx, &ny);
-  for (long long c = c0; c < c1; c++) {
+  if (span.c0 < span.c1) load(span.c0, nxt, &nx, &ny);
+  for (long long c = span.c0; c < span.c1; c++) {
     int a[V];
 #pragma unroll
     for (int j = 0; j < V; j++) a[j] = nxt[j];
     const int x = nx, y = ny;
-    if (c + 1 < c1) load(c + 1, nxt, &nx, &ny);     // the next chunk's load is in flight over this chunk's work
+    if (c + 1 < span.c1) load(c + 1, nxt, &nx, &ny);     // the next chunk's load is in flight over this chunk's work
 
     int before = __shfl_up(a[V - 1], 1);
     if (lane == 0) before = -1;                      // (labels are >= 0 here: the chunk's first pixel is a head)
     bool head[V];
-    u64 b[V], any = 0;
 #pragma unroll
-    for (int j = 0; j < V; j++) {
-      head[j] = a[j] != (j == 0 ? before : a[j > 0 ? j - 1 : 0]);
-      b[j] = __ballot(head[j]);
-      any |= b[j];
-    }
-    // first pixel slot of the chunk, after this lane, that holds a head
-    const u64 later = any & ~((2ull << lane) - 1ull);     // (lane 63: 2 << 63 wraps to 0, the mask to all ones)
-    int next_in_chunk = 64 * V;
-    if (later) {
-      const int ln = __ffsll((long long)later) - 1;
-      int jn = V - 1;
-#pragma unroll
-      for (int j = V - 1; j >= 0; j--) if ((b[j] >> ln) & 1ull) jn = j;
-      next_in_chunk = ln * V + jn;
-    }
+    for (int j = 0; j < V; j++) head[j] = a[j] != (j == 0 ? before : a[j > 0 ? j - 1 : 0]);
+    const int next_head = mn_walk_next_head<V>(head, lane);
 #pragma unroll
     for (int j = 0; j < V; j++) {
       if (!head[j] || a[j] == 0) continue;
-      int end = next_in_chunk - lane * V;            // one past the run's last pixel, counted from this lane's first
-#pragma unroll
-      for (int j2 = V - 1; j2 > j; j2--) if (head[j2]) end = j2;
-      const int len = end - j;
+      const int len = mn_walk_run_end<V>(head, j, next_head) - j;
       // (a run of a label > 0 ends before the pixels past W, which read as 0: xs + len - 1 < W)
       mn_inst_run(sh, lds_rows, table, a[j], len, x + j, x + j + len - 1, y);
     }

@@ -19,7 +19,8 @@
 #pragma once
 
 #include "mn_device.h"
-#include "mn_kernels_cc.h"        // the streaming typed loaders (mn_ld_stream*_t), mn_ld_int4_unaligned
+#include "mn_kernels_cc.h"        // the streaming typed loaders (mn_ld_stream*_t)
+#include "mn_row_walk.h"
 
 #ifndef MN_MS_WORKGROUPS
 #define MN_MS_WORKGROUPS 1024     /* most workgroups of the pass = most slots of the partials buffer (4 per CU) */
@@ -43,9 +44,9 @@ struct MnMapScoreArgs {
   const int* truth;               // [N] label mask
   const int* truth_classes;       // [G] (may be null when G == 0)
   int H, W, C, O, G;
-  int chunks_per_row, total_chunks, chunks_per_wave, slots;
+  RowWalk walk;                   // walk.blocks: the grid, and the slots of the partials buffer
   unsigned long long* confusion;  // [C][C], added to
-  double* partials;               // [3 * O][slots]
+  double* partials;               // [3 * O][walk.blocks]
   int di[MN_MAX_OFFSETS];
   int dj[MN_MAX_OFFSETS];
 };
@@ -69,9 +70,8 @@ __device__ __forceinline__ void mn_ms_load(const void* base, size_t i, float* v)
   }
 }
 
-// The walk of mn_overlap_table_runs: a wave takes `chunks_per_wave` consecutive chunks; a chunk is 64 * V consecutive
-// pixels of ONE row, lane l holds pixels V*l .. V*l + V-1 of it (V > 1: W % V == 0, so a lane is wholly inside the
-// row or wholly past it).  Two passes over the wave's chunks, so that every map element is loaded once:
+// The walk of mn_row_walk.h, V = 8, 4 or 1 by the maps' width and bases (the truth mask is read unaligned), in two
+// passes over the wave's chunks, so that every map element is loaded once:
 //   1. the class planes, MN_MS_CG in flight: the running argmax per pixel (a later plane wins only when greater:
 //      the lowest index among equals), then one count per pixel at (truth class, predicted class);
 //   2. the sameness planes in groups of MN_MS_OG offsets: per offset of the group a lane keeps its two float64 sums
@@ -93,14 +93,12 @@ __global__ __launch_bounds__(MN_MS_THREADS) void mn_map_scores_pass(const MnMapS
     __syncthreads();
   }
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const long long wave = (long long)blockIdx.x * MN_MS_WAVES + wv;
-  const long long c0 = min(wave * (long long)A.chunks_per_wave, (long long)A.total_chunks);
-  const long long c1 = min(c0 + (long long)A.chunks_per_wave, (long long)A.total_chunks);
+  const RowSpan span = row_walk_span(A.walk, (long long)blockIdx.x * MN_MS_WAVES + wv);
 
   // ---- 1. class planes -> confusion counts ----
-  for (long long c = c0; c < c1; c++) {
-    const int y = (int)(c / A.chunks_per_row);
-    const int x = ((int)(c - (long long)y * A.chunks_per_row) * 64 + lane) * V;
+  for (long long c = span.c0; c < span.c1; c++) {
+    int x, y;
+    row_walk_pixel(A.walk, V, c, lane, &x, &y);
     const bool in = x < W;
     const size_t at = (size_t)y * W + (size_t)(in ? x : 0);
     float best[V];
@@ -122,15 +120,7 @@ __global__ __launch_bounds__(MN_MS_THREADS) void mn_map_scores_pass(const MnMapS
         }
       }
       int t[V];
-      if constexpr (V >= 4) {
-#pragma unroll
-        for (int h = 0; h < V / 4; h++) {
-          const int4 u = mn_ld_int4_unaligned(A.truth + at + 4 * h);
-          t[4 * h] = u.x; t[4 * h + 1] = u.y; t[4 * h + 2] = u.z; t[4 * h + 3] = u.w;
-        }
-      } else {
-        t[0] = A.truth[at];
-      }
+      mn_walk_labels<V, false>(A.truth + at, t);
 #pragma unroll
       for (int j = 0; j < V; j++) {
         // the label is held to 1..G BEFORE it forms an address: the mask is the caller's memory
@@ -166,9 +156,9 @@ __global__ __launch_bounds__(MN_MS_THREADS) void mn_map_scores_pass(const MnMapS
     int n_diff[MN_MS_OG];
 #pragma unroll
     for (int g = 0; g < MN_MS_OG; g++) { s_diff[g] = 0.0; s_all[g] = 0.0; n_diff[g] = 0; }
-    for (long long c = c0; c < c1; c++) {
-      const int y = (int)(c / A.chunks_per_row);
-      const int x = ((int)(c - (long long)y * A.chunks_per_row) * 64 + lane) * V;
+    for (long long c = span.c0; c < span.c1; c++) {
+      int x, y;
+      row_walk_pixel(A.walk, V, c, lane, &x, &y);
       if (x >= W) continue;                          // (no shuffle or barrier inside this loop)
       const size_t at = (size_t)y * W + (size_t)x;
       float v[MN_MS_OG][V];
@@ -176,15 +166,7 @@ __global__ __launch_bounds__(MN_MS_THREADS) void mn_map_scores_pass(const MnMapS
       for (int g = 0; g < MN_MS_OG; g++)
         if (g0 + g < O) mn_ms_load<DT, LG, V>(A.same, (size_t)(g0 + g) * N + at, v[g]);
       int t[V];
-      if constexpr (V >= 4) {
-#pragma unroll
-        for (int h = 0; h < V / 4; h++) {
-          const int4 u = mn_ld_int4_unaligned(A.truth + at + 4 * h);
-          t[4 * h] = u.x; t[4 * h + 1] = u.y; t[4 * h + 2] = u.z; t[4 * h + 3] = u.w;
-        }
-      } else {
-        t[0] = A.truth[at];
-      }
+      mn_walk_labels<V, false>(A.truth + at, t);
 #pragma unroll
       for (int g = 0; g < MN_MS_OG; g++) {
         if (g0 + g >= O) continue;
@@ -197,11 +179,7 @@ __global__ __launch_bounds__(MN_MS_THREADS) void mn_map_scores_pass(const MnMapS
         if (yy < (unsigned)H) {
           const int* row = A.truth + (size_t)yy * W;
           if (V >= 4 && xx < (unsigned)W && xx + V <= (unsigned)W) {
-#pragma unroll
-            for (int h = 0; h < V / 4; h++) {
-              const int4 u = mn_ld_int4_unaligned(row + xx + 4 * h);
-              nb[4 * h] = u.x; nb[4 * h + 1] = u.y; nb[4 * h + 2] = u.z; nb[4 * h + 3] = u.w;
-            }
+            mn_walk_labels<V, false>(row + xx, nb);
           } else {
 #pragma unroll
             for (int j = 0; j < V; j++)
@@ -241,7 +219,7 @@ __global__ __launch_bounds__(MN_MS_THREADS) void mn_map_scores_pass(const MnMapS
     double s = sh_part[0][i];
 #pragma unroll
     for (int q = 1; q < MN_MS_WAVES; q++) s += sh_part[q][i];
-    A.partials[(size_t)i * A.slots + blockIdx.x] = s;
+    A.partials[(size_t)i * A.walk.blocks + blockIdx.x] = s;
   }
   if (lds)
     for (int i = threadIdx.x; i < C * C; i += MN_MS_THREADS) {

@@ -16,6 +16,7 @@
 #pragma once
 
 #include "mn_device.h"
+#include "mn_row_walk.h"
 
 // Two constants of the pass; a variant build for tools/time_overlap_table.py may set them (-D...):
 #ifndef MN_OVL_LDS_DIM
@@ -44,20 +45,18 @@ __device__ __forceinline__ void mn_ovl_run(int* sh, int lds_p, int lds_g, int* _
     atomicAdd(table + (size_t)p * (size_t)(G + 1) + (size_t)g, len);
 }
 
-// The walk of mn_instance_table_runs over TWO masks: a wave walks `chunks_per_wave` consecutive chunks; a chunk is
-// 64 * V consecutive pixels of ONE row, lane l holds pixels V*l .. V*l + V-1 of it in both masks.  V = 4: one
-// 16-byte load per lane and mask (W % 4 == 0 and BOTH bases 16-byte aligned), V = 1: 4-byte loads, any W.
+// The walk of mn_row_walk.h over TWO masks, V = 4 or 1 (BOTH bases decide it), the next chunk's loads in flight
+// over this chunk's work.
 // A pixel is the head of a run when EITHER mask differs from the pixel before it (the lane before for a lane's
-// first pixel; the first pixel of a chunk is always a head); one ballot per pixel slot, and a head reads where its
-// run ends from those ballots, as there.  Only heads update the table, by the run's length.
+// first pixel; the first pixel of a chunk is always a head); a head reads where its run ends from
+// mn_walk_run_end.  Only heads update the table, by the run's length.
 // Labels are clamped BEFORE they form an address: a prediction label outside 0..K and a truth label outside 0..G
 // -- both masks are the caller's memory -- read as 0.  Pixels of the last chunk of a row past W read as -1 in both
 // masks: they end the run before them and are counted nowhere, so the entries sum to H * W.
 template <int V>
 __global__ __launch_bounds__(MN_OVL_THREADS) void mn_overlap_table_runs(const int* __restrict__ pred,
                                                                         const int* __restrict__ truth, int H, int W,
-                                                                        int K, int G, int chunks_per_row,
-                                                                        int total_chunks, int chunks_per_wave,
+                                                                        int K, int G, const RowWalk R,
                                                                         int* __restrict__ table) {
   __shared__ int sh[MN_OVL_LDS_COLS * MN_OVL_LDS_COLS];
   const int lds_p = min(K + 1, MN_OVL_LDS_DIM), lds_g = min(G + 1, MN_OVL_LDS_DIM);
@@ -66,26 +65,17 @@ __global__ __launch_bounds__(MN_OVL_THREADS) void mn_overlap_table_runs(const in
     __syncthreads();
   }
   const int lane = threadIdx.x & 63;
-  const long long wave = (long long)blockIdx.x * (MN_OVL_THREADS / 64) + (threadIdx.x >> 6);
-  const long long c0 = wave * chunks_per_wave;
-  const long long c1 = min(c0 + (long long)chunks_per_wave, (long long)total_chunks);
+  const RowSpan span = row_walk_span(R, (long long)blockIdx.x * (MN_OVL_THREADS / 64) + (threadIdx.x >> 6));
 
   auto load = [&](long long c, int* a, int* t) {
-    const int y = (int)(c / chunks_per_row);
-    const int x = ((int)(c - (long long)y * chunks_per_row) * 64 + lane) * V;
+    int x, y;
+    row_walk_pixel(R, V, c, lane, &x, &y);
 #pragma unroll
     for (int j = 0; j < V; j++) a[j] = t[j] = -1;
-    if (x < W) {                                    // V = 4: W % 4 == 0, so x + 3 < W too
+    if (x < W) {
       const size_t at = (size_t)y * W + x;
-      if constexpr (V == 4) {
-        const int4 u = *reinterpret_cast<const int4*>(pred + at);
-        const int4 v = *reinterpret_cast<const int4*>(truth + at);
-        a[0] = u.x; a[1] = u.y; a[2] = u.z; a[3] = u.w;
-        t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
-      } else {
-        a[0] = pred[at];
-        t[0] = truth[at];
-      }
+      mn_walk_labels<V, true>(pred + at, a);
+      mn_walk_labels<V, true>(truth + at, t);
 #pragma unroll
       for (int j = 0; j < V; j++) {
         a[j] = ((unsigned)a[j] <= (unsigned)K) ? a[j] : 0;
@@ -95,41 +85,25 @@ __global__ __launch_bounds__(MN_OVL_THREADS) void mn_overlap_table_runs(const in
   };
 
   int na[V], nt[V];
-  if (c0 < c1) load(c0, na, nt);
-  for (long long c = c0; c < c1; c++) {
+  if (span.c0 < span.c1) load(span.c0, na, nt);
+  for (long long c = span.c0; c < span.c1; c++) {
     int a[V], t[V];
 #pragma unroll
     for (int j = 0; j < V; j++) { a[j] = na[j]; t[j] = nt[j]; }
-    if (c + 1 < c1) load(c + 1, na, nt);            // the next chunk's loads are in flight over this chunk's work
+    if (c + 1 < span.c1) load(c + 1, na, nt);            // the next chunk's loads are in flight over this chunk's work
 
     int before_a = __shfl_up(a[V - 1], 1), before_t = __shfl_up(t[V - 1], 1);
     if (lane == 0) before_a = -2;                    // (labels are >= -1 here: the chunk's first pixel is a head)
     bool head[V];
-    u64 b[V], any = 0;
 #pragma unroll
-    for (int j = 0; j < V; j++) {
+    for (int j = 0; j < V; j++)
       head[j] = a[j] != (j == 0 ? before_a : a[j > 0 ? j - 1 : 0]) ||
                 t[j] != (j == 0 ? before_t : t[j > 0 ? j - 1 : 0]);
-      b[j] = __ballot(head[j]);
-      any |= b[j];
-    }
-    // first pixel slot of the chunk, after this lane, that holds a head
-    const u64 later = any & ~((2ull << lane) - 1ull);     // (lane 63: 2 << 63 wraps to 0, the mask to all ones)
-    int next_in_chunk = 64 * V;
-    if (later) {
-      const int ln = __ffsll((long long)later) - 1;
-      int jn = V - 1;
-#pragma unroll
-      for (int j = V - 1; j >= 0; j--) if ((b[j] >> ln) & 1ull) jn = j;
-      next_in_chunk = ln * V + jn;
-    }
+    const int next_head = mn_walk_next_head<V>(head, lane);
 #pragma unroll
     for (int j = 0; j < V; j++) {
       if (!head[j] || a[j] < 0) continue;            // (a[j] < 0: past W, in both masks)
-      int end = next_in_chunk - lane * V;            // one past the run's last pixel, counted from this lane's first
-#pragma unroll
-      for (int j2 = V - 1; j2 > j; j2--) if (head[j2]) end = j2;
-      mn_ovl_run(sh, lds_p, lds_g, table, G, a[j], t[j], end - j);
+      mn_ovl_run(sh, lds_p, lds_g, table, G, a[j], t[j], mn_walk_run_end<V>(head, j, next_head) - j);
     }
   }
 

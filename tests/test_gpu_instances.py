@@ -17,7 +17,8 @@ SHAPES = [(1, 1),        # one pixel
           (7, 67),       # odd W: 4-byte loads, a run across the wave boundary
           (33, 257),
           (64, 1030),    # W % 4 != 0 and wider than one workgroup's share of a row
-          (48, 256)]     # W % 4 == 0: 16-byte loads
+          (48, 256),     # W % 4 == 0: 16-byte loads
+          (345, 516)]    # 16-byte loads AND two chunks per wave (three per row: a wave's pair straddles a row end)
 
 
 @functools.lru_cache(maxsize=None)

@@ -20,7 +20,8 @@ SHAPES = [(1, 1),
           (33, 257),     # 4-byte loads, the last chunk of a row reaches past W
           (48, 256),     # 16-byte loads, one chunk per row
           (32, 1028),    # 16-byte loads, the last chunk of a row partly past W
-          (64, 1030)]    # 4-byte loads, several chunks per row
+          (64, 1030),    # 4-byte loads, several chunks per row
+          (345, 516)]    # 16-byte loads AND two chunks per wave (three per row: a wave's pair straddles a row end)
 KINDS = ["blobs", "noise", "pred_rows", "truth_rows"]
 
 
