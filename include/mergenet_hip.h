@@ -107,6 +107,9 @@ enum mn_debug_flags {
                                           events on its own dispatch (round 2's first form: measures dispatch gap + kernel) */
   MN_DEBUG_SWEEP16_4PX = 256,          /* a 16-bit map's sweep takes 4 pixels per lane (8-byte loads) where it would take 8
                                           (16-byte loads) -- same results, for the measurement of the two forms */
+  MN_DEBUG_TILES_1PX = 1024,           /* the tile stage of the labelling takes one pixel per lane (mn_cc_tiles) where it
+                                          would take four (mn_cc_tiles4: W % 4 == 0, 16-byte aligned arrays) -- same
+                                          parent[] bit for bit, the yardstick of the four-pixel kernel inside one build */
   MN_DEBUG_SWEEP_FULL_FORM = 512       /* the sweep of components mode leaves the FULL form of its outputs (two mask words
                                           per pixel, per-lane class log-products for every lane) where the default path
                                           takes the lean form (one packed word for up to 16 offsets, one record per uniform

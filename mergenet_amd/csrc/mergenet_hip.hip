@@ -979,6 +979,16 @@ static void cc_core_masks(mn_context* c, const ImgParams& P, const CcPlan& pl, h
 // block's critical path and the tile layout reads 256-byte row segments.)
 static void cc_label(mn_context* c, const ImgParams& P, const CcPlan& pl, hipStream_t st) {
   const int kh = pl.unit.kh, kv = pl.unit.kv, dv = pl.unit.dv;
+  // Four pixels per lane (mn_cc_tiles4) wherever a lane's pixels are one 16-byte access of the masks, of parent[] and
+  // of the candidates; MN_DEBUG_TILES_1PX keeps the one-pixel kernel (the yardstick inside one build).  (Replay: the
+  // key holds the options and the width, and a recorded graph holds the context's arrays by address, so a graph is
+  // never replayed for the other kernel.)
+  const uintptr_t bases = reinterpret_cast<uintptr_t>(pl.lbits) | reinterpret_cast<uintptr_t>(c->parent) |
+                          reinterpret_cast<uintptr_t>(c->matched);
+  if (P.W % 4 == 0 && (bases & 15) == 0 && !(c->debug_flags & MN_DEBUG_TILES_1PX))
+    hipLaunchKernelGGL(mn_cc_tiles4, pl.tiles, dim3(256), 0, st, P, pl.lbits, c->parent, kh, kv, dv,
+                       c->osize, c->lp_acc, pl.clsmin, pl.clsmax, c->matched);
+  else
   hipLaunchKernelGGL(mn_cc_tiles, pl.tiles, dim3(MN_CC_TILE_ROWS * 64), 0, st, P, pl.lbits, c->parent, kh, kv, dv,
                      c->osize, c->lp_acc, pl.clsmin, pl.clsmax, c->matched);   // `matched` is free in this mode
   if (kh >= 0 || kv >= 0)

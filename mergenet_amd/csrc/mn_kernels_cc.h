@@ -21,7 +21,8 @@
 //                  everything after this kernel works on the masks (mn_cc_cross reads the values of the
 //                  negative edges again: 1.2 M of 21 M at 1024x2048);
 //   mn_cc_tiles    16 x 64-pixel tiles labelled in LDS over the two unit offsets (mask bits); flat
-//                  within the tile; accumulators of the tile roots cleared;
+//                  within the tile; accumulators of the tile roots cleared (mn_cc_tiles4: the same with four
+//                  pixels per lane, wherever W % 4 == 0 and the arrays are 16-byte aligned);
 //   mn_cc_borders  unit-offset edges across tile borders; mn_cc_flatten  parent[p] = root, once;
 //   mn_cc_hook     lock-free union-find over the other offsets (mask bits), root = lowest pixel id
 //                  of the component;
@@ -45,6 +46,7 @@ static_assert(MN_MAX_OFFSETS <= 32, "edge masks are 32-bit words: one bit per of
 #include "mn_device.h"
 #include "mn_kernels_merge.h"
 #include "mn_sweep_form.h"      /* LeanOut, MN_CC_SIGN_THREADS: what the host decides about a launch of the sweep */
+#include "mn_tile_runs.h"       /* run starts from a tile row's link mask (mn_cc_tiles4) */
 
 #define MN_LP_FIX 16777216.0     /* 2^24: fixed-point scale of class log-prob sums.  |log p| <= 16, so a
                                     value fits an int32 (ONE v_cvt_i32_f32; a float -> int64 conversion
@@ -652,6 +654,125 @@ __device__ __forceinline__ void mn_cc_wave_union(int* __restrict__ parent, bool 
     }
     todo &= ~__ballot(mine);
   }
+}
+
+// mn_cc_wave_union for the tile stage's four rows per wave: one lane per distinct pair of roots again, but the lanes
+// are chosen first -- the key travels by v_readlane, so the choice costs no LDS trip -- and then hook TOGETHER: the
+// unions of a wave's four rows cost one atomic's latency, not four.  (The hook itself is the lock-free one above,
+// which lanes of different waves run side by side anyway.)
+__device__ __forceinline__ void mn_cc_wave_union_together(int* __restrict__ parent, bool want, int a, int b) {
+  const int lane = threadIdx.x & 63;
+  u64 todo = __ballot(want);
+  if (!todo) return;                                    // (uniform)
+  const u64 key = mn_key(a, b);
+  bool lead = false;
+  while (todo) {
+    const int first = __ffsll((long long)todo) - 1;
+    const u64 k0v = ((u64)(unsigned)__builtin_amdgcn_readlane((int)(key >> 32), first) << 32) |
+                    (u64)(unsigned)__builtin_amdgcn_readlane((int)(key & 0xFFFFFFFFull), first);
+    lead = lead || lane == first;
+    todo &= ~__ballot(want && key == k0v);
+  }
+  if (lead) {
+    while (a != b) {                                    // hook the larger root under the smaller
+      if (a < b) { const int t = a; a = b; b = t; }
+      const int old = atomicMin(&parent[a], b);
+      if (old == a) break;
+      a = mn_cc_find(parent, old);
+      b = mn_cc_find(parent, b);
+    }
+  }
+}
+
+// The tile stage with FOUR pixels per lane: the same 16 x 64 tile, grid and 4 KB of LDS, a block of 256 lanes.  A
+// wave owns four tile rows, a DPP row of 16 lanes one tile row, a lane the four pixels 4 * l16 .. 4 * l16 + 3 of it
+// (W % 4 == 0 and 16-byte aligned bits / parent / cand: the host's rule, cc_label; a lane is then wholly inside or
+// wholly outside the image, and LDS slot 4 * t + j is pixel j of lane t).  mn_cc_tiles spends its time issuing
+// instructions; here four pixels share them:
+//  1. rows: the lane's link nibble L, the row's 64-bit link mask as the OR over the DPP row of L << 4 * l16 (two
+//     32-bit halves, the moves of mn_group_sum32<16>: the bits are disjoint, so the sum is the OR -- no ballot, no
+//     LDS), the four run starts (mn_tile_runs.h), ONE 16-byte LDS store;
+//  2. columns: a request (own label, label of the pixel in row + dv) per pixel with bit kv whose neighbour row is
+//     inside the tile; dropped where the pixel to its left in the lane asked and both labels read from lab[] equal
+//     that pixel's (the two pixels are then in the same two sets: the union is the same one); the rest through
+//     mn_cc_find2 (both chases step together) and one lane per distinct pair of roots of the wave
+//     (mn_cc_wave_union_together), larger root under smaller, so a tile component's root stays its first pixel;
+//  3. behind the second barrier the final chase (skipped where the label equals the left pixel's), parent as one
+//     int4, cand as one uchar4, the roots' accumulators cleared as mn_cc_tiles clears them.
+// parent[], cand[] and the cleared slots are functions of the masks alone and bit for bit what mn_cc_tiles leaves.
+__global__ __launch_bounds__(256) void mn_cc_tiles4(ImgParams P, const unsigned* __restrict__ bits,
+                                                    int* __restrict__ parent, int kh, int kv, int dv,
+                                                    int* __restrict__ osize, i64* __restrict__ lp_acc,
+                                                    int* __restrict__ clsmin, int* __restrict__ clsmax,
+                                                    unsigned char* __restrict__ cand) {
+  __shared__ __attribute__((aligned(16))) int lab[MN_CC_TILE_ROWS * 64];
+  static_assert(MN_CC_TILE_ROWS == 16, "four waves of four tile rows");
+  const int t = threadIdx.x, l16 = t & 15, i = t >> 4;   // tile row i, tile columns 4 * l16 ..
+  const int r = (int)blockIdx.y * MN_CC_TILE_ROWS + i, c = (int)blockIdx.x * 64 + 4 * l16;
+  const bool in = r < P.H && c < P.W;
+  const int p = in ? r * P.W + c : 0;
+  const uint4 b = in ? *reinterpret_cast<const uint4*>(bits + p) : make_uint4(0u, 0u, 0u, 0u);
+  unsigned L = 0u, V = 0u;                              // a set bit implies an in-bounds neighbour
+  if (kh >= 0) {
+    L = ((b.x >> kh) & 1u) | (((b.y >> kh) & 1u) << 1) | (((b.z >> kh) & 1u) << 2) | (((b.w >> kh) & 1u) << 3);
+    if (l16 == 15) L &= 7u;                             // next pixel in the same tile row
+  }
+  const int ni = i + dv;
+  if (kv >= 0 && ni >= 0 && ni < MN_CC_TILE_ROWS)
+    V = ((b.x >> kv) & 1u) | (((b.y >> kv) & 1u) << 1) | (((b.z >> kv) & 1u) << 2) | (((b.w >> kv) & 1u) << 3);
+  const unsigned nib = L << (4 * (l16 & 7));
+  const unsigned lo = (unsigned)mn_group_sum32<16>((int)(l16 < 8 ? nib : 0u));
+  const unsigned hi = (unsigned)mn_group_sum32<16>((int)(l16 < 8 ? 0u : nib));
+  int s[4];
+  mn_run_starts4(((u64)hi << 32) | (u64)lo, l16, L, s);
+  reinterpret_cast<int4*>(lab)[t] = make_int4(i * 64 + s[0], i * 64 + s[1], i * 64 + s[2], i * 64 + s[3]);
+  __syncthreads();
+  if (__ballot(V != 0u)) {                              // (uniform)
+    int own[4] = {0, 0, 0, 0}, nb[4] = {0, 0, 0, 0};
+    if (V) {
+      const int4 o = reinterpret_cast<const int4*>(lab)[t], n = reinterpret_cast<const int4*>(lab)[t + 16 * dv];
+      own[0] = o.x; own[1] = o.y; own[2] = o.z; own[3] = o.w;
+      nb[0] = n.x; nb[1] = n.y; nb[2] = n.z; nb[3] = n.w;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      bool ask = (V >> j) & 1u;
+      if (j > 0 && ((V >> (j - 1)) & 1u) && own[j] == own[j - 1] && nb[j] == nb[j - 1]) ask = false;
+      int a = 0, bb = 0;
+      bool want = false;
+      if (ask) {                                        // (the labels read are ancestors: the roots are the pixels')
+        mn_cc_find2(lab, own[j], nb[j], &a, &bb);
+        want = a != bb;
+      }
+      mn_cc_wave_union_together(lab, want, a, bb);
+    }
+  }
+  __syncthreads();
+  if (!in) return;
+  const int4 f = reinterpret_cast<const int4*>(lab)[t];
+  int x[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    if (j > 0 && (j == 1 ? f.y == f.x : j == 2 ? f.z == f.y : f.w == f.z)) { x[j] = x[j - 1]; continue; }
+    int y = x[j], n;
+    while ((n = lab[y]) != y) y = n;
+    x[j] = y;
+  }
+  const int base = (int)blockIdx.y * MN_CC_TILE_ROWS * P.W + (int)blockIdx.x * 64;
+  *reinterpret_cast<int4*>(parent + p) =
+      make_int4(base + (x[0] >> 6) * P.W + (x[0] & 63), base + (x[1] >> 6) * P.W + (x[1] & 63),
+                base + (x[2] >> 6) * P.W + (x[2] & 63), base + (x[3] >> 6) * P.W + (x[3] & 63));
+  uchar4 cd;                                            // the only pixels that can be a component root
+  cd.x = x[0] == 4 * t; cd.y = x[1] == 4 * t + 1; cd.z = x[2] == 4 * t + 2; cd.w = x[3] == 4 * t + 3;
+  *reinterpret_cast<uchar4*>(cand + p) = cd;
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+    if (x[j] == 4 * t + j) {
+      osize[p + j] = 0;                                 // (sizes are only ever read at roots)
+      for (int cc = 0; cc < P.C; cc++) lp_acc[(size_t)cc * P.N + p + j] = 0;
+      clsmin[p + j] = 255;
+      clsmax[p + j] = 0;
+    }
 }
 
 // Border stage: after mn_cc_tiles the only unit-offset edges still open are those that cross a

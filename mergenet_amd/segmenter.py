@@ -39,6 +39,7 @@ MN_DEBUG_LEAN_EVENTS, MN_DEBUG_REPLAY = 16, 32
 MN_DEBUG_SWEEP_EVENT_PACKETS = 128   # the sweep is timed by an event packet before and behind it
 MN_DEBUG_SWEEP16_4PX = 256    # a 16-bit map's sweep takes 4 pixels per lane (8-byte loads) where it would take 8
 MN_DEBUG_SWEEP_FULL_FORM = 512   # the sweep of components mode leaves the full form of its outputs, not the lean one
+MN_DEBUG_TILES_1PX = 1024   # the labelling's tile stage takes one pixel per lane (mn_cc_tiles) where it would take four
 MN_DTYPE_F32, MN_DTYPE_F16, MN_DTYPE_BF16 = 0, 1, 2   # enum mn_dtype: element type of the maps (*_t entry points)
 MN_MAPS_LOGITS = 0x100   # or-ed into that dtype: both maps hold logits, the kernels take the sigmoid on load
 MN_ERR_ARGUMENT = -1
