@@ -700,6 +700,61 @@ int mn_map_scores_device(mn_context* ctx, const void* d_class_pred, int class_di
                          const int* d_truth_classes, long long* d_confusion /* [C*C] */,
                          double* d_sums /* [3*O] */, int accumulate, void* stream);
 
+/* The training criterion from the label mask, on the device: loss and gradient in one pass.  Every recipe of the
+ * reference trains both parts of the network's output with torch.nn.BCEWithLogitsLoss against target planes
+ * (egs/cityscape/local/train.py:183-195, egs/coco/local/train.py:145,156; cls_loss + alpha * ofs_loss and its backward
+ * pass in utils/train_utils.py:42-79,145-180; the targets of utils/dataset.py:259-277 and :419-429).  Here ONE pass
+ * reads each logit once, looks its target up in the label mask that mn_map_scores_device takes, adds the terms up
+ * and -- if asked -- stores each gradient element once; no target plane is written or read.  One image per call.
+ *   d_class_logits [num_classes][height * width] and d_same_logits [offset_dim][height * width]: float32, float16 or
+ *   bfloat16 (`dtype`: MN_DTYPE_*; the maps are logits by definition, MN_MAPS_LOGITS is not accepted).
+ *   x: the element widened exactly to float32.
+ *   Truth class of a pixel: 0 for truth label 0, d_truth_classes[g - 1] for label g in 1..num_truth; a label outside
+ *   0..num_truth reads as 0.  The labels are compared as they stand in the mask for the offset planes.
+ *   Target y of class plane q: 1 where the truth class is q, else 0.  Target y of offset plane k = (di, dj): 0 where
+ *   (r + di, c + dj) is inside the image and carries another truth label ("different"), else 1 ("same": a neighbour
+ *   outside the image counts as same).
+ *   Term of an element: softplus(z) with z = y ? -x : x, computed in float32 as
+ *     fmaxf(z, 0) + log1pf(expf(-fabsf(z)))
+ *   -- PyTorch's stable form of BCEWithLogits; x - x * y is exact for y in {0, 1}, so it is the sign flip and
+ *   nothing cancels.  expf(-|x|) is a normal float32 up to |x| of about 87; beyond that a term that should be tiny
+ *   falls through the subnormals to 0 and is no longer accurate to a few ulp (a term near |x| still is).
+ *   Ignore class: a pixel whose truth class lies outside 0..num_classes-1 is left out of the class loss and gets
+ *   gradient 0 on all class planes (the store is made); it takes part in the offset planes as any other pixel.
+ *   d_sums float64 [2 + O]:
+ *     d_sums[0]     = sum of the class terms over the kept pixels and the num_classes planes
+ *     d_sums[1 + k] = sum of the terms of offset plane k over all pixels
+ *     d_sums[1 + O] = the number of kept pixels, an exact integer
+ *   each term widened to float64 before it is added.
+ *   Gradient: d_grad_class / d_grad_same have the element type and layout of the maps; either may be NULL (both NULL:
+ *   the validation loss, nothing but the sums is written).  Element = (s - y) * scale in float32 with s =
+ *   1.0f / (1.0f + expf(-x)) and scale = scale_class / scale_same, rounded to nearest even into the element type.  A
+ *   gradient buffer must not overlap a map.  A float16 gradient scaled by 1 / (number of elements) underflows: scale
+ *   it up (loss scaling) or use bfloat16.
+ * The sums of a call are bit-identical from run to run, the same whether or not a gradient is written and wherever
+ * the maps and gradients lie in memory: no floating-point atomic is used, which pixels a lane adds up follows
+ * (height, width, element type) only, every workgroup writes its partial sums to its own slot of a buffer of the
+ * context and a second launch adds the slots in a fixed order.  accumulate != 0: the image's 2 + O totals are ADDED to
+ * what d_sums holds (one IEEE addition per total) -- the totals of a batch or of a validation loop, with no
+ * synchronisation between images; accumulate == 0: they are stored.
+ * Accesses: 4 elements per lane and 16-byte load and store for float32, 8 for 16-bit maps, where the width is a
+ * multiple of that and ALL of the up to four map and gradient bases are 16-byte aligned; 4 per lane and 8-byte
+ * accesses for 16-bit maps of width % 4 == 0 and width % 8 != 0 aligned to 8; otherwise single elements, any width
+ * and any base.  The truth mask is read through the cache.
+ * Any image size (not held to the context's capacity).  0 <= num_classes <= MN_MAX_CLASSES and 0 <= offset_dim <=
+ * MN_MAX_OFFSETS, not both 0: num_classes == 0 (d_class_logits may be NULL) is offset-only training, offset_dim == 0
+ * (d_same_logits and offset_list may be NULL) class-only.  num_truth >= 0; d_truth_classes may be NULL when num_truth
+ * == 0.  offset_list is a HOST array of (di, dj) pairs, any values, (0, 0) and duplicates included.
+ * MN_ERR_ARGUMENT: a null pointer that is needed, a non-positive size, height * width > INT_MAX, img_width > 2^30,
+ * a count out of range, both counts 0, an unknown dtype or one with MN_MAPS_LOGITS, a scale that is not finite;
+ * nothing is launched then.  The partials buffer is the one of mn_map_scores_device (allocated by the first call of
+ * either): keep the calls of both on one context on one stream.  Enqueues on `stream` only: no host synchronisation. */
+int mn_mask_bce_device(mn_context* ctx, const void* d_class_logits, const void* d_same_logits,
+                       int dtype /* MN_DTYPE_* */, int img_width, int img_height, int num_classes, int offset_dim,
+                       const int* offset_list, const int* d_truth, int num_truth, const int* d_truth_classes,
+                       void* d_grad_class, void* d_grad_same, float scale_class, float scale_same,
+                       double* d_sums /* [2+O] */, int accumulate, void* stream);
+
 /* Wire format of the multi-GPU mask exchange (the all-gather of final instance masks the north
  * star asks for; the reference has no exchange, its jobs write files: segment.py:59-61).  d_wire is
  * int16 [n_pixels + 1 + max_instances + 4]: the labels (0..K), K, the classes of labels 1..K

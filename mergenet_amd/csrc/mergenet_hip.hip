@@ -25,6 +25,7 @@
 #include "mn_kernels_eval.h"
 #include "mn_kernels_cc.h"
 #include "mn_kernels_mapscore.h"
+#include "mn_kernels_loss.h"
 #include "mn_kernels_rle.h"
 #include "mn_kernels_tiles.h"
 #include "mn_sweep_form.h"
@@ -3016,6 +3017,71 @@ extern "C" int mn_map_scores_device(mn_context* c, const void* d_class_pred, int
     if (logits) map_scores_launch<MN_DTYPE_BF16, true>(v, g, st, A); else map_scores_launch<MN_DTYPE_BF16, false>(v, g, st, A);
   }
   hipLaunchKernelGGL(mn_map_scores_finish, dim3(3 * O), dim3(64), 0, st, (const double*)c->ms_partials, slots,
+                     d_sums, accumulate);
+  MN_HIP(hipGetLastError());
+  g_last_status = MN_OK;
+  return MN_OK;
+}
+
+// ---- the training criterion from the label mask (mn_kernels_loss.h) ---------------------------------------
+// Enqueues only: no host synchronisation, no copy.  Nothing of the segmentation path runs here.
+template <int DT>
+static void mask_bce_launch(int p, dim3 g, hipStream_t st, const MnMaskBceArgs& A) {
+  const dim3 b(MN_BCE_THREADS);
+  if (p == 8) {
+    if constexpr (DT != MN_DTYPE_F32) hipLaunchKernelGGL((mn_mask_bce_pass<DT, 8>), g, b, 0, st, A);
+  } else if (p == 4) {
+    hipLaunchKernelGGL((mn_mask_bce_pass<DT, 4>), g, b, 0, st, A);
+  } else {
+    hipLaunchKernelGGL((mn_mask_bce_pass<DT, 1>), g, b, 0, st, A);
+  }
+}
+
+extern "C" int mn_mask_bce_device(mn_context* c, const void* d_class_logits, const void* d_same_logits, int dtype,
+                                  int img_width, int img_height, int num_classes, int offset_dim,
+                                  const int* offset_list, const int* d_truth, int num_truth,
+                                  const int* d_truth_classes, void* d_grad_class, void* d_grad_same,
+                                  float scale_class, float scale_same, double* d_sums, int accumulate, void* stream) {
+  const int H = img_height, W = img_width, C = num_classes, O = offset_dim, G = num_truth;
+  if (!c || !d_truth || !d_sums || H <= 0 || W <= 0 || C < 0 || C > MN_MAX_CLASSES || O < 0 || O > MN_MAX_OFFSETS ||
+      C + O == 0 || (C > 0 && !d_class_logits) || (O > 0 && (!d_same_logits || !offset_list)) || G < 0 ||
+      (G > 0 && !d_truth_classes) || (size_t)H * (size_t)W > (size_t)INT_MAX || W > MN_MS_MAX_WIDTH ||
+      !dtype_ok(dtype, false) || !std::isfinite(scale_class) || !std::isfinite(scale_same)) {
+    g_last_status = MN_ERR_ARGUMENT;
+    return MN_ERR_ARGUMENT;
+  }
+  MN_HIP(hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (!c->ms_partials) MN_HIP(dev_alloc(c, &c->ms_partials, (size_t)MN_MS_VALUES * MN_MS_WORKGROUPS));
+
+  MnMaskBceArgs A;
+  memset(&A, 0, sizeof(A));
+  A.cls = C ? d_class_logits : nullptr; A.same = O ? d_same_logits : nullptr;
+  A.gcls = C ? d_grad_class : nullptr; A.gsame = O ? d_grad_same : nullptr;
+  A.truth = d_truth; A.truth_classes = d_truth_classes;
+  A.H = H; A.W = W; A.C = C; A.O = O; A.G = G;
+  A.scale_cls = scale_class; A.scale_same = scale_same;
+  A.partials = c->ms_partials;
+  for (int k = 0; k < O; k++) {   // held to -H..H and -W..W, as in mn_map_scores_device: row + di and column + dj stay ints
+    A.di[k] = std::max(-H, std::min(H, offset_list[2 * k]));
+    A.dj[k] = std::max(-W, std::min(W, offset_list[2 * k + 1]));
+  }
+  // The grid by the rule of mn_map_scores_device: a function of (H, W, element type) alone.  So are the pixels a lane
+  // holds (row_walk_v without bases); the four bases only decide between wide accesses and single elements.
+  const int dt = dtype & 0xFF;
+  const int elem = dt == MN_DTYPE_F32 ? 4 : 2;
+  const int widest = 16 / elem;
+  const long long nominal = (long long)H * ((W + 64 * widest - 1) / (64 * widest));
+  const long long want = (nominal + MN_BCE_WAVES * MN_MS_MIN_CHUNKS - 1) / (MN_BCE_WAVES * MN_MS_MIN_CHUNKS);
+  const int slots = (int)std::min<long long>(MN_MS_WORKGROUPS, want);
+  const int p = row_walk_v(W, elem, nullptr);
+  A.wide = std::min(row_walk_v(W, elem, A.cls, A.same), row_walk_v(W, elem, A.gcls, A.gsame)) == p ? 1 : 0;
+  A.walk = row_walk_fixed(H, W, p, slots, MN_BCE_WAVES);
+  const dim3 g((unsigned)slots);
+  if (dt == MN_DTYPE_F32) mask_bce_launch<MN_DTYPE_F32>(p, g, st, A);
+  else if (dt == MN_DTYPE_F16) mask_bce_launch<MN_DTYPE_F16>(p, g, st, A);
+  else mask_bce_launch<MN_DTYPE_BF16>(p, g, st, A);
+  hipLaunchKernelGGL(mn_map_scores_finish, dim3(2 + O), dim3(64), 0, st, (const double*)c->ms_partials, slots,
                      d_sums, accumulate);
   MN_HIP(hipGetLastError());
   g_last_status = MN_OK;

@@ -45,6 +45,7 @@ static_assert(MN_MAX_OFFSETS <= 32, "edge masks are 32-bit words: one bit per of
 
 #include "mn_device.h"
 #include "mn_kernels_merge.h"
+#include "mn_kernels_prepare.h" /* mn_narrow_f16 / mn_narrow_bf16: the typed store (mn_st_stream_t) */
 #include "mn_sweep_form.h"      /* LeanOut, MN_CC_SIGN_THREADS: what the host decides about a launch of the sweep */
 #include "mn_tile_runs.h"       /* run starts from a tile row's link mask (mn_cc_tiles4) */
 
@@ -157,6 +158,37 @@ __device__ __forceinline__ void mn_st_stream(int* p, int v) {
 }
 __device__ __forceinline__ void mn_st_stream(uint4* p, uint4 v) {
   *p = v;
+}
+// The typed store beside the typed loaders: V float32 values to elements i .. i+V-1 of a map of DT, narrowed to
+// nearest even (mn_narrow_*), in ONE vector store -- 16 bytes for V = 8 and for V = 4 of float32, 8 bytes for V = 4 of
+// 16-bit elements, which the element index must be aligned to -- or one element (V = 1).  Plain C++ stores, like
+// the two above.
+template <int DT>
+__device__ __forceinline__ unsigned mn_narrow2(float a, float b) {
+  if (DT == MN_DTYPE_F16) return (unsigned)mn_narrow_f16(a) | ((unsigned)mn_narrow_f16(b) << 16);
+  return (unsigned)mn_narrow_bf16(a) | ((unsigned)mn_narrow_bf16(b) << 16);
+}
+template <int DT, int V>
+__device__ __forceinline__ void mn_st_stream_t(void* base, size_t i, const float* v) {
+  static_assert(V == 1 || V == 4 || (V == 8 && DT != MN_DTYPE_F32), "one element, or one 8- or 16-byte store");
+  if constexpr (DT == MN_DTYPE_F32) {
+    if constexpr (V == 4) *reinterpret_cast<float4*>(static_cast<float*>(base) + i) = make_float4(v[0], v[1], v[2], v[3]);
+    else static_cast<float*>(base)[i] = v[0];
+  } else {
+    mn_u16* p = static_cast<mn_u16*>(base) + i;
+    if constexpr (V == 8) {
+      mn_u4v t;
+      t.x = mn_narrow2<DT>(v[0], v[1]); t.y = mn_narrow2<DT>(v[2], v[3]);
+      t.z = mn_narrow2<DT>(v[4], v[5]); t.w = mn_narrow2<DT>(v[6], v[7]);
+      *reinterpret_cast<mn_u4v*>(p) = t;
+    } else if constexpr (V == 4) {
+      mn_u2v t;
+      t.x = mn_narrow2<DT>(v[0], v[1]); t.y = mn_narrow2<DT>(v[2], v[3]);
+      *reinterpret_cast<mn_u2v*>(p) = t;
+    } else {
+      *p = DT == MN_DTYPE_F16 ? mn_narrow_f16(v[0]) : mn_narrow_bf16(v[0]);
+    }
+  }
 }
 
 // (a 16-bit map is always clipped on load: its PLAIN form is the clip alone, no same_different_bias; so are

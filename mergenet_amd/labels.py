@@ -559,3 +559,75 @@ def offset_iou(sums):
     with np.errstate(divide="ignore", invalid="ignore"):
         iou = s[0] / (s[1] + s[2] - s[0])
     return iou, iou.mean()
+
+
+# ---- the training criterion from the label mask: the numpy statement of Merger.mask_bce ---------------------------
+# (torch.nn.BCEWithLogitsLoss of the reference's recipes on the class planes and the offset planes, as sums, and its
+# gradient; the targets are those of utils/dataset.py:259-277 and :419-429, looked up in the label mask)
+
+def _truth_class_of(truth, truth_classes, num_truth: int):
+    """Per pixel: 0 for label 0 and for a label outside 0..num_truth, ``truth_classes[g - 1]`` for label g."""
+    t = np.asarray(truth).astype(np.int64)
+    G = int(num_truth)
+    by_label = np.zeros(G + 1, np.int64)
+    if G:
+        by_label[1:] = np.asarray(truth_classes).astype(np.int64).reshape(-1)[:G]
+    return by_label[np.where((t < 0) | (t > G), 0, t)]
+
+
+def _different(t, di: int, dj: int):
+    """bool [H,W]: (r + di, c + dj) is inside the image and carries another label than (r, c)."""
+    H, W = t.shape
+    diff = np.zeros((H, W), bool)
+    r0, r1 = max(0, -di), min(H, H - di)
+    c0, c1 = max(0, -dj), min(W, W - dj)
+    if r0 < r1 and c0 < c1:
+        diff[r0:r1, c0:c1] = t[r0:r1, c0:c1] != t[r0 + di:r1 + di, c0 + dj:c1 + dj]
+    return diff
+
+
+def mask_bce(class_logits, same_logits, offsets, truth, truth_classes, num_truth: int, scale_class: float = 1.0,
+             scale_same: float = 1.0):
+    """(sums float64 [2+O], grad_class float64 [C,H,W], grad_same float64 [O,H,W]) of one image.
+
+    x is the element widened exactly to float32; everything after that is float64.  Truth class: as in
+    :func:`map_scores`.  Target y of class plane q: 1 where the truth class is q; of offset plane k = (di, dj): 0
+    where (r + di, c + dj) is inside the image and carries another truth label (the labels as they stand), else 1.
+    Term: ``softplus(z) = logaddexp(0, z)`` with z = -x where y is 1 and x where it is 0 -- ``BCEWithLogitsLoss`` per
+    element.  A pixel whose truth class lies outside 0..C-1 (an ignore class) has no class term and class gradient
+    0; the offset planes take it as any other pixel.  ``sums[0]``: the class terms of the kept pixels over the C
+    planes, ``sums[1 + k]``: the terms of offset plane k, ``sums[1 + O]``: the number of kept pixels; each the
+    correctly rounded sum (``math.fsum``).  Gradient: ``(expit(x) - y) * scale``.  Either map may be None or have
+    no planes."""
+    t = np.asarray(truth).astype(np.int64)
+    H, W = t.shape
+    cl = np.zeros((0, H, W), np.float32) if class_logits is None else np.asarray(class_logits).astype(np.float32)
+    sl = np.zeros((0, H, W), np.float32) if same_logits is None else np.asarray(same_logits).astype(np.float32)
+    C, O = cl.shape[0], sl.shape[0]
+    offs = np.asarray(offsets if O else [], np.int64).reshape(-1, 2)
+    if cl.shape != (C, H, W) or sl.shape != (O, H, W) or offs.shape[0] != O:
+        raise ValueError("the maps, the offsets and the truth mask differ in size")
+
+    def expit(x):
+        e = np.exp(-np.abs(x))
+        return np.where(x >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+
+    tcls = _truth_class_of(t, truth_classes, num_truth)
+    keep = (tcls >= 0) & (tcls < C)
+    sums = np.zeros(2 + O, np.float64)
+    grad_class = np.zeros((C, H, W), np.float64)
+    grad_same = np.zeros((O, H, W), np.float64)
+    class_terms = []
+    for q in range(C):
+        x = cl[q].astype(np.float64)
+        y = tcls == q
+        class_terms.append(np.logaddexp(0.0, np.where(y, -x, x))[keep])
+        grad_class[q] = np.where(keep, (expit(x) - y) * float(scale_class), 0.0)
+    sums[0] = math.fsum(v for plane in class_terms for v in plane.tolist())      # (one plane's list at a time)
+    for k, (di, dj) in enumerate(offs.tolist()):
+        x = sl[k].astype(np.float64)
+        y = ~_different(t, di, dj)
+        sums[1 + k] = math.fsum(np.logaddexp(0.0, np.where(y, -x, x)).reshape(-1).tolist())
+        grad_same[k] = (expit(x) - y) * float(scale_same)
+    sums[1 + O] = float(keep.sum())
+    return sums, grad_class, grad_same

@@ -96,7 +96,7 @@ EXPORTS = ["mn_default_options", "mn_create", "mn_destroy", "mn_workspace_bytes"
            "mn_segment_device", "mn_segment_launch", "mn_segment_finish", "mn_segment_exact_batch", "mn_score_device", "mn_exact_phase_a_device", "mn_sweep_device", "mn_sweep_time_device", "mn_segment_host", "c_run_segmentation",
            "mn_prepare_device", "mn_upsample_mask_device", "mn_rle_points_device", "mn_rle_encode_host", "mn_rle_counts_host", "mn_rle_decode_device", "mn_sameness_targets_device", "mn_instance_scores_device",
            "mn_instance_table_device", "mn_filter_instances_device",
-           "mn_overlap_table_device", "mn_match_overlaps_device", "mn_map_scores_device", "mn_tile_class_maps_device",
+           "mn_overlap_table_device", "mn_match_overlaps_device", "mn_map_scores_device", "mn_mask_bce_device", "mn_tile_class_maps_device",
            "mn_eval_append_device", "mn_eval_keys_device", "mn_eval_accumulate_device",
            "mn_pack_wire_device", "mn_runs_wire_words", "mn_pack_runs_device", "mn_unpack_runs_device",
            "mn_unpack_runs_batch_device",
@@ -264,6 +264,13 @@ def load_library() -> ctypes.CDLL:
                                              _i32p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         lib.mn_map_scores_device.restype = ctypes.c_int
+    if hasattr(lib, "mn_mask_bce_device"):               # (absent from older variant builds: MN_LIB)
+        lib.mn_mask_bce_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p,
+                                           ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_void_p,
+                                           ctypes.c_int, ctypes.c_void_p]
+        lib.mn_mask_bce_device.restype = ctypes.c_int
     if hasattr(lib, "mn_tile_class_maps_device"):        # (absent from older variant builds: MN_LIB)
         lib.mn_tile_class_maps_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int,
@@ -1159,6 +1166,89 @@ class Merger:
         if rc != 0:
             raise MergeNetError(rc)
         return {"confusion": confusion, "sums": sums}
+
+    def mask_bce(self, class_logits, same_logits, offsets, truth, truth_classes, scale_class: float = 1.0,
+                 scale_same: float = 1.0, grad: bool = True, into=None, out=None):
+        """The training criterion of the reference from the label mask: ``torch.nn.BCEWithLogitsLoss`` of the class
+        planes and of the offset planes (egs/cityscape/local/train.py:183-195) as sums, and its gradient, in one pass
+        on the device -- each logit is read once, each gradient element written once, no target plane exists.
+        ``class_logits`` [C,H,W] and ``same_logits`` [O,H,W]: contiguous float32, float16 or bfloat16 LOGITS (views
+        of one prediction tensor are fine); either may be None or have no planes (offset-only or class-only
+        training), not both.  ``truth``, ``truth_classes``: as for :meth:`map_scores`; a pixel whose truth class is
+        outside 0..C-1 is an ignore class: no class term, class gradient 0, offset planes as usual.  Returns
+        ``{"sums": float64 [2+O], "grad_class": [C,H,W] or None, "grad_same": [O,H,W] or None}`` on the maps' device:
+        ``sums[0]`` the sum of the class terms, ``sums[1+k]`` the sum of the terms of offset k, ``sums[1+O]`` the
+        number of kept pixels (``labels.mask_bce`` is the numpy statement and gives the definitions).  The gradients
+        are ``(sigmoid(x) - y) * scale_class`` / ``* scale_same`` in the maps' dtype; ``grad=False``: the sums alone
+        (the validation loss), bit-equal to those of a call with gradients.  ``out=(grad_class, grad_same)``: the
+        caller's buffers of the maps' shapes and dtype, which may be views (and None for a part that has no planes).
+        ``into``: a previous result (or its ``sums`` tensor), to which this image's sums are added with one IEEE
+        addition each.  A float16 gradient scaled by 1 / (number of elements) underflows: pass larger scales (loss
+        scaling) or use bfloat16.  The sums of a call are bit-identical from run to run and do not depend on where the
+        tensors lie in memory.  Any image size; nothing is synchronised or copied.  The calls of one Merger share a
+        buffer of partial sums with :meth:`map_scores`: keep them on ONE stream."""
+        torch = self.torch
+        fn = self._entry("mn_mask_bce_device")
+        maps = [None if t is None or t.shape[0] == 0 else t for t in (class_logits, same_logits)]
+        first = next((t for t in maps if t is not None), None)
+        if first is None:
+            raise MergeNetError(MN_ERR_ARGUMENT)                 # (what the entry point answers to C == 0 and O == 0)
+        for t in maps:
+            if t is None:
+                continue
+            if not (t.is_cuda and t.is_contiguous() and t.dim() == 3):
+                raise ValueError("expected contiguous %s [K,H,W] tensors on the GPU" % self.DTYPE_NAMES)
+            if t.dtype != first.dtype:
+                raise ValueError("class and offset logits must share one dtype (%s)" % self.DTYPE_NAMES)
+            if t.device.index != self.device:
+                raise ValueError("tensor lives on another device than the Merger")
+            if t.shape[1:] != first.shape[1:]:
+                raise ValueError("class and offset logits differ in height or width")
+        code = self._dtype(first)
+        dev = first.device
+        H, W = int(first.shape[1]), int(first.shape[2])
+        C = 0 if maps[0] is None else int(maps[0].shape[0])
+        O = 0 if maps[1] is None else int(maps[1].shape[0])
+        off = np.ascontiguousarray(np.asarray(offsets if O else [], dtype=np.int32).reshape(-1, 2))
+        if off.shape[0] != O:
+            raise ValueError("%d offsets for %d offset planes" % (off.shape[0], O))
+        if self._check_mask(truth) != (H, W) or truth.device != dev:
+            raise ValueError("truth: a mask of the maps' height and width on the maps' GPU")
+        G = 0
+        if truth_classes is not None:
+            if not (truth_classes.is_cuda and truth_classes.dtype == torch.int32 and truth_classes.is_contiguous()
+                    and truth_classes.dim() == 1 and truth_classes.device == dev):
+                raise ValueError("truth_classes: a contiguous int32 [G] tensor on the maps' GPU, or None")
+            G = int(truth_classes.numel())
+        if into is None:
+            sums = torch.empty((2 + O,), dtype=torch.float64, device=dev)
+        else:
+            sums = into["sums"] if isinstance(into, dict) else into
+            if not (sums.is_cuda and sums.dtype == torch.float64 and sums.is_contiguous()
+                    and tuple(sums.shape) == (2 + O,) and sums.device == dev):
+                raise ValueError("into: a previous result of mask_bce for %d offsets on the maps' GPU" % O)
+        grads = [None, None]
+        if out is not None:
+            if not grad or len(out) != 2:
+                raise ValueError("out: (grad_class, grad_same), with grad=True")
+            for i, (g, t) in enumerate(zip(out, maps)):
+                if t is None:
+                    continue
+                if g is None or not (g.is_cuda and g.is_contiguous() and g.dtype == t.dtype and g.shape == t.shape
+                                     and g.device == dev):
+                    raise ValueError("out: contiguous buffers of the maps' shapes and dtype on the maps' GPU")
+                grads[i] = g
+        elif grad:
+            grads = [None if t is None else torch.empty_like(t) for t in maps]
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = fn(self.handle, maps[0].data_ptr() if C else None, maps[1].data_ptr() if O else None, code, W, H, C, O,
+                off.ctypes.data_as(_i32p) if O else None, truth.data_ptr(), G,
+                truth_classes.data_ptr() if G else None, grads[0].data_ptr() if grads[0] is not None else None,
+                grads[1].data_ptr() if grads[1] is not None else None, float(scale_class), float(scale_same),
+                sums.data_ptr(), 1 if into is not None else 0, ctypes.c_void_p(stream))
+        if rc != 0:
+            raise MergeNetError(rc)
+        return {"sums": sums, "grad_class": grads[0], "grad_same": grads[1]}
 
     def tile_class_maps(self, tiles, flip_tiles, row_starts, col_starts, height: int, width: int, num_classes: int,
                         out_dtype=None, clip: bool = False):
