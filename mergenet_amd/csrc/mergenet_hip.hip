@@ -43,6 +43,8 @@
 #define MN_MAX_SUBROUNDS 64
 
 static thread_local int g_last_status = MN_OK;
+// How an entry point leaves: the status is kept for mn_last_status() and returned.
+static int done(int status) { return g_last_status = status; }
 
 #define MN_HIP(expr)                                                                      \
   do {                                                                                    \
@@ -50,8 +52,7 @@ static thread_local int g_last_status = MN_OK;
     if (_e != hipSuccess) {                                                               \
       fprintf(stderr, "mergenet_hip: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(_e), \
               __FILE__, __LINE__);                                                        \
-      g_last_status = MN_ERR_NO_DEVICE;                                                   \
-      return MN_ERR_NO_DEVICE;                                                            \
+      return done(MN_ERR_NO_DEVICE);                                                      \
     }                                                                                     \
   } while (0)
 
@@ -664,7 +665,7 @@ static int begin_call(mn_context* c, const ImageCall& call, bool entry_ok, mn_st
   int rc = check_args(c, call);
   if (rc == MN_OK && (!call.d_class || !call.d_adj || !dtype_ok(call.dtype, true) || !entry_ok)) rc = MN_ERR_ARGUMENT;
   if (stats) { memset(stats, 0, sizeof(*stats)); stats->status = rc; stats->total_logprob = NAN; }
-  if (rc != MN_OK) { g_last_status = rc; return rc; }
+  if (rc != MN_OK) return done(rc);
   MN_HIP(hipSetDevice(c->device));
   fill_params(P, call);
   return MN_OK;
@@ -684,6 +685,21 @@ static inline unsigned grid_for(size_t n, unsigned block) { return (unsigned)((n
 static inline unsigned quad_grid(int N, unsigned block) { return grid_for((size_t)(N >> 2) > 0 ? (size_t)(N >> 2) : 1, block); }
 static inline unsigned all_offsets(int O) { return O >= 32 ? 0xFFFFFFFFu : ((1u << O) - 1u); }
 template <int V> using Int = std::integral_constant<int, V>;
+// Run-time values as compile-time ones, for generic lambdas: f(Int<DT>()) for the element type dt (what dtype_ok took,
+// without the logits bit), and f(Int<V>()) for v pixels per lane -- 8 only for the 16-bit types, then 4, then 1.
+template <typename F>
+static void by_dtype(int dt, F f) {
+  if (dt == MN_DTYPE_F32) f(Int<MN_DTYPE_F32>());
+  else if (dt == MN_DTYPE_F16) f(Int<MN_DTYPE_F16>());
+  else f(Int<MN_DTYPE_BF16>());
+}
+template <int DT, typename F>
+static void by_pixels(Int<DT>, int v, F f) {
+  if constexpr (DT != MN_DTYPE_F32) {
+    if (v == 8) return f(Int<8>());
+  }
+  v == 4 ? f(Int<4>()) : f(Int<1>());
+}
 
 struct FillList {
   FillJobs j;
@@ -856,14 +872,8 @@ static void launch_sweep(mn_context* c, const ImgParams& P, hipStream_t st, cons
     else if (F.cls) launch(lg, dt, px, no, yes, no);
     else launch(lg, dt, px, no, no, no);
   };
-  auto by_16 = [&](auto lg, auto px) {
-    P.dtype == MN_DTYPE_F16 ? by_form(lg, Int<MN_DTYPE_F16>(), px) : by_form(lg, Int<MN_DTYPE_BF16>(), px);
-  };
   auto by_px = [&](auto lg) {
-    if (P.dtype == MN_DTYPE_F32) F.px == 4 ? by_form(lg, Int<MN_DTYPE_F32>(), Int<4>()) : by_form(lg, Int<MN_DTYPE_F32>(), Int<1>());
-    else if (F.px == 8) by_16(lg, Int<8>());
-    else if (F.px == 4) by_16(lg, Int<4>());
-    else by_16(lg, Int<1>());
+    by_dtype(P.dtype, [&](auto dt) { by_pixels(dt, F.px, [&](auto px) { by_form(lg, dt, px); }); });
   };
   P.logits ? by_px(yes) : by_px(no);
 }
@@ -1639,8 +1649,7 @@ static int segment_read_back(mn_context* c, const mn_options* opts, const Queued
       }
     }
   }
-  g_last_status = rc;
-  return rc;
+  return done(rc);
 }
 
 struct Plan {              // everything an attempt decides before its first launch
@@ -2094,7 +2103,7 @@ extern "C" int mn_segment_launch_t(mn_context* c, const void* d_class_pred, int 
                                    int num_classes, const int* offset_list, int* d_mask,
                                    int* d_object_class, int* d_partition, const mn_options* opts,
                                    void* stream) {
-  if (!c || c->pend.active || !dtype_ok(dtype, true)) { g_last_status = MN_ERR_ARGUMENT; return MN_ERR_ARGUMENT; }
+  if (!c || c->pend.active || !dtype_ok(dtype, true)) return done(MN_ERR_ARGUMENT);
   HostLaunchTimer host_timer;
   mn_context::Pending& q = c->pend;
   q.call = ImageCall{d_class_pred, d_adj_pred, dtype, class_dim, offset_dim, W, H, num_classes, d_mask, d_object_class, d_partition};
@@ -2139,7 +2148,7 @@ extern "C" int mn_segment_launch(mn_context* c, const float* d_class_pred, int c
 // Second half: wait for the image queued by mn_segment_launch, read the verdict (a speculative
 // attempt that does not hold is redone here on the ordinary path) and fill `stats`.
 extern "C" int mn_segment_finish(mn_context* c, mn_stats* stats) {
-  if (!c || !c->pend.active) { g_last_status = MN_ERR_ARGUMENT; return MN_ERR_ARGUMENT; }
+  if (!c || !c->pend.active) return done(MN_ERR_ARGUMENT);
   const double t_in = host_now_us();
   double t_synced = t_in;
   mn_context::Pending& q = c->pend;
@@ -2228,17 +2237,14 @@ extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void
   shared.opts.mode = MN_MODE_EXACT;
   const mn_options& o = shared.opts;
   if (!ctxs || count <= 0 || count > 4096 || !d_class_pred || !d_adj_pred || !d_mask || !d_object_class ||
-      !dtype_ok(dtype, true)) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
+      !dtype_ok(dtype, true))
+    return done(MN_ERR_ARGUMENT);
   for (int i = 0; i < count; i++) {
-    if (!ctxs[i] || ctxs[i]->pend.active || ctxs[i]->device != ctxs[0]->device) { g_last_status = MN_ERR_ARGUMENT; return MN_ERR_ARGUMENT; }
-    for (int j = 0; j < i; j++) if (ctxs[j] == ctxs[i]) { g_last_status = MN_ERR_ARGUMENT; return MN_ERR_ARGUMENT; }
+    if (!ctxs[i] || ctxs[i]->pend.active || ctxs[i]->device != ctxs[0]->device) return done(MN_ERR_ARGUMENT);
+    for (int j = 0; j < i; j++) if (ctxs[j] == ctxs[i]) return done(MN_ERR_ARGUMENT);
     const int rc = check_args(ctxs[i], shared);
     if (rc != MN_OK || !d_class_pred[i] || !d_adj_pred[i] || !d_mask[i] || !d_object_class[i]) {
-      g_last_status = rc != MN_OK ? rc : MN_ERR_ARGUMENT;
-      return g_last_status;
+      return done(rc != MN_OK ? rc : MN_ERR_ARGUMENT);
     }
   }
   MN_HIP(hipSetDevice(ctxs[0]->device));
@@ -2249,7 +2255,7 @@ extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void
   HostBuf<ImageCall> calls((size_t)count); HostBuf<ImgParams> Ps((size_t)count), rc_P((size_t)count);
   HostBuf<mn_context*> rc_ctx((size_t)count); HostBuf<unsigned char> redo((size_t)count); HostBuf<int> rc_idx((size_t)count);
   if (!calls.ok() || !Ps.ok() || !rc_P.ok() || !rc_ctx.ok() || !redo.ok() || !rc_idx.ok() || !own_stats.ok())
-    return g_last_status = MN_ERR_INTERNAL;
+    return done(MN_ERR_INTERNAL);
   int rc = MN_OK;
   for (int i = 0; i < count; i++) {
     calls[i] = shared;
@@ -2270,7 +2276,7 @@ extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void
   const bool ref_only = ref_possible && o.tie_order == MN_TIES_REFERENCE;
   if (!ref_only) rc = exact_run(ctxs, count, Ps, st);
   for (int i = 0; i < count; i++) ctxs[i]->xw.max_blocks = 0;
-  if (rc != MN_OK) { g_last_status = rc; return rc; }
+  if (rc != MN_OK) return done(rc);
   // The tie policy, as a single call applies it: images whose tied choices conflict (or all, with
   // MN_TIES_REFERENCE) are redone in the reference's order among equals -- TOGETHER, one workgroup per image in one
   // launch of that loop.  Inside a batch the loop's cost is shared, so the size limit is higher than for a single
@@ -2285,7 +2291,7 @@ extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void
     rc_ctx[n_redo] = ctxs[i]; rc_P[n_redo] = Ps[i]; n_redo++;
   }
   if (n_redo > 0) rc = redo_in_reference_order(rc_ctx, n_redo, rc_P, st, !ref_only);
-  if (rc != MN_OK) { g_last_status = rc; return rc; }
+  if (rc != MN_OK) return done(rc);
   // hand-over and output stage of every image (labels, mask, class table, certificate, log-likelihood)
   for (int i = 0; i < count; i++) {
     ctxs[i]->xw.prerun = redo[i] ? 2 : 1;
@@ -2314,8 +2320,7 @@ extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void
       for (int j = 0; j < n2; j++) out[rc_idx[j]].status = MN_ERR_UNPROVEN;
       if (rc == MN_OK) rc = MN_ERR_UNPROVEN;
     } else if (r2 != MN_OK) {
-      g_last_status = r2;
-      return r2;
+      return done(r2);
     }
     for (int j = 0; j < n2 && r2 == MN_OK; j++) {
       const int i = rc_idx[j];
@@ -2325,8 +2330,7 @@ extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void
       if (r != MN_OK && rc == MN_OK) rc = r;
     }
   }
-  g_last_status = rc;
-  return rc;
+  return done(rc);
 }
 
 extern "C" int mn_segment_exact_batch(mn_context** ctxs, int count, const float* const* d_class_pred, int class_dim,
@@ -2363,8 +2367,7 @@ extern "C" int mn_score_device_t(mn_context* c, const void* d_class_pred, int cl
   if (ms_class_pass) *ms_class_pass = ms;
   (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
   if (ms_edge_pass) *ms_edge_pass = ms;
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 extern "C" int mn_score_device(mn_context* c, const float* d_class_pred, int class_dim,
@@ -2417,8 +2420,7 @@ extern "C" int mn_sweep_device_t(mn_context* c, const void* d_class_pred, int cl
   if (logsum_out) *logsum_out = t;
   if (info_out) { info_out[0] = F.px; info_out[1] = F.cls ? 1 : 0; info_out[2] = c->h_scalars[6]; }
   MN_HIP(hipGetLastError());
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 extern "C" int mn_sweep_device(mn_context* c, const float* d_class_pred, int class_dim,
@@ -2465,8 +2467,7 @@ extern "C" int mn_sweep_time_device_t(mn_context* c, const void* const* d_class_
   MN_HIP(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
   *us_per_launch = ms * 1e3f / (float)reps;
   MN_HIP(hipGetLastError());
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 extern "C" int mn_sweep_time_device(mn_context* c, const float* const* d_class_pred, const float* const* d_adj_pred,
@@ -2492,13 +2493,12 @@ extern "C" int mn_exact_phase_a_device_t(mn_context* c, const void* d_class_pred
   if (rc != MN_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // (deliberate carry-over: debug_flags is not set here -- nothing below reads it)
-  if ((rc = exact_setup(c, P, st)) != MN_OK) { g_last_status = rc; return rc; }
+  if ((rc = exact_setup(c, P, st)) != MN_OK) return done(rc);
   hipLaunchKernelGGL(mn_x_export_phase_a, dim3(grid_for((size_t)P.N * P.O, 256)), dim3(256), 0, st, P, c->xw.X,
                      d_oml_out, d_prio_out, d_cls_out);
   MN_HIP(hipGetLastError());
   MN_HIP(hipStreamSynchronize(st));
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 extern "C" int mn_exact_phase_a_device(mn_context* c, const float* d_class_pred, int class_dim,
@@ -2529,7 +2529,7 @@ extern "C" int mn_segment_host(mn_context* c, const float* class_pred, int class
   opts = &call.opts;
   int rc = check_args(c, call);
   if (rc == MN_OK && (!class_pred || !adj_pred || !mask || !object_class)) rc = MN_ERR_ARGUMENT;
-  if (rc != MN_OK) { g_last_status = rc; if (stats) { memset(stats, 0, sizeof(*stats)); stats->status = rc; } return rc; }
+  if (rc != MN_OK) { if (stats) { memset(stats, 0, sizeof(*stats)); stats->status = rc; } return done(rc); }
   MN_HIP(hipSetDevice(c->device));
   rc = ensure_staging(c);
   if (rc != MN_OK) return rc;
@@ -2594,18 +2594,15 @@ extern "C" int mn_prepare_device_t(mn_context* c, const void* d_in, int in_dtype
                                    int in_width, void* d_out, int out_dtype, int out_height, int out_width,
                                    int apply_sigmoid, int clip, void* stream) {
   if (!c || !d_in || !d_out || channels <= 0 || in_height <= 0 || in_width <= 0 || out_height <= 0 ||
-      out_width <= 0 || out_height > 65535 || channels > 65535 || !dtype_ok(in_dtype, false) || !dtype_ok(out_dtype, false)) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
+      out_width <= 0 || out_height > 65535 || channels > 65535 || !dtype_ok(in_dtype, false) || !dtype_ok(out_dtype, false))
+    return done(MN_ERR_ARGUMENT);
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(mn_prepare_maps, dim3(grid_for(out_width, 256), out_height, channels), dim3(256),
                      0, st, d_in, in_dtype, channels, in_height, in_width, d_out, out_dtype, out_height, out_width,
                      apply_sigmoid, clip);
   MN_HIP(hipGetLastError());
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 extern "C" int mn_prepare_device(mn_context* c, const float* d_in, int channels, int in_height,
@@ -2618,17 +2615,14 @@ extern "C" int mn_prepare_device(mn_context* c, const float* d_in, int channels,
 extern "C" int mn_upsample_mask_device(mn_context* c, const int* d_mask, int in_height, int in_width,
                                        int* d_out, int out_height, int out_width, void* stream) {
   if (!c || !d_mask || !d_out || in_height <= 0 || in_width <= 0 || out_height <= 0 ||
-      out_width <= 0 || out_height > 65535) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
+      out_width <= 0 || out_height > 65535)
+    return done(MN_ERR_ARGUMENT);
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(mn_upsample_mask, dim3(grid_for(out_width, 256), out_height), dim3(256), 0, st,
                      d_mask, in_height, in_width, d_out, out_height, out_width);
   MN_HIP(hipGetLastError());
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 
@@ -2639,10 +2633,8 @@ extern "C" int mn_upsample_mask_device(mn_context* c, const int* d_mask, int in_
 extern "C" int mn_rle_points_device(mn_context* c, const int* d_mask, int height, int width,
                                     int* d_points, int capacity, int* count, void* stream) {
   if (!c || !d_mask || !d_points || !count || height <= 0 || width <= 0 || capacity <= 0 ||
-      (size_t)height * width > c->N) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
+      (size_t)height * width > c->N)
+    return done(MN_ERR_ARGUMENT);
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int N = height * width;
@@ -2654,14 +2646,13 @@ extern "C" int mn_rle_points_device(mn_context* c, const int* d_mask, int height
   MN_HIP(hipStreamSynchronize(st));
   const int total = c->h_scalars[5];
   *count = total;
-  if (total > capacity) { g_last_status = MN_ERR_CAPACITY; return MN_ERR_CAPACITY; }
+  if (total > capacity) return done(MN_ERR_CAPACITY);
   hipLaunchKernelGGL(mn_rle_scatter, dim3(nblk), dim3(256), 0, st, d_mask, height, width,
                      (const int*)c->block_count, d_points, d_points + capacity,
                      d_points + 2 * (size_t)capacity);
   MN_HIP(hipGetLastError());
   MN_HIP(hipStreamSynchronize(st));
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 
@@ -2669,10 +2660,8 @@ extern "C" int mn_sameness_targets_device(mn_context* c, const int* d_mask, int 
                                           const int* offset_list, int offset_dim, float* d_out,
                                           void* stream) {
   if (!c || !d_mask || !offset_list || !d_out || height <= 0 || width <= 0 || offset_dim <= 0 ||
-      offset_dim > MN_MAX_OFFSETS) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
+      offset_dim > MN_MAX_OFFSETS)
+    return done(MN_ERR_ARGUMENT);
   MN_HIP(hipSetDevice(c->device));
   ImgParams P;
   memset(&P, 0, sizeof(P));
@@ -2680,22 +2669,20 @@ extern "C" int mn_sameness_targets_device(mn_context* c, const int* d_mask, int 
   hipLaunchKernelGGL(mn_sameness_targets, dim3(grid_for((size_t)height * width, 256), offset_dim),
                      dim3(256), 0, static_cast<hipStream_t>(stream), d_mask, height, width, P, d_out);
   MN_HIP(hipGetLastError());
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 // Confidence of the instances of the LAST mn_segment_device call on this context:
 // d_scores[k-1] = lp[cls] - lp[0] of label k (float32, at least num_instances entries).  The class
 // planes passed to that call must still be alive (objects that never merged read them).
 extern "C" int mn_instance_scores_device(mn_context* c, float* d_scores, void* stream) {
-  if (!c || !d_scores || !c->last_valid) { g_last_status = MN_ERR_ARGUMENT; return MN_ERR_ARGUMENT; }
+  if (!c || !d_scores || !c->last_valid) return done(MN_ERR_ARGUMENT);
   MN_HIP(hipSetDevice(c->device));
   hipLaunchKernelGGL(mn_instance_scores, dim3(grid_for(c->last_params.N, 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), c->last_params, obj_state(c),
                      (const int*)c->label, d_scores);
   MN_HIP(hipGetLastError());
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 // ---- instance table, small-instance filter (mn_kernels_instances.h) -------------------------------
@@ -2704,12 +2691,9 @@ extern "C" int mn_instance_scores_device(mn_context* c, float* d_scores, void* s
 extern "C" int mn_instance_table_device(mn_context* c, const int* d_mask, int height, int width,
                                         int num_instances, int* d_table, void* stream) {
   if (!c || !d_mask || height <= 0 || width <= 0 || num_instances < 0 || (num_instances > 0 && !d_table) ||
-      (size_t)height * (size_t)width > (size_t)INT_MAX) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
-  g_last_status = MN_OK;
-  if (num_instances == 0) return MN_OK;
+      (size_t)height * (size_t)width > (size_t)INT_MAX)
+    return done(MN_ERR_ARGUMENT);
+  if (num_instances == 0) return done(MN_OK);
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(mn_instance_table_init, dim3(grid_for(num_instances, 256)), dim3(256), 0, st, num_instances,
@@ -2722,7 +2706,7 @@ extern "C" int mn_instance_table_device(mn_context* c, const int* d_mask, int he
   else
     hipLaunchKernelGGL(mn_instance_table_runs<1>, g, b, 0, st, d_mask, height, width, num_instances, R, d_table);
   MN_HIP(hipGetLastError());
-  return MN_OK;
+  return done(MN_OK);
 }
 
 extern "C" int mn_filter_instances_device(mn_context* c, const int* d_mask, int height, int width,
@@ -2736,10 +2720,8 @@ extern "C" int mn_filter_instances_device(mn_context* c, const int* d_mask, int 
                              (d_scores && !d_scores_out))) ||
       // the compaction is out of place (and d_remap is read by the relabel while the mask is written)
       (d_table_out && d_table_out == d_table) || (d_object_class_out && d_object_class_out == d_object_class) ||
-      (d_scores_out && d_scores_out == d_scores) || d_remap == d_mask_out || d_remap == d_mask) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
+      (d_scores_out && d_scores_out == d_scores) || d_remap == d_mask_out || d_remap == d_mask)
+    return done(MN_ERR_ARGUMENT);
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(mn_instance_keep, dim3(1), dim3(1024), 0, st, num_instances, d_table, d_object_class, d_scores,
@@ -2752,8 +2734,7 @@ extern "C" int mn_filter_instances_device(mn_context* c, const int* d_mask, int 
     hipLaunchKernelGGL(mn_relabel_mask, dim3(grid_for(N, 256)), dim3(256), 0, st, d_mask, N, num_instances,
                        (const int*)d_remap, d_mask_out);
   MN_HIP(hipGetLastError());
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 // ---- overlap table, IoU and matching against the ground truth (mn_kernels_match.h) ------------------
@@ -2762,10 +2743,8 @@ extern "C" int mn_overlap_table_device(mn_context* c, const int* d_pred, const i
                                        int num_pred, int num_truth, int* d_table, void* stream) {
   if (!c || !d_pred || !d_truth || !d_table || height <= 0 || width <= 0 || num_pred < 0 || num_truth < 0 ||
       (size_t)height * (size_t)width > (size_t)INT_MAX ||
-      ((long long)num_pred + 1) * ((long long)num_truth + 1) > (1LL << 28)) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
+      ((long long)num_pred + 1) * ((long long)num_truth + 1) > (1LL << 28))
+    return done(MN_ERR_ARGUMENT);
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t entries = (size_t)(num_pred + 1) * (size_t)(num_truth + 1);
@@ -2780,8 +2759,7 @@ extern "C" int mn_overlap_table_device(mn_context* c, const int* d_pred, const i
     hipLaunchKernelGGL(mn_overlap_table_runs<1>, g, b, 0, st, d_pred, d_truth, height, width, num_pred, num_truth, R,
                        d_table);
   MN_HIP(hipGetLastError());
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 static MnThresholds match_thresholds(const double* thresholds, int T) {
@@ -2818,14 +2796,9 @@ extern "C" int mn_match_overlaps_device(mn_context* c, const int* d_table, int n
                                          unsigned char* d_pred_ignore, unsigned char* d_truth_ignore, void* stream) {
   const int K = num_pred, G = num_truth, T = num_thresholds;
   if (!c || !d_table || !thresholds || T < 1 || T > 16 || K < 0 || G < 0 ||
-      (K > 0 && (!d_pred_class || !d_pred_match || !d_pred_ignore)) || (G > 0 && (!d_truth_class || !d_truth_match))) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
-  if (K > MN_MATCH_MAX_INSTANCES || G > MN_MATCH_MAX_INSTANCES) {
-    g_last_status = MN_ERR_CAPACITY;
-    return MN_ERR_CAPACITY;
-  }
+      (K > 0 && (!d_pred_class || !d_pred_match || !d_pred_ignore)) || (G > 0 && (!d_truth_class || !d_truth_match)))
+    return done(MN_ERR_ARGUMENT);
+  if (K > MN_MATCH_MAX_INSTANCES || G > MN_MATCH_MAX_INSTANCES) return done(MN_ERR_CAPACITY);
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (K == 0 || G == 0) {                                        // nothing to match: every output is zero
@@ -2837,16 +2810,14 @@ extern "C" int mn_match_overlaps_device(mn_context* c, const int* d_table, int n
       MN_HIP(hipMemsetAsync(d_truth_match, 0, (size_t)T * G * sizeof(int), st));
       if (d_truth_ignore) MN_HIP(hipMemsetAsync(d_truth_ignore, 0, (size_t)G, st));
     }
-    g_last_status = MN_OK;
-    return MN_OK;
+    return done(MN_OK);
   }
   if (!c->match_work) MN_HIP(dev_alloc(c, &c->match_work, 1));
   match_launch(c, st, d_table, K, G, d_pred_class, d_pred_score, d_truth_class, d_truth_crowd,
                match_thresholds(thresholds, T), T, area_lo, area_hi, d_iou, d_pred_match, d_truth_match, d_pred_ignore,
                d_truth_ignore, /* ordered */ false);
   MN_HIP(hipGetLastError());
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 // ---- the dataset-level evaluation: a log of records, accumulate (mn_kernels_eval.h) ----------------------
@@ -2859,18 +2830,10 @@ extern "C" int mn_eval_append_device(mn_context* c, const int* d_table, int num_
   const int K = num_pred, G = num_truth, T = num_thresholds, A = num_areas;
   if (!c || !d_table || !thresholds || !area_ranges || !d_npig || T < 1 || T > 16 || A < 1 || A > MN_EVAL_MAX_AREAS ||
       K < 0 || G < 0 || max_det < 1 || num_classes < 1 || image < 0 || (K > 0 && (!d_pred_class || !d_records)) ||
-      (G > 0 && !d_truth_class) || (reinterpret_cast<uintptr_t>(d_records) & 15) != 0) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
-  if (K > MN_MATCH_MAX_INSTANCES || G > MN_MATCH_MAX_INSTANCES) {
-    g_last_status = MN_ERR_CAPACITY;
-    return MN_ERR_CAPACITY;
-  }
-  if (K == 0 && G == 0) {                                        // an image without anything: no record, no count
-    g_last_status = MN_OK;
-    return MN_OK;
-  }
+      (G > 0 && !d_truth_class) || (reinterpret_cast<uintptr_t>(d_records) & 15) != 0)
+    return done(MN_ERR_ARGUMENT);
+  if (K > MN_MATCH_MAX_INSTANCES || G > MN_MATCH_MAX_INSTANCES) return done(MN_ERR_CAPACITY);
+  if (K == 0 && G == 0) return done(MN_OK);                      // an image without anything: no record, no count
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (!c->match_work) MN_HIP(dev_alloc(c, &c->match_work, 1));
@@ -2903,17 +2866,14 @@ extern "C" int mn_eval_append_device(mn_context* c, const int* d_table, int num_
                        G > 0 ? 1 : 0, d_pred_class, d_pred_score, (const MnMatchWork*)c->match_work,
                        (const MnEvalWork*)e, image, static_cast<uint4*>(d_records));
   MN_HIP(hipGetLastError());
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 extern "C" int mn_eval_keys_device(mn_context* c, const void* d_records, long long num_records, int num_classes,
                                     long long* d_keys, void* stream) {
   if (!c || num_records < 0 || num_records > (long long)INT_MAX || num_classes < 1 ||
-      (num_records > 0 && (!d_records || !d_keys)) || (reinterpret_cast<uintptr_t>(d_records) & 15) != 0) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
+      (num_records > 0 && (!d_records || !d_keys)) || (reinterpret_cast<uintptr_t>(d_records) & 15) != 0)
+    return done(MN_ERR_ARGUMENT);
   if (num_records > 0) {
     MN_HIP(hipSetDevice(c->device));
     hipLaunchKernelGGL(mn_eval_keys, dim3(grid_for((size_t)num_records, MN_EVAL_THREADS)), dim3(MN_EVAL_THREADS), 0,
@@ -2921,8 +2881,7 @@ extern "C" int mn_eval_keys_device(mn_context* c, const void* d_records, long lo
                        num_classes, d_keys);
     MN_HIP(hipGetLastError());
   }
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 extern "C" int mn_eval_accumulate_device(mn_context* c, const void* d_records, long long num_records,
@@ -2942,34 +2901,18 @@ extern "C" int mn_eval_accumulate_device(mn_context* c, const void* d_records, l
     md.m[m] = max_dets[m < M ? m : M - 1];
     ok = md.m[m] >= 1 && (m == 0 || m >= M || md.m[m] > md.m[m - 1]);
   }
-  if (!ok) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
+  if (!ok) return done(MN_ERR_ARGUMENT);
   MN_HIP(hipSetDevice(c->device));
   hipLaunchKernelGGL(mn_eval_scan, dim3((unsigned)(C * A * M), (unsigned)T), dim3(MN_EVAL_THREADS), 0,
                      static_cast<hipStream_t>(stream), static_cast<const uint4*>(d_records), (int)num_records,
                      d_sorted_keys, d_sorted_index, d_npig, C, T, R, A, M, md, d_rec_thresholds, d_precision, d_recall,
                      d_scores);
   MN_HIP(hipGetLastError());
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 // ---- the maps against the ground truth (mn_kernels_mapscore.h) ---------------------------------------
 // Enqueues only: no host synchronisation, no copy.  Nothing of the segmentation path runs here.
-template <int DT, bool LG>
-static void map_scores_launch(int v, dim3 g, hipStream_t st, const MnMapScoreArgs& A) {
-  const dim3 b(MN_MS_THREADS);
-  if (v == 8) {
-    if constexpr (DT != MN_DTYPE_F32) hipLaunchKernelGGL((mn_map_scores_pass<DT, LG, 8>), g, b, 0, st, A);
-  } else if (v == 4) {
-    hipLaunchKernelGGL((mn_map_scores_pass<DT, LG, 4>), g, b, 0, st, A);
-  } else {
-    hipLaunchKernelGGL((mn_map_scores_pass<DT, LG, 1>), g, b, 0, st, A);
-  }
-}
-
 extern "C" int mn_map_scores_device(mn_context* c, const void* d_class_pred, int class_dim, const void* d_adj_pred,
                                     int offset_dim, int dtype, int img_width, int img_height, int num_classes,
                                     const int* offset_list, const int* d_truth, int num_truth,
@@ -2979,10 +2922,8 @@ extern "C" int mn_map_scores_device(mn_context* c, const void* d_class_pred, int
   if (!c || !d_class_pred || !d_adj_pred || !offset_list || !d_truth || !d_confusion || !d_sums || H <= 0 || W <= 0 ||
       C < 1 || C > MN_MAX_CLASSES || class_dim < C || O < 1 || O > MN_MAX_OFFSETS || G < 0 ||
       (G > 0 && !d_truth_classes) || (size_t)H * (size_t)W > (size_t)INT_MAX || W > MN_MS_MAX_WIDTH ||
-      !dtype_ok(dtype, true)) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
+      !dtype_ok(dtype, true))
+    return done(MN_ERR_ARGUMENT);
   const int dt = dtype & 0xFF, logits = (dtype & MN_MAPS_LOGITS) ? 1 : 0;
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2995,48 +2936,28 @@ extern "C" int mn_map_scores_device(mn_context* c, const void* d_class_pred, int
   A.H = H; A.W = W; A.C = C; A.O = O; A.G = G;
   A.confusion = reinterpret_cast<unsigned long long*>(d_confusion);
   A.partials = c->ms_partials;
-  for (int k = 0; k < O; k++) {   // an offset of H rows or W columns or more leaves the image whatever its size: held
-    A.di[k] = std::max(-H, std::min(H, offset_list[2 * k]));       // to that, so that row + di and column + dj stay ints
-    A.dj[k] = std::max(-W, std::min(W, offset_list[2 * k + 1]));
-  }
-  // The grid is a function of (H, W, element type) alone: it is sized for the widest loads of the element type.
-  // Pixels per lane follow the width and BOTH maps' base addresses; fewer of them mean more chunks per wave.
+  truth_pass_offsets(offset_list, O, H, W, A.di, A.dj);
+  // The grid by (H, W, element type) alone; pixels per lane follow the width and BOTH maps' base addresses.
   const int elem = dt == MN_DTYPE_F32 ? 4 : 2;
-  const int widest = 16 / elem;
-  const long long nominal = (long long)H * ((W + 64 * widest - 1) / (64 * widest));
-  const long long want = (nominal + MN_MS_WAVES * MN_MS_MIN_CHUNKS - 1) / (MN_MS_WAVES * MN_MS_MIN_CHUNKS);
-  const int slots = (int)std::min<long long>(MN_MS_WORKGROUPS, want);
+  const int slots = truth_pass_slots(H, W, elem, MN_MS_WAVES);
   const int v = row_walk_v(W, elem, d_class_pred, d_adj_pred);
   A.walk = row_walk_fixed(H, W, v, slots, MN_MS_WAVES);
-  const dim3 g((unsigned)slots);
-  if (dt == MN_DTYPE_F32) {
-    if (logits) map_scores_launch<MN_DTYPE_F32, true>(v, g, st, A); else map_scores_launch<MN_DTYPE_F32, false>(v, g, st, A);
-  } else if (dt == MN_DTYPE_F16) {
-    if (logits) map_scores_launch<MN_DTYPE_F16, true>(v, g, st, A); else map_scores_launch<MN_DTYPE_F16, false>(v, g, st, A);
-  } else {
-    if (logits) map_scores_launch<MN_DTYPE_BF16, true>(v, g, st, A); else map_scores_launch<MN_DTYPE_BF16, false>(v, g, st, A);
-  }
+  const dim3 g((unsigned)slots), b(MN_MS_THREADS);
+  by_dtype(dt, [&](auto t) {
+    by_pixels(t, v, [&](auto px) {
+      constexpr int DT = decltype(t)::value, V = decltype(px)::value;
+      if (logits) hipLaunchKernelGGL((mn_map_scores_pass<DT, true, V>), g, b, 0, st, A);
+      else hipLaunchKernelGGL((mn_map_scores_pass<DT, false, V>), g, b, 0, st, A);
+    });
+  });
   hipLaunchKernelGGL(mn_map_scores_finish, dim3(3 * O), dim3(64), 0, st, (const double*)c->ms_partials, slots,
                      d_sums, accumulate);
   MN_HIP(hipGetLastError());
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 // ---- the training criterion from the label mask (mn_kernels_loss.h) ---------------------------------------
 // Enqueues only: no host synchronisation, no copy.  Nothing of the segmentation path runs here.
-template <int DT>
-static void mask_bce_launch(int p, dim3 g, hipStream_t st, const MnMaskBceArgs& A) {
-  const dim3 b(MN_BCE_THREADS);
-  if (p == 8) {
-    if constexpr (DT != MN_DTYPE_F32) hipLaunchKernelGGL((mn_mask_bce_pass<DT, 8>), g, b, 0, st, A);
-  } else if (p == 4) {
-    hipLaunchKernelGGL((mn_mask_bce_pass<DT, 4>), g, b, 0, st, A);
-  } else {
-    hipLaunchKernelGGL((mn_mask_bce_pass<DT, 1>), g, b, 0, st, A);
-  }
-}
-
 extern "C" int mn_mask_bce_device(mn_context* c, const void* d_class_logits, const void* d_same_logits, int dtype,
                                   int img_width, int img_height, int num_classes, int offset_dim,
                                   const int* offset_list, const int* d_truth, int num_truth,
@@ -3046,10 +2967,8 @@ extern "C" int mn_mask_bce_device(mn_context* c, const void* d_class_logits, con
   if (!c || !d_truth || !d_sums || H <= 0 || W <= 0 || C < 0 || C > MN_MAX_CLASSES || O < 0 || O > MN_MAX_OFFSETS ||
       C + O == 0 || (C > 0 && !d_class_logits) || (O > 0 && (!d_same_logits || !offset_list)) || G < 0 ||
       (G > 0 && !d_truth_classes) || (size_t)H * (size_t)W > (size_t)INT_MAX || W > MN_MS_MAX_WIDTH ||
-      !dtype_ok(dtype, false) || !std::isfinite(scale_class) || !std::isfinite(scale_same)) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
+      !dtype_ok(dtype, false) || !std::isfinite(scale_class) || !std::isfinite(scale_same))
+    return done(MN_ERR_ARGUMENT);
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (!c->ms_partials) MN_HIP(dev_alloc(c, &c->ms_partials, (size_t)MN_MS_VALUES * MN_MS_WORKGROUPS));
@@ -3062,30 +2981,25 @@ extern "C" int mn_mask_bce_device(mn_context* c, const void* d_class_logits, con
   A.H = H; A.W = W; A.C = C; A.O = O; A.G = G;
   A.scale_cls = scale_class; A.scale_same = scale_same;
   A.partials = c->ms_partials;
-  for (int k = 0; k < O; k++) {   // held to -H..H and -W..W, as in mn_map_scores_device: row + di and column + dj stay ints
-    A.di[k] = std::max(-H, std::min(H, offset_list[2 * k]));
-    A.dj[k] = std::max(-W, std::min(W, offset_list[2 * k + 1]));
-  }
-  // The grid by the rule of mn_map_scores_device: a function of (H, W, element type) alone.  So are the pixels a lane
-  // holds (row_walk_v without bases); the four bases only decide between wide accesses and single elements.
+  truth_pass_offsets(offset_list, O, H, W, A.di, A.dj);
+  // The grid by (H, W, element type) alone.  So are the pixels a lane holds (row_walk_v without bases); the four
+  // bases only decide between wide accesses and single elements.
   const int dt = dtype & 0xFF;
   const int elem = dt == MN_DTYPE_F32 ? 4 : 2;
-  const int widest = 16 / elem;
-  const long long nominal = (long long)H * ((W + 64 * widest - 1) / (64 * widest));
-  const long long want = (nominal + MN_BCE_WAVES * MN_MS_MIN_CHUNKS - 1) / (MN_BCE_WAVES * MN_MS_MIN_CHUNKS);
-  const int slots = (int)std::min<long long>(MN_MS_WORKGROUPS, want);
+  const int slots = truth_pass_slots(H, W, elem, MN_BCE_WAVES);
   const int p = row_walk_v(W, elem, nullptr);
   A.wide = std::min(row_walk_v(W, elem, A.cls, A.same), row_walk_v(W, elem, A.gcls, A.gsame)) == p ? 1 : 0;
   A.walk = row_walk_fixed(H, W, p, slots, MN_BCE_WAVES);
-  const dim3 g((unsigned)slots);
-  if (dt == MN_DTYPE_F32) mask_bce_launch<MN_DTYPE_F32>(p, g, st, A);
-  else if (dt == MN_DTYPE_F16) mask_bce_launch<MN_DTYPE_F16>(p, g, st, A);
-  else mask_bce_launch<MN_DTYPE_BF16>(p, g, st, A);
+  const dim3 g((unsigned)slots), b(MN_BCE_THREADS);
+  by_dtype(dt, [&](auto t) {
+    by_pixels(t, p, [&](auto px) {
+      hipLaunchKernelGGL((mn_mask_bce_pass<decltype(t)::value, decltype(px)::value>), g, b, 0, st, A);
+    });
+  });
   hipLaunchKernelGGL(mn_map_scores_finish, dim3(2 + O), dim3(64), 0, st, (const double*)c->ms_partials, slots,
                      d_sums, accumulate);
   MN_HIP(hipGetLastError());
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 // ---- class maps from a tiled semantic network (mn_kernels_tiles.h) -------------------------------------
@@ -3108,15 +3022,6 @@ static bool tile_axis_ok(const int* starts, int n, int side, int size) {
   return reach >= size;
 }
 
-template <int DT>
-static void tile_class_maps_launch(int cn, dim3 g, hipStream_t st, const MnTileArgs& A) {
-  const dim3 b(MN_TILES_THREADS);
-  if (cn <= 8) hipLaunchKernelGGL((mn_tile_class_maps<DT, 8>), g, b, 0, st, A);
-  else if (cn <= 20) hipLaunchKernelGGL((mn_tile_class_maps<DT, 20>), g, b, 0, st, A);
-  else if (cn <= 32) hipLaunchKernelGGL((mn_tile_class_maps<DT, 32>), g, b, 0, st, A);
-  else hipLaunchKernelGGL((mn_tile_class_maps<DT, MN_TILES_MAX_CLASSES>), g, b, 0, st, A);
-}
-
 extern "C" int mn_tile_class_maps_device(mn_context* c, const void* d_tiles, const void* d_flip_tiles, int dtype,
                                          int net_classes, int tile_height, int tile_width,
                                          const int* row_starts, int num_rows, const int* col_starts, int num_cols,
@@ -3128,10 +3033,8 @@ extern "C" int mn_tile_class_maps_device(mn_context* c, const void* d_tiles, con
             dtype_ok(out_dtype, false);
   ok = ok && tile_axis_ok(row_starts, num_rows, tile_height, H) && tile_axis_ok(col_starts, num_cols, tile_width, W);
   const long long blocks_per_row = ok ? ((long long)W + MN_TILES_THREADS - 1) / MN_TILES_THREADS : 0;
-  if (!ok || blocks_per_row * (long long)H > (long long)INT_MAX) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
+  if (!ok || blocks_per_row * (long long)H > (long long)INT_MAX)
+    return done(MN_ERR_ARGUMENT);
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   MnTileArgs A;
@@ -3142,13 +3045,16 @@ extern "C" int mn_tile_class_maps_device(mn_context* c, const void* d_tiles, con
   A.out_dtype = out_dtype; A.clip = clip ? 1 : 0;
   for (int i = 0; i < num_rows; i++) A.rs[i] = row_starts[i];
   for (int j = 0; j < num_cols; j++) A.cs[j] = col_starts[j];
-  const dim3 g((unsigned)(blocks_per_row * H));
-  if (dtype == MN_DTYPE_F32) tile_class_maps_launch<MN_DTYPE_F32>(Cn, g, st, A);
-  else if (dtype == MN_DTYPE_F16) tile_class_maps_launch<MN_DTYPE_F16>(Cn, g, st, A);
-  else tile_class_maps_launch<MN_DTYPE_BF16>(Cn, g, st, A);
+  const dim3 g((unsigned)(blocks_per_row * H)), b(MN_TILES_THREADS);
+  by_dtype(dtype, [&](auto t) {
+    constexpr int DT = decltype(t)::value;
+    if (Cn <= 8) hipLaunchKernelGGL((mn_tile_class_maps<DT, 8>), g, b, 0, st, A);
+    else if (Cn <= 20) hipLaunchKernelGGL((mn_tile_class_maps<DT, 20>), g, b, 0, st, A);
+    else if (Cn <= 32) hipLaunchKernelGGL((mn_tile_class_maps<DT, 32>), g, b, 0, st, A);
+    else hipLaunchKernelGGL((mn_tile_class_maps<DT, MN_TILES_MAX_CLASSES>), g, b, 0, st, A);
+  });
   MN_HIP(hipGetLastError());
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 // Wire format of the mask exchange (mergenet_amd/distributed.py): d_wire is int16
@@ -3158,18 +3064,15 @@ extern "C" int mn_pack_wire_device(const int* d_mask, const int* d_object_class,
                                    double total_logprob, int n_pixels, int max_instances,
                                    short* d_wire, void* stream) {
   if (!d_mask || !d_object_class || !d_wire || n_pixels <= 0 || max_instances <= 0 ||
-      max_instances > 32767 || num_instances < 0 || num_instances > max_instances) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
+      max_instances > 32767 || num_instances < 0 || num_instances > max_instances)
+    return done(MN_ERR_ARGUMENT);
   const size_t threads = (size_t)(n_pixels >> 2) > (size_t)max_instances + 1 ? (size_t)(n_pixels >> 2)
                                                                               : (size_t)max_instances + 1;
   hipLaunchKernelGGL(mn_pack_wire, dim3(grid_for(threads < 4 ? 4 : threads, 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), n_pixels, max_instances, num_instances,
                      total_logprob, d_mask, d_object_class, d_wire);
   MN_HIP(hipGetLastError());
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 
@@ -3183,10 +3086,8 @@ extern "C" int mn_pack_runs_device(mn_context* c, const int* d_mask, const int* 
                                    int max_instances, int* d_wire, void* stream) {
   if (!c || !d_mask || !d_object_class || !d_wire || n_pixels <= 0 || (size_t)n_pixels > c->N ||
       capacity <= 0 || max_instances <= 0 || num_instances < 0 || num_instances > max_instances ||
-      num_instances > 32767) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
+      num_instances > 32767)
+    return done(MN_ERR_ARGUMENT);
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int nblk = (int)grid_for(n_pixels, MN_RLE_ITEMS);
@@ -3197,25 +3098,21 @@ extern "C" int mn_pack_runs_device(mn_context* c, const int* d_mask, const int* 
                      (const int*)c->wire_counts, (const int*)total, capacity, max_instances, num_instances,
                      total_logprob, d_object_class, d_wire);
   MN_HIP(hipGetLastError());
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 extern "C" int mn_unpack_runs_batch_device(const int* d_wires, long long wire_stride_words, int count,
                                            int n_pixels, int capacity, int max_instances, int* d_masks,
                                            int* d_tables, void* stream) {
   if (!d_wires || !d_masks || n_pixels <= 0 || capacity <= 0 || max_instances <= 0 || count <= 0 || count > 65535 ||
-      wire_stride_words < (long long)mn_runs_wire_words(capacity, max_instances)) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
+      wire_stride_words < (long long)mn_runs_wire_words(capacity, max_instances))
+    return done(MN_ERR_ARGUMENT);
   const size_t threads = (size_t)n_pixels > (size_t)max_instances ? (size_t)n_pixels : (size_t)max_instances;
   hipLaunchKernelGGL(mn_runs_unpack, dim3(grid_for(threads, 256), (unsigned)count), dim3(256), 0,
                      static_cast<hipStream_t>(stream), d_wires, n_pixels, capacity, max_instances, d_masks, d_tables,
                      wire_stride_words);
   MN_HIP(hipGetLastError());
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }
 
 extern "C" int mn_unpack_runs_device(const int* d_wire, int n_pixels, int capacity, int max_instances,
@@ -3348,10 +3245,8 @@ extern "C" int mn_rle_decode_device(mn_context* c, const unsigned* d_counts, con
   const int A = num_annotations;
   if (!c || !d_mask || height <= 0 || width <= 0 || (size_t)height * (size_t)width > (size_t)INT_MAX ||
       A < 0 || A > MN_RLE_MAX_ANNOTATIONS || num_counts < 0 ||
-      (A > 0 && (!d_starts || !d_scratch_records)) || (num_counts > 0 && (!d_counts || !d_scratch_ends))) {
-    g_last_status = MN_ERR_ARGUMENT;
-    return MN_ERR_ARGUMENT;
-  }
+      (A > 0 && (!d_starts || !d_scratch_records)) || (num_counts > 0 && (!d_counts || !d_scratch_ends)))
+    return done(MN_ERR_ARGUMENT);
   static_assert(sizeof(MnRleRecord) == MN_RLE_RECORD_INTS * sizeof(int), "the record size the header states");
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -3363,6 +3258,5 @@ extern "C" int mn_rle_decode_device(mn_context* c, const unsigned* d_counts, con
                      dim3(MN_RLE_PAINT_THREADS), 0, st, (const unsigned*)d_scratch_ends, (const MnRleRecord*)rec,
                      d_values, A, height, width, d_mask);
   MN_HIP(hipGetLastError());
-  g_last_status = MN_OK;
-  return MN_OK;
+  return done(MN_OK);
 }

@@ -29,16 +29,13 @@
 #pragma once
 
 #include "mn_device.h"
-#include "mn_kernels_cc.h"        // the streaming typed loaders and stores (mn_ld_stream*_t, mn_st_stream*_t)
-#include "mn_kernels_mapscore.h"  // mn_ms_load, mn_map_scores_finish, the grid rule's constants
 #include "mn_row_walk.h"
+#include "mn_truth_pass.h"        // what this pass shares with mn_map_scores_pass: the grid, the truth reads, the sums
 
 #define MN_BCE_THREADS 256
 #define MN_BCE_WAVES (MN_BCE_THREADS / 64)
 #define MN_BCE_OG 5               /* offset planes whose loads are in flight together (and whose sums a lane holds) */
 #define MN_BCE_CG 4               /* class planes whose loads are in flight together */
-#define MN_BCE_VALUES (2 + MN_MAX_OFFSETS)
-static_assert(MN_BCE_VALUES <= MN_MS_VALUES, "the pass shares the partials buffer of mn_map_scores_device");
 
 struct MnMaskBceArgs {
   const void* cls;                // [C][N] logits (null when C == 0)
@@ -64,37 +61,15 @@ __device__ __forceinline__ float mn_bce_grad(float x, bool y, float scale) {
   return (mn_sigmoid(x) - (y ? 1.0f : 0.0f)) * scale;
 }
 
-// The lane's P consecutive elements of one plane, from element i: one wide access (mn_ms_load / mn_st_stream_t:
-// 16 bytes for P = 8 and for P = 4 of float32, 8 bytes for P = 4 of 16-bit elements) or -- a base off the
-// boundary, uniform over the launch -- P single elements.  P = 1 is the single element either way.
-template <int DT, int P>
-__device__ __forceinline__ void mn_bce_load(const void* base, size_t i, bool wide, float* v) {
-  if (P == 1 || wide) {
-    mn_ms_load<DT, false, P>(base, i, v);
-  } else {
-#pragma unroll
-    for (int j = 0; j < P; j++) v[j] = mn_ld_stream1_t<DT, false>(base, i + j);
-  }
-}
-template <int DT, int P>
-__device__ __forceinline__ void mn_bce_store(void* base, size_t i, bool wide, const float* g) {
-  if (P == 1 || wide) {
-    mn_st_stream_t<DT, P>(base, i, g);
-  } else {
-#pragma unroll
-    for (int j = 0; j < P; j++) mn_st_stream_t<DT, 1>(base, i + j, g + j);
-  }
-}
-
 // The walk of mn_row_walk.h with P pixels per lane, P = 8, 4 or 1 by the element size and the WIDTH alone
 // (row_walk_v without bases), so that which pixels a lane holds, and with that the grouping of every float64 sum,
 // does not depend on where the caller's buffers lie: bases that do not admit the wide access (A.wide == 0) change
-// the loads and stores to single elements, not the walk.  The sums of an image are therefore the same bits whatever
-// the alignment of the maps and gradients, and whether or not a gradient is written.
+// the loads and stores to single elements (mn_plane_load / mn_plane_store), not the walk.  The sums of an image are
+// therefore the same bits whatever the alignment of the maps and gradients, and whether or not a gradient is written.
 //   1. the class planes, MN_BCE_CG in flight: per pixel its truth class once, then per plane the term (added to the
 //      lane's float64 sum for a kept pixel) and the gradient, stored as soon as the group's values are in;
 //   2. the offset planes in groups of MN_BCE_OG: per offset of the group a lane keeps its float64 sum in registers
-//      over all its chunks, as mn_map_scores_pass does; neighbour labels under the same unsigned bound tests.
+//      over all its chunks, as mn_map_scores_pass does; neighbour labels by the same rule (mn_truth_pass.h).
 // Every map element is loaded once and every gradient element stored once; a lane past W loads and stores nothing.
 // The truth mask is read through the cache.  The wave adds its lanes' sums with the fixed butterfly, the workgroup
 // writes all 2 + O values to its slot of the partials buffer (no clearing needed), mn_map_scores_finish adds the
@@ -124,16 +99,14 @@ __global__ __launch_bounds__(MN_BCE_THREADS) void mn_mask_bce_pass(const MnMaskB
         mn_walk_labels<P, false>(A.truth + at, t);
 #pragma unroll
         for (int j = 0; j < P; j++) {
-          // the label is held to 1..G BEFORE it forms an address: the mask is the caller's memory
-          const int cl = ((unsigned)t[j] - 1u < (unsigned)G) ? A.truth_classes[(unsigned)t[j] - 1u] : 0;
-          tc[j] = ((unsigned)cl < (unsigned)C) ? cl : -1;
+          tc[j] = mn_kept_class(t[j], A.truth_classes, G, C);
           kept += tc[j] >= 0 ? 1 : 0;
         }
         for (int q0 = 0; q0 < C; q0 += MN_BCE_CG) {
           float v[MN_BCE_CG][P];
 #pragma unroll
           for (int q = 0; q < MN_BCE_CG; q++)
-            if (q0 + q < C) mn_bce_load<DT, P>(A.cls, (size_t)(q0 + q) * N + at, wide, v[q]);
+            if (q0 + q < C) mn_plane_load<DT, false, P>(A.cls, (size_t)(q0 + q) * N + at, wide, v[q]);
 #pragma unroll
           for (int q = 0; q < MN_BCE_CG; q++) {
             if (q0 + q >= C) continue;
@@ -145,16 +118,13 @@ __global__ __launch_bounds__(MN_BCE_THREADS) void mn_mask_bce_pass(const MnMaskB
               s_cls += keep ? term : 0.0;
               if (want) g[j] = keep ? mn_bce_grad(v[q][j], yes, scale) : 0.0f;
             }
-            if (want) mn_bce_store<DT, P>(A.gcls, (size_t)(q0 + q) * N + at, wide, g);
+            if (want) mn_plane_store<DT, P>(A.gcls, (size_t)(q0 + q) * N + at, wide, g);
           }
         }
       }
     }
     long long n = kept;
-    for (int s = 32; s > 0; s >>= 1) {                 // a fixed butterfly: the same grouping on every run
-      s_cls += __shfl_xor(s_cls, s);
-      n += __shfl_xor(n, s);
-    }
+    mn_wave_sums(s_cls, n);
     if (lane == 0) {
       sh_part[wv][0] = s_cls;
       sh_part[wv][1 + O] = (double)n;                  // (an integer below 2^53: exact)
@@ -177,18 +147,16 @@ __global__ __launch_bounds__(MN_BCE_THREADS) void mn_mask_bce_pass(const MnMaskB
         float v[MN_BCE_OG][P];
 #pragma unroll
         for (int g = 0; g < MN_BCE_OG; g++)
-          if (g0 + g < O) mn_bce_load<DT, P>(A.same, (size_t)(g0 + g) * N + at, wide, v[g]);
+          if (g0 + g < O) mn_plane_load<DT, false, P>(A.same, (size_t)(g0 + g) * N + at, wide, v[g]);
         int t[P];
         mn_walk_labels<P, false>(A.truth + at, t);
 #pragma unroll
         for (int g = 0; g < MN_BCE_OG; g++) {
           if (g0 + g >= O) continue;
-          // row + di and column + dj in unsigned arithmetic: |di| <= H and |dj| <= W (the entry point holds them to
-          // that), so a sum below 0 wraps to 2^31 or more and fails the same test as one past the edge
           const unsigned yy = (unsigned)y + (unsigned)A.di[g0 + g], xx = (unsigned)x + (unsigned)A.dj[g0 + g];
           int nb[P];
 #pragma unroll
-          for (int j = 0; j < P; j++) nb[j] = t[j];    // outside the image: "same"
+          for (int j = 0; j < P; j++) nb[j] = t[j];    // (the neighbour rule of mn_truth_pass.h)
           if (yy < (unsigned)H) {
             const int* row = A.truth + (size_t)yy * W;
             if (P >= 4 && xx < (unsigned)W && xx + P <= (unsigned)W) {
@@ -206,24 +174,18 @@ __global__ __launch_bounds__(MN_BCE_THREADS) void mn_mask_bce_pass(const MnMaskB
             s_same[g] += (double)mn_bce_term(v[g][j], yes);
             if (want) gr[j] = mn_bce_grad(v[g][j], yes, scale);
           }
-          if (want) mn_bce_store<DT, P>(A.gsame, (size_t)(g0 + g) * N + at, wide, gr);
+          if (want) mn_plane_store<DT, P>(A.gsame, (size_t)(g0 + g) * N + at, wide, gr);
         }
       }
 #pragma unroll
       for (int g = 0; g < MN_BCE_OG; g++) {
         if (g0 + g >= O) continue;
         double a = s_same[g];
-        for (int s = 32; s > 0; s >>= 1) a += __shfl_xor(a, s);
+        mn_wave_sums(a);
         if (lane == 0) sh_part[wv][1 + g0 + g] = a;
       }
     }
   }
 
-  __syncthreads();
-  for (int i = threadIdx.x; i < 2 + O; i += MN_BCE_THREADS) {
-    double s = sh_part[0][i];
-#pragma unroll
-    for (int q = 1; q < MN_BCE_WAVES; q++) s += sh_part[q][i];
-    A.partials[(size_t)i * A.walk.blocks + blockIdx.x] = s;
-  }
+  mn_truth_flush<MN_BCE_WAVES>(sh_part, 2 + O, A.partials, A.walk.blocks);
 }

@@ -19,22 +19,15 @@
 #pragma once
 
 #include "mn_device.h"
-#include "mn_kernels_cc.h"        // the streaming typed loaders (mn_ld_stream*_t)
 #include "mn_row_walk.h"
+#include "mn_truth_pass.h"        // what this pass shares with mn_mask_bce_pass: the grid, the truth reads, the sums
 
-#ifndef MN_MS_WORKGROUPS
-#define MN_MS_WORKGROUPS 1024     /* most workgroups of the pass = most slots of the partials buffer (4 per CU) */
-#endif
-#ifndef MN_MS_MIN_CHUNKS
-#define MN_MS_MIN_CHUNKS 2        /* a wave takes at least this many chunks before the grid grows */
-#endif
 #define MN_MS_THREADS 256
 #define MN_MS_WAVES (MN_MS_THREADS / 64)
 #define MN_MS_OG 5                /* offsets whose loads are in flight together (and whose sums a lane holds) */
 #define MN_MS_CG 4                /* class planes whose loads are in flight together */
 #define MN_MS_LDS_CLASSES 32      /* C <= this: the confusion counts of a workgroup gather in LDS (C * C ints, 4 KB
                                      at most -- no occupancy lost); above it every count is a global atomic */
-#define MN_MS_VALUES (3 * MN_MAX_OFFSETS)
 #define MN_MS_MAX_WIDTH (1 << 30) /* widest image taken: a row's chunks are counted in ints, chunk * 64 * V + lane * V
                                      stays below W + 512 (the entry point refuses a wider image) */
 
@@ -56,31 +49,15 @@ __device__ __forceinline__ void mn_ms_count(int* sh, bool lds, unsigned long lon
   else atomicAdd(confusion + key, (unsigned long long)n);
 }
 
-// V consecutive values of one plane, from element i: V = 8 one 16-byte load of 16-bit values, V = 4 one 16-byte
-// (float32) or 8-byte load, V = 1 one element.
-template <int DT, bool LG, int V>
-__device__ __forceinline__ void mn_ms_load(const void* base, size_t i, float* v) {
-  if constexpr (V == 8) {
-    mn_ld_stream8_t<DT, LG>(base, i, v);
-  } else if constexpr (V == 4) {
-    const float4 t = mn_ld_stream4_t<DT, LG>(base, i);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = mn_ld_stream1_t<DT, LG>(base, i);
-  }
-}
-
 // The walk of mn_row_walk.h, V = 8, 4 or 1 by the maps' width and bases (the truth mask is read unaligned), in two
 // passes over the wave's chunks, so that every map element is loaded once:
 //   1. the class planes, MN_MS_CG in flight: the running argmax per pixel (a later plane wins only when greater:
 //      the lowest index among equals), then one count per pixel at (truth class, predicted class);
 //   2. the sameness planes in groups of MN_MS_OG offsets: per offset of the group a lane keeps its two float64 sums
 //      and its count in registers over all its chunks; the wave adds them up with a fixed butterfly of shuffles.
-// The truth mask is read through the cache: a pixel's own label once per pass and group, its neighbour once per offset.
-// Neighbour reads stay inside the neighbour's ROW of the mask: the 16-byte form only where all four columns are
-// inside 0..W-1, single reads under a column test otherwise; a neighbour row outside the image is not read at all.
-// The workgroup's sums go to its slot of the partials buffer (all 3 * O values are written by every workgroup, so
-// the buffer needs no clearing); mn_map_scores_finish adds the slots up.  No floating-point atomic anywhere.
+// The truth mask is read through the cache: a pixel's own label once per pass and group, its neighbour once per offset
+// (the rule: mn_truth_pass.h).  Every load of a map is the walk's wide one: V follows the bases.  The workgroup's 3 * O sums
+// go to its slot of the partials buffer, mn_map_scores_finish adds the slots up.  No floating-point atomic anywhere.
 template <int DT, bool LG, int V>
 __global__ __launch_bounds__(MN_MS_THREADS) void mn_map_scores_pass(const MnMapScoreArgs A) {
   __shared__ int sh_conf[MN_MS_LDS_CLASSES * MN_MS_LDS_CLASSES];
@@ -110,7 +87,7 @@ __global__ __launch_bounds__(MN_MS_THREADS) void mn_map_scores_pass(const MnMapS
         float v[MN_MS_CG][V];
 #pragma unroll
         for (int q = 0; q < MN_MS_CG; q++)
-          if (q0 + q < C) mn_ms_load<DT, LG, V>(A.cls, (size_t)(q0 + q) * N + at, v[q]);
+          if (q0 + q < C) mn_plane_load<DT, LG, V>(A.cls, (size_t)(q0 + q) * N + at, true, v[q]);
 #pragma unroll
         for (int q = 0; q < MN_MS_CG; q++) {
           if (q0 + q >= C) continue;
@@ -123,9 +100,8 @@ __global__ __launch_bounds__(MN_MS_THREADS) void mn_map_scores_pass(const MnMapS
       mn_walk_labels<V, false>(A.truth + at, t);
 #pragma unroll
       for (int j = 0; j < V; j++) {
-        // the label is held to 1..G BEFORE it forms an address: the mask is the caller's memory
-        const int tc = ((unsigned)t[j] - 1u < (unsigned)G) ? A.truth_classes[(unsigned)t[j] - 1u] : 0;
-        key[j] = ((unsigned)tc < (unsigned)C) ? tc * C + arg[j] : -1;
+        const int tc = mn_truth_class(t[j], A.truth_classes, G);
+        key[j] = ((unsigned)tc < (unsigned)C) ? tc * C + arg[j] : -1;        // (the test of mn_kept_class)
       }
     }
     // A chunk that lies in one (truth class, predicted class) cell -- most of an image -- is ONE count; any other
@@ -164,18 +140,16 @@ __global__ __launch_bounds__(MN_MS_THREADS) void mn_map_scores_pass(const MnMapS
       float v[MN_MS_OG][V];
 #pragma unroll
       for (int g = 0; g < MN_MS_OG; g++)
-        if (g0 + g < O) mn_ms_load<DT, LG, V>(A.same, (size_t)(g0 + g) * N + at, v[g]);
+        if (g0 + g < O) mn_plane_load<DT, LG, V>(A.same, (size_t)(g0 + g) * N + at, true, v[g]);
       int t[V];
       mn_walk_labels<V, false>(A.truth + at, t);
 #pragma unroll
       for (int g = 0; g < MN_MS_OG; g++) {
         if (g0 + g >= O) continue;
-        // row + di and column + dj in unsigned arithmetic: |di| <= H and |dj| <= W (the entry point holds them to
-        // that), so a sum below 0 wraps to 2^31 or more and fails the same test as one past the edge
         const unsigned yy = (unsigned)y + (unsigned)A.di[g0 + g], xx = (unsigned)x + (unsigned)A.dj[g0 + g];
         int nb[V];
 #pragma unroll
-        for (int j = 0; j < V; j++) nb[j] = t[j];    // outside the image: "same"
+        for (int j = 0; j < V; j++) nb[j] = t[j];    // (the neighbour rule of mn_truth_pass.h)
         if (yy < (unsigned)H) {
           const int* row = A.truth + (size_t)yy * W;
           if (V >= 4 && xx < (unsigned)W && xx + V <= (unsigned)W) {
@@ -201,11 +175,7 @@ __global__ __launch_bounds__(MN_MS_THREADS) void mn_map_scores_pass(const MnMapS
       if (g0 + g >= O) continue;
       double a = s_diff[g], b = s_all[g];
       long long n = n_diff[g];
-      for (int s = 32; s > 0; s >>= 1) {             // a fixed butterfly: the same grouping on every run
-        a += __shfl_xor(a, s);
-        b += __shfl_xor(b, s);
-        n += __shfl_xor(n, s);
-      }
+      mn_wave_sums(a, b, n);
       if (lane == 0) {
         sh_part[wv][g0 + g] = a;
         sh_part[wv][O + g0 + g] = b;
@@ -214,30 +184,10 @@ __global__ __launch_bounds__(MN_MS_THREADS) void mn_map_scores_pass(const MnMapS
     }
   }
 
-  __syncthreads();
-  for (int i = threadIdx.x; i < 3 * O; i += MN_MS_THREADS) {
-    double s = sh_part[0][i];
-#pragma unroll
-    for (int q = 1; q < MN_MS_WAVES; q++) s += sh_part[q][i];
-    A.partials[(size_t)i * A.walk.blocks + blockIdx.x] = s;
-  }
+  mn_truth_flush<MN_MS_WAVES>(sh_part, 3 * O, A.partials, A.walk.blocks);
   if (lds)
     for (int i = threadIdx.x; i < C * C; i += MN_MS_THREADS) {
       const int n = sh_conf[i];
       if (n) atomicAdd(A.confusion + i, (unsigned long long)n);
     }
-}
-
-// One wave per value (3 * O of them): lane l adds the slots l*per .. l*per + per-1 in ascending order, the lanes'
-// sums meet in the fixed butterfly.  The image's total is then stored, or -- accumulate -- added to what the
-// caller's buffer holds in ONE IEEE addition: the running total of a validation loop.
-__global__ __launch_bounds__(64) void mn_map_scores_finish(const double* __restrict__ partials, int slots,
-                                                            double* __restrict__ sums, int accumulate) {
-  const int lane = threadIdx.x;
-  const int per = (slots + 63) / 64;
-  const double* p = partials + (size_t)blockIdx.x * slots;
-  double s = 0.0;
-  for (int i = lane * per; i < min(slots, (lane + 1) * per); i++) s += p[i];
-  for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
-  if (lane == 0) sums[blockIdx.x] = accumulate ? sums[blockIdx.x] + s : s;
 }

@@ -1120,6 +1120,19 @@ class Merger:
         1..4 ascending positive values; ``capacity``: records the log holds at first (it grows by doubling)."""
         return DatasetEval(self, num_classes, thresholds, rec_thresholds, area_ranges, max_dets, capacity)
 
+    def _check_truth(self, truth, truth_classes, H, W, dev) -> int:
+        """The ground truth of :meth:`map_scores` and :meth:`mask_bce`: the label mask and the classes of its labels.
+        Returns G, the number of truth labels."""
+        torch = self.torch
+        if self._check_mask(truth) != (H, W) or truth.device != dev:
+            raise ValueError("truth: a mask of the maps' height and width on the maps' GPU")
+        if truth_classes is None:
+            return 0
+        if not (truth_classes.is_cuda and truth_classes.dtype == torch.int32 and truth_classes.is_contiguous()
+                and truth_classes.dim() == 1 and truth_classes.device == dev):
+            raise ValueError("truth_classes: a contiguous int32 [G] tensor on the maps' GPU, or None")
+        return int(truth_classes.numel())
+
     def map_scores(self, class_probs, same_probs, offsets, truth, truth_classes, logits: bool = False, into=None):
         """The network's maps themselves against the ground truth: what ``runningScore.update`` and
         ``offsetIoU.update`` (utils/score.py:20-32,77-86) accumulate per image, in one pass over the maps on the
@@ -1141,14 +1154,7 @@ class Merger:
         fn = self._entry("mn_map_scores_device")
         C, H, W, O, off = self._check(class_probs, same_probs, offsets)
         dev = class_probs.device
-        if self._check_mask(truth) != (H, W) or truth.device != dev:
-            raise ValueError("truth: a mask of the maps' height and width on the maps' GPU")
-        G = 0
-        if truth_classes is not None:
-            if not (truth_classes.is_cuda and truth_classes.dtype == torch.int32 and truth_classes.is_contiguous()
-                    and truth_classes.dim() == 1 and truth_classes.device == dev):
-                raise ValueError("truth_classes: a contiguous int32 [G] tensor on the maps' GPU, or None")
-            G = int(truth_classes.numel())
+        G = self._check_truth(truth, truth_classes, H, W, dev)
         if into is None:
             confusion = torch.empty((C, C), dtype=torch.int64, device=dev)
             sums = torch.empty((3, O), dtype=torch.float64, device=dev)
@@ -1212,14 +1218,7 @@ class Merger:
         off = np.ascontiguousarray(np.asarray(offsets if O else [], dtype=np.int32).reshape(-1, 2))
         if off.shape[0] != O:
             raise ValueError("%d offsets for %d offset planes" % (off.shape[0], O))
-        if self._check_mask(truth) != (H, W) or truth.device != dev:
-            raise ValueError("truth: a mask of the maps' height and width on the maps' GPU")
-        G = 0
-        if truth_classes is not None:
-            if not (truth_classes.is_cuda and truth_classes.dtype == torch.int32 and truth_classes.is_contiguous()
-                    and truth_classes.dim() == 1 and truth_classes.device == dev):
-                raise ValueError("truth_classes: a contiguous int32 [G] tensor on the maps' GPU, or None")
-            G = int(truth_classes.numel())
+        G = self._check_truth(truth, truth_classes, H, W, dev)
         if into is None:
             sums = torch.empty((2 + O,), dtype=torch.float64, device=dev)
         else:

@@ -233,6 +233,29 @@ def test_16_bit_maps_score_as_their_widened_values(merger, dtype, shape):
           "4 bytes off")
 
 
+def far_offsets(shape):
+    """(0, 1), then five offsets that leave the image whatever the pixel: by exactly H rows or W columns, by one more,
+    and by the ends of the int32 range (the entry point holds each to -H..H / -W..W)."""
+    H, W = shape
+    return [(0, 1), (H, 0), (0, -W), (H + 1, 0), (2 ** 31 - 1, -2 ** 31), (-2 ** 31, 2 ** 31 - 1)]
+
+
+@pytest.mark.parametrize("shape,dtype", [((3, 5), "float32"),          # single elements
+                                         ((9, 260), "bfloat16")])       # W % 8 == 4: four pixels per lane
+def test_offsets_beyond_the_image_find_no_different_pixel(merger, shape, dtype):
+    import torch
+    cp, sp, truth = image(shape, span=15)
+    offs = far_offsets(shape)
+    t_cp, t_sp = dev(cp).to(getattr(torch, dtype)), dev(sp[:len(offs)]).to(getattr(torch, dtype))
+    assert t_cp.data_ptr() % 16 == 0 and t_sp.data_ptr() % 16 == 0
+    want = labels.map_scores(t_cp.float().cpu().numpy(), t_sp.float().cpu().numpy(), offs, truth, TRUTH_CLASSES, G_TRUTH)
+    assert want[1][2, 0] > 0 and (want[1][[0, 2], 1:] == 0).all() and (want[1][1] > 0).all()
+    got = merger.map_scores(t_cp, t_sp, offs, dev(truth), classes())
+    check(got, want, truth.size, "%s %s" % (shape, dtype))
+    sums = got["sums"].cpu().numpy()
+    assert (sums[[0, 2], 1:] == 0).all()                         # exactly 0: no neighbour was found, none was read
+
+
 @pytest.mark.parametrize("shape", [(33, 257), (48, 256)])
 def test_float32_logits_equal_the_call_on_their_probabilities_bit_for_bit(merger, shape):
     import torch

@@ -233,6 +233,33 @@ def test_each_base_off_the_boundary_gives_the_same_sums_bit_for_bit(merger, shap
         check_run(res, bufs, shape, dtype, 1.0, 1.0 / 64, "base %d one element off" % which)
 
 
+@pytest.mark.parametrize("shape,dtype", [((3, 5), "float32"),          # single elements
+                                         ((9, 260), "bfloat16")])       # W % 8 == 4: four pixels per lane
+def test_offsets_beyond_the_image_have_target_one_everywhere(merger, shape, dtype):
+    """(0, 1), then five offsets that leave the image whatever the pixel: by exactly H rows or W columns, by one more,
+    and by the ends of the int32 range (the entry point holds each to -H..H / -W..W)."""
+    H, W = shape
+    offs = [(0, 1), (H, 0), (0, -W), (H + 1, 0), (2 ** 31 - 1, -2 ** 31), (-2 ** 31, 2 ** 31 - 1)]
+    cl, sl, truth = image(shape, dtype)
+    sl = sl[:len(offs)]
+    want_sums, gc, gs = labels.mask_bce(cl, sl, offs, truth, TRUTH_CLASSES, G_TRUTH)
+    different = [labels._different(truth.astype(np.int64), di, dj) for di, dj in offs]
+    assert different[0].any() and not any(d.any() for d in different[1:])
+    bufs = (GradBuffer(cl.shape, dtype), GradBuffer(sl.shape, dtype))
+    res = merger.mask_bce(dev(cl, dtype), dev(sl, dtype), offs, dev(truth), classes(), 1.0, 1.0,
+                          out=(bufs[0].view, bufs[1].view))
+    what = "%s %s" % (shape, dtype)
+    check_sums(res["sums"].cpu().numpy(), want_sums, int(want_sums[-1]) * C, truth.size, what)
+    check_grad(bufs[0].view, gc, 1.0, dtype, what + ", class gradient")
+    check_grad(bufs[1].view, gs, 1.0, dtype, what + ", offset gradient")
+    # target 1 everywhere: the gradient sigmoid(x) - 1 is never above 0 (a target of 0 gives sigmoid(x) > 0, also at
+    # x = -80), and the term is softplus(-x)
+    g = bufs[1].view.float().cpu().numpy()
+    assert (g[1:] <= 0).all() and (g[0][different[0]] > 0).all()
+    for b in bufs:
+        b.check_surroundings()
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_parts_may_be_absent(merger, dtype):
     import torch

@@ -8,8 +8,13 @@ The expected values are worked out by hand from the rules; none comes from the f
     chunks_per_row  ceil(W / (64 V)),  total = H * chunks_per_row
     aimed (tables)  4 waves per workgroup, 256 workgroups aimed at: chunks_per_wave = ceil(total / 1024),
                     blocks = ceil(total / (4 * chunks_per_wave))
-    fixed (scores)  blocks given -- mn_map_scores_device: min(1024, ceil(H * ceil(W / (64 * widest V)) / 8)) --
+    fixed (scores)  blocks given -- truth_pass_slots of mn_truth_pass.h, held to the same hand-made grids below --
                     and chunks_per_wave = ceil(total / (4 * blocks))
+
+The host part of mn_truth_pass.h is in the same build: truth_pass_slots, the grid of the passes over the maps and a
+truth mask, and truth_pass_offsets, the clamp of their offsets.  The check program has a main of its own: built with
+the address and undefined-behaviour sanitizers it answers the same tables as a child process (that build is never
+loaded into this one).
 
 CPU only.
 """
@@ -54,12 +59,22 @@ TABLE = [
     ((1024, 2048), 2, OFF8, 512, (4, 8, 8192, 4, 512)),       # the same grid at V = 4: 4 chunks per wave
 ]
 
+# truth_pass_slots: the grids TABLE gives by hand, and one shape that meets the cap of 1024 workgroups
+# (8 chunks per row at 4 float32 values per lane: 4096 * 8 / 8 = 4096)
+SLOTS = sorted({(shape, elem, grid) for shape, elem, _, grid, _ in TABLE if grid is not None}) + [((4096, 2048), 4, 1024)]
+
+# truth_pass_offsets at (H, W) = (3, 5): each offset held to -3..3 / -5..5
+OFFSETS_HW = (3, 5)
+OFFSETS_IN = [(0, 1), (-3, 2), (3, 0), (0, -5), (4, -6), (2 ** 31 - 1, -2 ** 31), (-2 ** 31, 2 ** 31 - 1)]
+OFFSETS_OUT = [(0, 1), (-3, 2), (3, 0), (0, -5), (3, -5), (3, -5), (-3, 5)]
+
+SRC = os.path.join(ROOT, "tests", "tools", "row_walk_check.cpp")
+
 
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
     so = str(tmp_path_factory.mktemp("row_walk") / "librow_walk_host.so")
-    src = os.path.join(ROOT, "tests", "tools", "row_walk_check.cpp")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Werror", src, "-o", so], check=True)
+    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Werror", SRC, "-o", so], check=True)
     lib = ctypes.CDLL(so)
     i32p, i64p = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_longlong)
     lib.row_walk_v_check.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong]
@@ -70,6 +85,10 @@ def host_lib(tmp_path_factory):
     lib.row_walk_span_check.restype = None
     lib.row_walk_cover.argtypes = [ctypes.c_int, ctypes.c_int, i32p, ctypes.c_int, i32p]
     lib.row_walk_cover.restype = ctypes.c_longlong
+    lib.truth_pass_slots_check.argtypes = [ctypes.c_int] * 4
+    lib.truth_pass_slots_check.restype = ctypes.c_int
+    lib.truth_pass_offsets_check.argtypes = [i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, i32p]
+    lib.truth_pass_offsets_check.restype = None
     return lib
 
 
@@ -125,3 +144,40 @@ def test_spans_are_clamped_at_both_ends(host_lib):
     assert span(host_lib, r, 518) == (1035, 1035) and span(host_lib, r, 519) == (1035, 1035)
     r = np.array([1, 2 ** 20, 2 ** 31 - 1, 2 ** 21, 256], np.int32)           # far waves: no overflow of the product
     assert span(host_lib, r, 2 ** 40) == (2 ** 31 - 1, 2 ** 31 - 1)
+
+
+def test_slots_table_holds_the_five_hand_made_grids():
+    assert SLOTS[:-1] == sorted([((256, 1040), 4, 160), ((16, 520), 2, 4), ((9, 260), 2, 2), ((1, 1000), 2, 1),
+                                 ((1024, 2048), 2, 512)])
+
+
+@pytest.mark.parametrize("shape,elem,grid", SLOTS)
+def test_truth_pass_slots(host_lib, shape, elem, grid):
+    assert host_lib.truth_pass_slots_check(shape[0], shape[1], elem, WAVES_PER_BLOCK) == grid
+
+
+def test_truth_pass_offsets(host_lib):
+    H, W = OFFSETS_HW
+    off = np.array(OFFSETS_IN, np.int32)
+    out = np.full_like(off, 99)
+    host_lib.truth_pass_offsets_check(ptr(off), len(OFFSETS_IN), H, W, ptr(out))
+    assert [tuple(int(x) for x in row) for row in out] == OFFSETS_OUT
+    host_lib.truth_pass_offsets_check(None, 0, H, W, None)         # no offsets: nothing is read or written
+
+
+def test_truth_pass_rules_under_the_sanitizers(tmp_path):
+    exe = str(tmp_path / "row_walk_check")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover", SRC, "-o", exe], check=True)
+    H, W = OFFSETS_HW
+    args, want = [], []
+    for shape, elem, grid in SLOTS:
+        args += ["slots", shape[0], shape[1], elem, WAVES_PER_BLOCK]
+        want.append(str(grid))
+    args += ["offsets", H, W, len(OFFSETS_IN)] + [x for pair in OFFSETS_IN for x in pair]
+    want.append(" ".join(str(x) for pair in OFFSETS_OUT for x in pair))
+    args += ["offsets", H, W, 0]
+    want.append("")
+    res = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert res.stdout.split("\n")[:-1] == want, res.stdout + res.stderr
