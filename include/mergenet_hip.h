@@ -755,6 +755,89 @@ int mn_mask_bce_device(mn_context* ctx, const void* d_class_logits, const void* 
                        void* d_grad_class, void* d_grad_same, float scale_class, float scale_same,
                        double* d_sums /* [2+O] */, int accumulate, void* stream);
 
+/* The criteria whose gradient needs totals over a whole plane, from the label mask: the reference's SoftDiceLoss and
+ * MultiBCEWithLogitsLoss (utils/loss.py:38-76; --loss dice / --loss mbce of egs/cityscape/local/train.py:193-204 and
+ * egs/coco/local/train.py:143-154).  The gradient of an element depends on sums over its plane, so there are three
+ * steps -- the sums, a tiny launch for per-plane coefficients, the gradient -- and ONE part of the network's output
+ * per call; no target plane is written or read.  One image per call. */
+#define MN_PART_CLASS 0          /* the class planes of mn_mask_bce_device: their targets and their ignore class */
+#define MN_PART_OFFSET 1         /* its offset planes */
+#define MN_PLANE_COMPLEMENT 1    /* flag: q = sigmoid(-x), z = !y (SoftDiceLoss(mode='0')) */
+#define MN_PLANE_TERMS 2         /* flag of the sums: rows 3 and 4, the BCE terms, are wanted */
+#define MN_CRIT_DICE 0
+#define MN_CRIT_MBCE 1
+
+/* Step 1, the sums of one image.
+ *   d_logits [num_planes][height * width]: float32, float16 or bfloat16 LOGITS (`dtype`: MN_DTYPE_*; MN_MAPS_LOGITS
+ *   is not accepted).  x: the element widened exactly to float32.
+ *   part == MN_PART_CLASS: num_planes = C class planes; truth class, target y (1 where the truth class is the plane)
+ *   and ignore class (a truth class outside 0..C-1) as for mn_mask_bce_device.  part == MN_PART_OFFSET: num_planes = O
+ *   offset planes, offset_list a HOST array of O (di, dj) pairs, any values; y = 0 where (r + di, c + dj) is inside
+ *   the image and carries another truth label, else 1; num_truth and d_truth_classes are not used (num_truth >= 0).
+ *   s = 1.0f / (1.0f + expf(-x)) in float32.  Without MN_PLANE_COMPLEMENT q = s and z = y; with it
+ *   q = 1.0f / (1.0f + expf(x)) and z = !y -- not 1 - s, which cancels where z is rare.
+ *   term = softplus(y ? -x : x) in float32, as for mn_mask_bce_device.
+ *   d_sums float64 [5 * num_planes + 1], row r of plane p at d_sums[r * num_planes + p]:
+ *     row 0  Q_p  = sum of q                      row 3  L1_p = sum of term where y
+ *     row 1  I_p  = sum of q where z              row 4  L0_p = sum of term where !y
+ *     row 2  Z_p  = the number of z, exact        last   the pixels that took part, exact: the kept pixels of the
+ *                                                        class part, height * width of the offset part
+ *   each value widened to float64 before it is added.  An ignored pixel is left out of every sum.  Rows 3 and 4 are
+ *   computed only with MN_PLANE_TERMS; without it they are written as 0 and no log1pf is spent.
+ * The sums of a call are bit-identical from run to run and wherever the map lies in memory: no floating-point atomic
+ * is used, which pixels a lane adds up follows (height, width, element type) only, every workgroup writes its partial
+ * sums to its own slot of a buffer of the context and a second launch adds the slots in a fixed order.  accumulate !=
+ * 0: the image's totals are ADDED to what d_sums holds (one IEEE addition per total) -- the totals of a batch, with no
+ * synchronisation between images; accumulate == 0: they are stored.
+ * Accesses: as for mn_mask_bce_device (16-byte loads where the width is a multiple of 4 float32 / 8 16-bit elements
+ * and the base is aligned, 8-byte loads for 16-bit maps of width % 8 == 4 aligned to 8, single elements otherwise).
+ * Any image size (not held to the context's capacity).  1 <= num_planes <= MN_MAX_CLASSES (class part) or
+ * MN_MAX_OFFSETS (offset part).  MN_ERR_ARGUMENT: a null pointer that is needed (d_truth_classes when num_truth > 0 in
+ * the class part, offset_list in the offset part), a non-positive size, height * width > INT_MAX, img_width > 2^30, a
+ * count out of range, an unknown part or flag bit, an unknown dtype or one with MN_MAPS_LOGITS; nothing is launched
+ * then.  The partials buffer of this pass is its own (5 MiB, allocated by the first call, freed with the context);
+ * keep the calls of one context on one stream.  Enqueues on `stream` only: no host synchronisation. */
+int mn_plane_sums_device(mn_context* ctx, const void* d_logits, int dtype /* MN_DTYPE_* */, int img_width,
+                         int img_height, int part, int num_planes, const int* offset_list, const int* d_truth,
+                         int num_truth, const int* d_truth_classes, int flags, double* d_sums /* [5*P+1] */,
+                         int accumulate, void* stream);
+
+/* Step 2, per plane the value of the criterion and the four coefficients of the gradient, from d_sums of step 1 (of
+ * one image, or accumulated over a batch).  One small launch, all in float64; each coefficient is rounded once to
+ * float32.  d_coeffs float32 [4][num_planes]: c0 / c1 multiply q * (1 - q) where z / where !z, c2 / c3 multiply
+ * (s - y) where y / where !y.  With Q, I, Z, L1, L0 the plane's sums:
+ *   MN_CRIT_DICE  D = Q + Z + smooth; value = 1 - (2 I + smooth) / D; c1 = sigma scale (2 I + smooth) / D^2;
+ *                 c0 = c1 - sigma scale 2 / D; c2 = c3 = 0; sigma = -1 with MN_PLANE_COMPLEMENT (dq/dx = -q (1 - q)),
+ *                 else +1.  smooth must be > 0 (D cannot be 0 then).  `pixels` is not used.
+ *   MN_CRIT_MBCE  w = (pixels - Q + 1) / (Q + 1); value = w L1 + L0; c0 = c1 = scale L1 (-(pixels + 2) / (Q + 1)^2)
+ *                 -- the weight depends on x, this is its derivative --; c2 = scale w; c3 = scale.  The sums must come
+ *                 from a call with MN_PLANE_TERMS and without MN_PLANE_COMPLEMENT; the flag is refused here.  `smooth`
+ *                 is not used.
+ * *d_loss gets scale * (the values added over the planes in ascending order): stored, or -- accumulate != 0 -- added
+ * to what it holds in one IEEE addition.  `flags`: MN_PLANE_COMPLEMENT as in step 1 (MN_PLANE_TERMS is accepted and
+ * means nothing here).  MN_ERR_ARGUMENT: a null pointer, num_planes outside 1..MN_MAX_CLASSES, an unknown criterion or
+ * flag bit, the complement with MN_CRIT_MBCE, smooth, scale or pixels not finite, pixels < 0, smooth <= 0 with
+ * MN_CRIT_DICE; nothing is launched then.  Enqueues on `stream` only. */
+int mn_plane_coeffs_device(mn_context* ctx, int criterion, int flags, const double* d_sums, int num_planes,
+                           double pixels, double smooth, double scale, float* d_coeffs /* [4*P] */, double* d_loss,
+                           int accumulate, void* stream);
+
+/* Step 3, the gradient of one image: the arguments of step 1, the coefficients of step 2.
+ *   element = f * (q * (1 - q) * (z ? c0 : c1) + (s - y) * (y ? c2 : c3)) in float32, each operation rounded (no
+ *   fused multiply-add), rounded to nearest even into the element type of the map; an ignored pixel (class part) gets
+ *   0, the store is made.  f = *d_factor, a float32 on the device -- the incoming gradient of a backward pass, read by
+ *   the kernel: no synchronisation, no multiply pass --, or 1 when d_factor is NULL.  When c2 and c3 are zero for
+ *   every plane (MN_CRIT_DICE) the (s - y) part is skipped, by a branch that is uniform over the launch; the value
+ *   is the same either way.
+ *   d_grad [num_planes][height * width] has the element type of d_logits and must not overlap it.  Each logit is
+ *   loaded once, each gradient element stored once; wide accesses where BOTH bases admit them.
+ * `flags`: MN_PLANE_COMPLEMENT as in step 1.  MN_ERR_ARGUMENT: as for step 1, and a null d_coeffs or d_grad; nothing
+ * is launched then.  Enqueues on `stream` only: no host synchronisation. */
+int mn_plane_grad_device(mn_context* ctx, const void* d_logits, int dtype /* MN_DTYPE_* */, int img_width,
+                         int img_height, int part, int num_planes, const int* offset_list, const int* d_truth,
+                         int num_truth, const int* d_truth_classes, int flags, const float* d_coeffs /* [4*P] */,
+                         const float* d_factor, void* d_grad, void* stream);
+
 /* Wire format of the multi-GPU mask exchange (the all-gather of final instance masks the north
  * star asks for; the reference has no exchange, its jobs write files: segment.py:59-61).  d_wire is
  * int16 [n_pixels + 1 + max_instances + 4]: the labels (0..K), K, the classes of labels 1..K

@@ -26,6 +26,7 @@
 #include "mn_kernels_cc.h"
 #include "mn_kernels_mapscore.h"
 #include "mn_kernels_loss.h"
+#include "mn_kernels_planeloss.h"
 #include "mn_kernels_rle.h"
 #include "mn_kernels_tiles.h"
 #include "mn_sweep_form.h"
@@ -168,6 +169,7 @@ struct mn_context {
   MnMatchWork* match_work;  // scratch of mn_match_overlaps_device (mn_kernels_match.h): allocated on first use
   MnEvalWork* eval_work;    // scratch of mn_eval_append_device (mn_kernels_eval.h): allocated on first use
   double* ms_partials;      // [MN_MS_VALUES][MN_MS_WORKGROUPS] partial sums of mn_map_scores_device: allocated on first use
+  double* pl_partials;      // [MN_PL_VALUES][MN_MS_WORKGROUPS] partial sums of mn_plane_sums_device: allocated on first use
   // workspace of the exact engine (mn_kernels_exact.h): allocated on first use, for the largest
   // image seen so far
   struct XWork {
@@ -510,7 +512,7 @@ extern "C" void mn_destroy(mn_context* c) {
                  c->label, c->mapbuf, c->lpsum, c->lp_acc, c->ball, c->bsub, c->fin_lists, c->cc_tcount, c->cc_lcount, c->cc_bits, c->cc_roots, c->cc_negbits,
                  c->block_count, c->wire_counts, c->partial, c->statblk,
                  c->bg_key, c->gmax, c->touch, c->theta, c->progress, c->d_class, c->d_same, c->d_mask, c->d_objcls, c->d_part,
-                 c->match_work, c->eval_work, c->ms_partials};
+                 c->match_work, c->eval_work, c->ms_partials, c->pl_partials};
   for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); i++)
     if (dev[i]) (void)hipFree(dev[i]);
   x_free(c);
@@ -2998,6 +3000,98 @@ extern "C" int mn_mask_bce_device(mn_context* c, const void* d_class_logits, con
   });
   hipLaunchKernelGGL(mn_map_scores_finish, dim3(2 + O), dim3(64), 0, st, (const double*)c->ms_partials, slots,
                      d_sums, accumulate);
+  MN_HIP(hipGetLastError());
+  return done(MN_OK);
+}
+
+// ---- Dice and weighted multi-BCE from the label mask (mn_kernels_planeloss.h) ----------------------------
+// Enqueue only: no host synchronisation, no copy.  Nothing of the segmentation path runs here.
+// What the sums and the gradient pass check alike, and the kernel argument they share (d_grad: null for the sums).
+static bool plane_call(MnPlaneArgs* A, const mn_context* c, const void* d_logits, int dtype, int W, int H, int part,
+                       int NP, const int* offset_list, const int* d_truth, int G, const int* d_truth_classes,
+                       int flags, void* d_grad) {
+  const bool cls = part == MN_PART_CLASS;
+  if (!c || !d_logits || !d_truth || H <= 0 || W <= 0 || (!cls && part != MN_PART_OFFSET) || NP < 1 ||
+      NP > (cls ? MN_MAX_CLASSES : MN_MAX_OFFSETS) || (!cls && !offset_list) || G < 0 ||
+      (cls && G > 0 && !d_truth_classes) || (size_t)H * (size_t)W > (size_t)INT_MAX || W > MN_MS_MAX_WIDTH ||
+      !dtype_ok(dtype, false) || (flags & ~(MN_PLANE_COMPLEMENT | MN_PLANE_TERMS)))
+    return false;
+  memset(A, 0, sizeof(*A));
+  A->maps = d_logits; A->grad = d_grad; A->truth = d_truth; A->truth_classes = cls ? d_truth_classes : nullptr;
+  A->H = H; A->W = W; A->NP = NP; A->G = cls ? G : 0; A->part = part;
+  A->comp = (flags & MN_PLANE_COMPLEMENT) ? 1 : 0;
+  if (!cls) truth_pass_offsets(offset_list, NP, H, W, A->di, A->dj);
+  // The grid by (H, W, element type) alone.  So are the pixels a lane holds (row_walk_v without bases); the bases
+  // only decide between wide accesses and single elements.
+  const int elem = (dtype & 0xFF) == MN_DTYPE_F32 ? 4 : 2;
+  const int slots = truth_pass_slots(H, W, elem, MN_PL_WAVES);
+  const int p = row_walk_v(W, elem, nullptr);
+  A->wide = row_walk_v(W, elem, d_logits, d_grad) == p ? 1 : 0;
+  A->walk = row_walk_fixed(H, W, p, slots, MN_PL_WAVES);
+  return true;
+}
+
+extern "C" int mn_plane_sums_device(mn_context* c, const void* d_logits, int dtype, int img_width, int img_height,
+                                    int part, int num_planes, const int* offset_list, const int* d_truth,
+                                    int num_truth, const int* d_truth_classes, int flags, double* d_sums,
+                                    int accumulate, void* stream) {
+  MnPlaneArgs A;
+  if (!d_sums || !plane_call(&A, c, d_logits, dtype, img_width, img_height, part, num_planes, offset_list, d_truth,
+                             num_truth, d_truth_classes, flags, nullptr))
+    return done(MN_ERR_ARGUMENT);
+  MN_HIP(hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (!c->pl_partials) MN_HIP(dev_alloc(c, &c->pl_partials, (size_t)MN_PL_VALUES * MN_MS_WORKGROUPS));
+  A.partials = c->pl_partials;
+  const int slots = A.walk.blocks;
+  const dim3 g((unsigned)slots), b(MN_PL_THREADS);
+  by_dtype(dtype & 0xFF, [&](auto t) {
+    by_pixels(t, A.walk.v, [&](auto px) {
+      constexpr int DT = decltype(t)::value, V = decltype(px)::value;
+      if (flags & MN_PLANE_TERMS) hipLaunchKernelGGL((mn_plane_sums_pass<DT, V, true>), g, b, 0, st, A);
+      else hipLaunchKernelGGL((mn_plane_sums_pass<DT, V, false>), g, b, 0, st, A);
+    });
+  });
+  hipLaunchKernelGGL(mn_map_scores_finish, dim3(MN_PL_ROWS * num_planes + 1), dim3(64), 0, st,
+                     (const double*)c->pl_partials, slots, d_sums, accumulate);
+  MN_HIP(hipGetLastError());
+  return done(MN_OK);
+}
+
+extern "C" int mn_plane_coeffs_device(mn_context* c, int criterion, int flags, const double* d_sums, int num_planes,
+                                      double pixels, double smooth, double scale, float* d_coeffs, double* d_loss,
+                                      int accumulate, void* stream) {
+  const bool dice = criterion == MN_CRIT_DICE;
+  if (!c || !d_sums || !d_coeffs || !d_loss || num_planes < 1 || num_planes > MN_MAX_CLASSES ||
+      (!dice && criterion != MN_CRIT_MBCE) || (flags & ~(MN_PLANE_COMPLEMENT | MN_PLANE_TERMS)) ||
+      (!dice && (flags & MN_PLANE_COMPLEMENT)) || !std::isfinite(pixels) || !std::isfinite(smooth) ||
+      !std::isfinite(scale) || pixels < 0.0 || (dice && !(smooth > 0.0)))
+    return done(MN_ERR_ARGUMENT);
+  MN_HIP(hipSetDevice(c->device));
+  hipLaunchKernelGGL(mn_plane_coeffs, dim3(1), dim3(MN_PL_COEFF_THREADS), 0, static_cast<hipStream_t>(stream),
+                     criterion, (flags & MN_PLANE_COMPLEMENT) ? 1 : 0, d_sums, num_planes, pixels, smooth, scale,
+                     d_coeffs, d_loss, accumulate);
+  MN_HIP(hipGetLastError());
+  return done(MN_OK);
+}
+
+extern "C" int mn_plane_grad_device(mn_context* c, const void* d_logits, int dtype, int img_width, int img_height,
+                                    int part, int num_planes, const int* offset_list, const int* d_truth,
+                                    int num_truth, const int* d_truth_classes, int flags, const float* d_coeffs,
+                                    const float* d_factor, void* d_grad, void* stream) {
+  MnPlaneArgs A;
+  if (!d_coeffs || !d_grad || !plane_call(&A, c, d_logits, dtype, img_width, img_height, part, num_planes,
+                                          offset_list, d_truth, num_truth, d_truth_classes, flags, d_grad))
+    return done(MN_ERR_ARGUMENT);
+  MN_HIP(hipSetDevice(c->device));
+  A.coeffs = d_coeffs; A.factor = d_factor;
+  const dim3 g((unsigned)A.walk.blocks), b(MN_PL_THREADS);
+  by_dtype(dtype & 0xFF, [&](auto t) {
+    by_pixels(t, A.walk.v, [&](auto px) {
+      hipLaunchKernelGGL((mn_plane_grad_pass<decltype(t)::value, decltype(px)::value>), g, b, 0,
+                         static_cast<hipStream_t>(stream), A);
+    });
+  });
   MN_HIP(hipGetLastError());
   return done(MN_OK);
 }

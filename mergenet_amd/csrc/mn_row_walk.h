@@ -1,6 +1,7 @@
 // mn_row_walk.h -- the one walk of the passes that stream a label mask (and the maps beside it) row by row:
-// mn_instance_table_runs, mn_overlap_table_runs, mn_map_scores_pass, mn_mask_bce_pass (what the last two share beyond
-// the walk -- their grid, the truth reads, the sums -- is mn_truth_pass.h).  The host part is plain C++ that g++ alone
+// mn_instance_table_runs, mn_overlap_table_runs, mn_map_scores_pass, mn_mask_bce_pass, mn_plane_sums_pass and
+// mn_plane_grad_pass (what the last four share beyond the walk -- their grid, the truth reads, the sums -- is
+// mn_truth_pass.h).  The host part is plain C++ that g++ alone
 // compiles (tests/tools/row_walk_check.cpp, tests/test_row_walk.py).
 // A chunk is 64 * V consecutive pixels of ONE row; lane l of the wave holds pixels V*l .. V*l + V-1 of it.  The image
 // is total_chunks = H * chunks_per_row (<= H * W) chunks, numbered row by row; wave w of the grid takes the

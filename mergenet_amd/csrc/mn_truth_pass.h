@@ -1,7 +1,9 @@
 // mn_truth_pass.h -- what the passes over the network's maps and a truth label mask share: mn_map_scores_pass
-// (mn_kernels_mapscore.h) and mn_mask_bce_pass (mn_kernels_loss.h).  Both walk the image by mn_row_walk.h, read a
-// pixel's truth label and its neighbours' under ONE rule, keep float64 sums per lane, add them up in a fixed order
-// into the workgroup's slot of one partials buffer, and leave the slots to mn_map_scores_finish.  The host part -- the
+// (mn_kernels_mapscore.h), mn_mask_bce_pass (mn_kernels_loss.h) and mn_plane_sums_pass / mn_plane_grad_pass
+// (mn_kernels_planeloss.h).  They walk the image by mn_row_walk.h, read a pixel's truth label and its neighbours'
+// under ONE rule, keep float64 sums per lane, add them up in a fixed order into the workgroup's slot of a partials
+// buffer (one for the first two, one of its own for the plane sums), and leave the slots to mn_map_scores_finish
+// (the gradient pass of the plane losses keeps no sums).  The host part -- the
 // grid and the clamp of the offsets -- is plain C++ that g++ alone compiles (tests/tools/row_walk_check.cpp,
 // tests/test_row_walk.py).
 #pragma once

@@ -631,3 +631,192 @@ def mask_bce(class_logits, same_logits, offsets, truth, truth_classes, num_truth
         grad_same[k] = (expit(x) - y) * float(scale_same)
     sums[1 + O] = float(keep.sum())
     return sums, grad_class, grad_same
+
+
+# ---- Dice and weighted multi-BCE from the label mask: the numpy statements of Merger.plane_sums / plane_coeffs /
+# plane_grad and of losses.MaskDiceLoss / MaskMultiBCELoss (SoftDiceLoss and MultiBCEWithLogitsLoss of utils/loss.py:
+# 38-76 on the targets of utils/dataset.py:259-277 and :419-429, looked up in the label mask) -------------------------
+
+PART_CLASS, PART_OFFSET = 0, 1
+
+
+def _part_of(part) -> int:
+    if part in (PART_CLASS, "class"):
+        return PART_CLASS
+    if part in (PART_OFFSET, "offset"):
+        return PART_OFFSET
+    raise ValueError("part: 'class' or 'offset'")
+
+
+def _expit(x):
+    e = np.exp(-np.abs(x))
+    return np.where(x >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+
+
+def plane_targets(part, num_planes: int, offsets, truth, truth_classes, num_truth: int):
+    """(y bool [P,H,W], keep bool [H,W]): the targets of one part of the output and the pixels that take part.
+
+    Class part: y of plane q is 1 where the truth class (:func:`map_scores`) is q; a pixel whose truth class lies
+    outside 0..P-1 is ignored.  Offset part: y of plane k = (di, dj) is 0 where (r + di, c + dj) is inside the image
+    and carries another truth label (the labels as they stand), else 1; every pixel takes part."""
+    t = np.asarray(truth).astype(np.int64)
+    H, W = t.shape
+    P = int(num_planes)
+    if _part_of(part) == PART_CLASS:
+        tcls = _truth_class_of(t, truth_classes, num_truth)
+        return np.stack([tcls == q for q in range(P)]), (tcls >= 0) & (tcls < P)
+    offs = np.asarray(offsets, np.int64).reshape(-1, 2)
+    if offs.shape[0] != P:
+        raise ValueError("%d offsets for %d offset planes" % (offs.shape[0], P))
+    return np.stack([~_different(t, di, dj) for di, dj in offs.tolist()]), np.ones((H, W), bool)
+
+
+def plane_sums(logits, part, offsets, truth, truth_classes, num_truth: int, complement: bool = False,
+               terms: bool = True):
+    """float64 [5*P + 1] of one image: per plane p ``Q = sum q`` at [p], ``I = sum of q where z`` at [P + p], ``Z =
+    number of z`` at [2P + p], ``L1 = sum of term where y`` at [3P + p], ``L0 = sum of term where !y`` at [4P + p]
+    (both 0 without ``terms``), then the number of pixels that took part.
+
+    x is the element widened exactly to float64 (float64 logits are taken as they are), and so is all else.  ``q = expit(x)``, ``z = y``;
+    ``complement``: ``q = expit(-x)``, ``z = !y``.  ``term = logaddexp(0, -x where y else x)``.  Ignored pixels
+    (:func:`plane_targets`) are left out of every sum.  Each sum is the correctly rounded one (``math.fsum``)."""
+    x = np.asarray(logits).astype(np.float64)
+    P = x.shape[0]
+    y, keep = plane_targets(part, P, offsets, truth, truth_classes, num_truth)
+    sums = np.zeros(5 * P + 1, np.float64)
+    for p in range(P):
+        xp, yp = x[p][keep], y[p][keep]
+        q = _expit(-xp if complement else xp)
+        z = ~yp if complement else yp
+        sums[p] = math.fsum(q.tolist())
+        sums[P + p] = math.fsum(q[z].tolist())
+        sums[2 * P + p] = float(z.sum())
+        if terms:
+            term = np.logaddexp(0.0, np.where(yp, -xp, xp))
+            sums[3 * P + p] = math.fsum(term[yp].tolist())
+            sums[4 * P + p] = math.fsum(term[~yp].tolist())
+    sums[5 * P] = float(keep.sum())
+    return sums
+
+
+def plane_coeffs(criterion: str, sums, pixels: float = 0.0, smooth: float = 1.0, scale: float = 1.0,
+                 complement: bool = False):
+    """(coeffs float64 [4,P], loss): per plane the coefficients of :func:`plane_grad` and ``scale`` times the sum of
+    the planes' values, from the sums of :func:`plane_sums` (of one image or added over a batch).  The device rounds
+    each coefficient once to float32; these are not rounded.
+
+    ``'dice'``: ``D = Q + Z + smooth``, value ``1 - (2I + smooth)/D``, ``c1 = sigma*scale*(2I + smooth)/D^2``, ``c0 =
+    c1 - sigma*scale*2/D``, ``c2 = c3 = 0``; sigma is -1 with ``complement`` (dq/dx = -q(1-q)), else 1.
+    ``'mbce'``: ``w = (pixels - Q + 1)/(Q + 1)``, value ``w*L1 + L0``, ``c0 = c1 = scale*L1*(-(pixels + 2)/(Q + 1)^2)``
+    -- the weight is a function of x, this is its derivative --, ``c2 = scale*w``, ``c3 = scale``."""
+    s = np.asarray(sums, np.float64).reshape(-1)
+    P = (s.size - 1) // 5
+    if s.size != 5 * P + 1 or P < 1:
+        raise ValueError("sums: 5*P + 1 values")
+    Q, I, Z, L1, L0 = (s[r * P:(r + 1) * P] for r in range(5))
+    scale = float(scale)
+    if criterion == "dice":
+        if not smooth > 0:
+            raise ValueError("smooth must be > 0")
+        sigma = -1.0 if complement else 1.0
+        D, top = Q + Z + float(smooth), 2.0 * I + float(smooth)
+        value = 1.0 - top / D
+        c1 = sigma * scale * top / (D * D)
+        c0 = c1 - sigma * scale * 2.0 / D
+        c2 = c3 = np.zeros(P)
+    elif criterion == "mbce":
+        if complement:
+            raise ValueError("mbce has no complement")
+        S1 = Q + 1.0
+        w = (float(pixels) - Q + 1.0) / S1
+        value = w * L1 + L0
+        c0 = c1 = scale * L1 * (-(float(pixels) + 2.0) / (S1 * S1))
+        c2, c3 = scale * w, np.full(P, scale)
+    else:
+        raise ValueError("criterion: 'dice' or 'mbce'")
+    total = 0.0
+    for v in value.tolist():                       # (ascending planes, as the device adds them)
+        total += v
+    return np.stack([c0, c1, c2, c3]).astype(np.float64), total * scale
+
+
+def plane_grad(logits, part, offsets, truth, truth_classes, num_truth: int, coeffs, factor: float = 1.0,
+               complement: bool = False):
+    """float64 [P,H,W]: ``factor * (q*(1-q)*(c0 where z else c1) + (s - y)*(c2 where y else c3))`` with ``s =
+    expit(x)`` and q, z as in :func:`plane_sums`; 0 at an ignored pixel."""
+    x = np.asarray(logits).astype(np.float64)
+    P = x.shape[0]
+    c = np.asarray(coeffs, np.float64).reshape(4, P)
+    y, keep = plane_targets(part, P, offsets, truth, truth_classes, num_truth)
+    s = _expit(x)
+    q = _expit(-x) if complement else s
+    z = ~y if complement else y
+    pick = lambda m, a, b: np.where(m, a[:, None, None], b[:, None, None])
+    g = float(factor) * (q * (1.0 - q) * pick(z, c[0], c[1]) + (s - y) * pick(y, c[2], c[3]))
+    return np.where(keep[None], g, 0.0)
+
+
+def _batch_targets(prediction, part, offsets, truth, truth_classes):
+    x = np.asarray(prediction).astype(np.float64)
+    B, P = x.shape[:2]
+    if truth_classes is None:
+        truth_classes = [None] * B
+    y, keep = [], []
+    for b in range(B):
+        tc = truth_classes[b]
+        yb, kb = plane_targets(part, P, offsets, truth[b], tc, 0 if tc is None else len(tc))
+        y.append(yb)
+        keep.append(np.broadcast_to(kb[None], yb.shape))
+    return x, np.stack(y), np.stack(keep)
+
+
+def dice_loss(prediction, part, offsets, truth, truth_classes=None, mode: str = "1", smooth: float = 1.0):
+    """(loss, gradient float64 [B,P,H,W]) of ``SoftDiceLoss(mode, smooth)`` (utils/loss.py:38-58) on one part of a
+    batch, written directly: per plane i over the WHOLE batch ``1 - (2*sum(p*t) + smooth)/(sum(p) + sum(t) + smooth)``
+    with ``p = sigmoid(x)``, the planes added up; mode ``'0'`` takes ``1 - p`` (as ``sigmoid(-x)``) and ``1 - t``.
+    ``prediction`` [B,P,H,W], ``truth`` [B,H,W], ``truth_classes``: per image the classes of its labels or None.
+    Ignored pixels (class part) are left out of every sum and have gradient 0."""
+    if mode not in ("0", "1"):
+        raise ValueError("mode: '0' or '1'")
+    x, y, keep = _batch_targets(prediction, part, offsets, truth, truth_classes)
+    comp = mode == "0"
+    q = np.where(keep, _expit(-x if comp else x), 0.0)
+    z = np.where(keep, ~y if comp else y, False)
+    sigma = -1.0 if comp else 1.0
+    loss, grad = 0.0, np.zeros_like(x)
+    for i in range(x.shape[1]):
+        qi, zi = q[:, i], z[:, i]
+        top = 2.0 * math.fsum(qi[zi].tolist()) + smooth
+        D = math.fsum(qi.reshape(-1).tolist()) + float(zi.sum()) + smooth
+        loss += 1.0 - top / D
+        grad[:, i] = sigma * qi * (1.0 - qi) * (top / (D * D) - np.where(zi, 2.0 / D, 0.0))
+    return loss, np.where(keep, grad, 0.0)
+
+
+def multi_bce_loss(prediction, part, offsets, truth, truth_classes=None):
+    """(loss, gradient float64 [B,P,H,W]) of ``MultiBCEWithLogitsLoss`` (utils/loss.py:63-76) on one part of a batch,
+    written directly: per image and plane ``S = sum sigmoid(x)``, ``w = (n - S + 1)/(S + 1)`` with ``n = H*W``; the
+    element weight is w where the target is 1, else 1; the loss is the mean over all B*P*H*W elements of weight times
+    BCE term.  The gradient is that of this loss as a function of x, the weight INCLUDED (the reference's torch kept it
+    in the graph): ``[(s - y)*(w where y else 1) + L1*(-(n + 2)/(S + 1)^2)*s*(1 - s)] / (B*P*H*W)`` with L1 the sum of
+    the terms of the plane's target-1 elements.  Ignored pixels (class part) are left out of S and L1, contribute 0
+    and have gradient 0; they still count in n and in the divisor."""
+    x, y, keep = _batch_targets(prediction, part, offsets, truth, truth_classes)
+    B, P, H, W = x.shape
+    n, scale = float(H * W), 1.0 / (B * P * H * W)
+    s = _expit(x)
+    term = np.logaddexp(0.0, np.where(y, -x, x))
+    grad = np.zeros_like(x)
+    values = []
+    for b in range(B):
+        for p in range(P):
+            k, yy = keep[b, p], y[b, p] & keep[b, p]
+            S = math.fsum(s[b, p][k].tolist())
+            L1 = math.fsum(term[b, p][yy].tolist())
+            L0 = math.fsum(term[b, p][k & ~yy].tolist())
+            w = (n - S + 1.0) / (S + 1.0)
+            values.append(w * L1 + L0)
+            sp = s[b, p]
+            grad[b, p] = scale * ((sp - y[b, p]) * np.where(y[b, p], w, 1.0)
+                                  + L1 * (-(n + 2.0) / ((S + 1.0) * (S + 1.0))) * sp * (1.0 - sp))
+    return math.fsum(values) * scale, np.where(keep, grad, 0.0)

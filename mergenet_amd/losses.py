@@ -5,6 +5,10 @@ of the network's output and adds them as ``cls_loss + alpha * ofs_loss`` (egs/ci
 utils/train_utils.py:42-79,145-180), against float32 target planes that the dataset materialises.  Here the targets
 are looked up in the int32 label mask, and the loss and its gradient come out of ONE pass per image
 (``Merger.mask_bce``): the logits are read once, the gradient is written once.
+
+``MaskDiceLoss`` and ``MaskMultiBCELoss`` are the recipes' ``--loss dice`` and ``--loss mbce`` (``SoftDiceLoss`` and
+``MultiBCEWithLogitsLoss`` of utils/loss.py) on one part of the output.  Their gradient depends on totals over a whole
+plane, so they take three steps: ``Merger.plane_sums``, ``Merger.plane_coeffs``, ``Merger.plane_grad``.
 """
 from __future__ import annotations
 
@@ -104,3 +108,146 @@ class MaskBCELoss(nn.Module):
     def forward(self, prediction, truth, truth_classes=None):
         want_grad = prediction.requires_grad and torch.is_grad_enabled()     # (grad mode is off inside the Function)
         return _MaskBCE.apply(prediction, self, truth, truth_classes, want_grad)
+
+
+# ---- the criteria whose gradient needs totals over a plane: soft Dice and weighted multi-BCE ----------------------
+
+class _PlaneLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, prediction, module, truth, truth_classes):
+        pred = prediction.detach()
+        loss, sums, coeffs = module._sums_and_coeffs(pred, truth, truth_classes)
+        module.last_sums = sums
+        ctx.save_for_backward(prediction)
+        ctx.module, ctx.truth, ctx.truth_classes, ctx.coeffs = module, truth, truth_classes, coeffs
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (prediction,) = ctx.saved_tensors
+        factor = grad_output.detach().to(torch.float32).contiguous()      # (a device scalar: the kernel reads it)
+        grad = ctx.module._gradient(prediction.detach(), ctx.truth, ctx.truth_classes, ctx.coeffs, factor)
+        return grad, None, None, None
+
+
+class _MaskPlaneLoss(nn.Module):
+    """What :class:`MaskDiceLoss` and :class:`MaskMultiBCELoss` share: one part of the output, three steps."""
+
+    def __init__(self, merger, part, offsets=None):
+        super().__init__()
+        if part not in ("class", "offset"):
+            raise ValueError("part: 'class' or 'offset'")
+        self.merger = merger
+        self.part = part
+        self.offsets = None if offsets is None else [(int(di), int(dj)) for di, dj in offsets]
+        if part == "offset" and not self.offsets:
+            raise ValueError("the offset part needs its offsets")
+        self.last_sums = None
+
+    def _check(self, prediction, truth, truth_classes):
+        if not (prediction.is_cuda and prediction.dim() == 4 and prediction.shape[0] > 0
+                and all(prediction[b].is_contiguous() for b in range(prediction.shape[0]))):
+            raise ValueError("prediction: a [B, P, H, W] tensor on the GPU whose images are contiguous [P, H, W] blocks")
+        B, P, H, W = prediction.shape
+        if self.part == "offset" and P != len(self.offsets):
+            raise ValueError("prediction has %d planes, the criterion %d offsets" % (P, len(self.offsets)))
+        if not (truth.is_cuda and truth.dtype == torch.int32 and truth.is_contiguous()
+                and tuple(truth.shape) == (B, H, W)):
+            raise ValueError("truth: a contiguous int32 [B, H, W] tensor on the GPU")
+        if truth_classes is None:
+            truth_classes = [None] * B
+        if len(truth_classes) != B:
+            raise ValueError("truth_classes: one int32 tensor (or None) per image")
+        return B, P, H, W, truth_classes
+
+    def forward(self, prediction, truth, truth_classes=None):
+        return _PlaneLoss.apply(prediction, self, truth, truth_classes)
+
+
+class MaskDiceLoss(_MaskPlaneLoss):
+    """``SoftDiceLoss(mode, smooth)`` of the reference (utils/loss.py:38-58; ``--loss dice`` of the Cityscapes recipe
+    is mode ``'0'`` on the offset planes, egs/cityscape/local/train.py:193-204) on ONE part of the network's output,
+    from the label mask: no target plane is materialised.
+
+    ``merger``: a :class:`mergenet_amd.segmenter.Merger` on the prediction's GPU; ``part``: ``'class'`` or
+    ``'offset'`` (then ``offsets``, one pair per plane); ``mode='0'`` takes ``1 - p`` and ``1 - t`` (``1 - p`` as
+    ``sigmoid(-x)``: nothing cancels where the zeros are rare); ``smooth`` > 0.
+
+    ``forward(prediction [B, P, H, W], truth [B, H, W] int32, truth_classes=None)``: ``prediction`` float32, float16
+    or bfloat16 LOGITS, possibly a channel slice of the network's output -- every ``prediction[b]`` must be a
+    contiguous [P, H, W] block; ``truth``, ``truth_classes`` as for :class:`MaskBCELoss`.  Returns, as a float32 device
+    scalar, the sum over the planes of ``1 - (2*sum(p*t) + smooth) / (sum(p) + sum(t) + smooth)`` with the sums over
+    the WHOLE batch (``labels.dice_loss`` is the numpy statement).  A pixel whose truth class lies outside 0..P-1
+    (class part) is left out of every sum and gets gradient 0.
+
+    Forward: B passes for the sums, added into one buffer (``last_sums``, float64 [5*P + 1]), and one small launch
+    for the loss and the planes' coefficients; no gradient buffer exists and nothing is synchronised.  Backward: B
+    gradient passes into a fresh tensor of the prediction's dtype; the incoming gradient is read by the kernel as a
+    device scalar.  The prediction is saved, so a result may be back-propagated more than once.  Under
+    ``torch.no_grad()``, or when the prediction requires no gradient, only the forward's launches run."""
+
+    def __init__(self, merger, part, offsets=None, mode: str = "1", smooth: float = 1.0):
+        super().__init__(merger, part, offsets)
+        if mode not in ("0", "1"):
+            raise ValueError("mode: '0' or '1'")
+        if not (smooth > 0 and smooth < float("inf")):
+            raise ValueError("smooth must be finite and > 0")
+        self.mode, self.smooth = mode, float(smooth)
+
+    def _sums_and_coeffs(self, prediction, truth, truth_classes):
+        B, P, H, W, tcs = self._check(prediction, truth, truth_classes)
+        comp = self.mode == "0"
+        sums = None
+        for b in range(B):
+            sums = self.merger.plane_sums(prediction[b], self.part, self.offsets, truth[b], tcs[b], complement=comp,
+                                          terms=False, into=sums)
+        res = self.merger.plane_coeffs("dice", sums, pixels=H * W, smooth=self.smooth, scale=1.0, complement=comp)
+        return res["loss"].to(torch.float32), sums, res["coeffs"]
+
+    def _gradient(self, prediction, truth, truth_classes, coeffs, factor):
+        B, P, H, W, tcs = self._check(prediction, truth, truth_classes)
+        grad = torch.empty((B, P, H, W), dtype=prediction.dtype, device=prediction.device)
+        for b in range(B):
+            self.merger.plane_grad(prediction[b], self.part, self.offsets, truth[b], tcs[b], coeffs, factor=factor,
+                                   complement=self.mode == "0", out=grad[b])
+        return grad
+
+
+class MaskMultiBCELoss(_MaskPlaneLoss):
+    """``MultiBCEWithLogitsLoss`` of the reference (utils/loss.py:63-76, ``--loss mbce``) on ONE part of the network's
+    output, from the label mask.  Per image and plane ``S = sum sigmoid(x)``, ``w = (H*W - S + 1) / (S + 1)``; an
+    element's weight is w where its target is 1, else 1; the loss is the mean over all B*P*H*W elements of weight
+    times BCE term (``labels.multi_bce_loss`` is the numpy statement).  The weight is a function of the prediction
+    and the gradient is that of the loss as stated, the weight's own derivative INCLUDED -- what the reference's torch
+    computed; a current torch refuses to differentiate ``binary_cross_entropy_with_logits`` with respect to its
+    weight.
+
+    Arguments and ``forward`` as for :class:`MaskDiceLoss`.  A pixel whose truth class lies outside 0..P-1 (class
+    part) is left out of S, contributes 0 and gets gradient 0; it still COUNTS in H*W and in the divisor.
+    Forward: per image one pass for the sums (``last_sums``, float64 [B, 5*P + 1]) and one small launch for its
+    coefficients, the loss added up on the device.  Backward: B gradient passes, the incoming gradient read by the
+    kernel.  The prediction is saved, so a result may be back-propagated more than once.
+
+    float16: a gradient scaled by 1 / (B*P*H*W) underflows binary16 at any real image size, and nothing here
+    rescales it behind the caller's back.  Train in bfloat16 or float32, or scale the loss before ``backward`` (the
+    factor reaches the kernel before the rounding to float16)."""
+
+    def _sums_and_coeffs(self, prediction, truth, truth_classes):
+        B, P, H, W, tcs = self._check(prediction, truth, truth_classes)
+        dev = prediction.device
+        sums = torch.empty((B, 5 * P + 1), dtype=torch.float64, device=dev)
+        coeffs = torch.empty((B, 4, P), dtype=torch.float32, device=dev)
+        loss = None
+        for b in range(B):
+            self.merger.plane_sums(prediction[b], self.part, self.offsets, truth[b], tcs[b], terms=True, out=sums[b])
+            loss = self.merger.plane_coeffs("mbce", sums[b], pixels=H * W, scale=1.0 / (B * P * H * W), into=loss,
+                                            out=coeffs[b])["loss"]
+        return loss.to(torch.float32), sums, coeffs
+
+    def _gradient(self, prediction, truth, truth_classes, coeffs, factor):
+        B, P, H, W, tcs = self._check(prediction, truth, truth_classes)
+        grad = torch.empty((B, P, H, W), dtype=prediction.dtype, device=prediction.device)
+        for b in range(B):
+            self.merger.plane_grad(prediction[b], self.part, self.offsets, truth[b], tcs[b], coeffs[b], factor=factor,
+                                   out=grad[b])
+        return grad

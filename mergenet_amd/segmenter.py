@@ -42,6 +42,9 @@ MN_DEBUG_SWEEP_FULL_FORM = 512   # the sweep of components mode leaves the full 
 MN_DEBUG_TILES_1PX = 1024   # the labelling's tile stage takes one pixel per lane (mn_cc_tiles) where it would take four
 MN_DTYPE_F32, MN_DTYPE_F16, MN_DTYPE_BF16 = 0, 1, 2   # enum mn_dtype: element type of the maps (*_t entry points)
 MN_MAPS_LOGITS = 0x100   # or-ed into that dtype: both maps hold logits, the kernels take the sigmoid on load
+MN_PART_CLASS, MN_PART_OFFSET = 0, 1          # the part of the output a plane-loss call takes (Merger.plane_sums)
+MN_PLANE_COMPLEMENT, MN_PLANE_TERMS = 1, 2    # its flags
+MN_CRIT_DICE, MN_CRIT_MBCE = 0, 1             # the criteria of Merger.plane_coeffs
 MN_ERR_ARGUMENT = -1
 MN_ERR_CAPACITY = -4
 MN_MATCH_MAX_INSTANCES = 4096   # most prediction / truth instances of Merger.match_instances
@@ -96,7 +99,7 @@ EXPORTS = ["mn_default_options", "mn_create", "mn_destroy", "mn_workspace_bytes"
            "mn_segment_device", "mn_segment_launch", "mn_segment_finish", "mn_segment_exact_batch", "mn_score_device", "mn_exact_phase_a_device", "mn_sweep_device", "mn_sweep_time_device", "mn_segment_host", "c_run_segmentation",
            "mn_prepare_device", "mn_upsample_mask_device", "mn_rle_points_device", "mn_rle_encode_host", "mn_rle_counts_host", "mn_rle_decode_device", "mn_sameness_targets_device", "mn_instance_scores_device",
            "mn_instance_table_device", "mn_filter_instances_device",
-           "mn_overlap_table_device", "mn_match_overlaps_device", "mn_map_scores_device", "mn_mask_bce_device", "mn_tile_class_maps_device",
+           "mn_overlap_table_device", "mn_match_overlaps_device", "mn_map_scores_device", "mn_mask_bce_device", "mn_plane_sums_device", "mn_plane_coeffs_device", "mn_plane_grad_device", "mn_tile_class_maps_device",
            "mn_eval_append_device", "mn_eval_keys_device", "mn_eval_accumulate_device",
            "mn_pack_wire_device", "mn_runs_wire_words", "mn_pack_runs_device", "mn_unpack_runs_device",
            "mn_unpack_runs_batch_device",
@@ -271,6 +274,21 @@ def load_library() -> ctypes.CDLL:
                                            ctypes.c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_void_p,
                                            ctypes.c_int, ctypes.c_void_p]
         lib.mn_mask_bce_device.restype = ctypes.c_int
+    if hasattr(lib, "mn_plane_sums_device"):             # (absent from older variant builds: MN_LIB)
+        lib.mn_plane_sums_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_void_p,
+                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                             ctypes.c_int, ctypes.c_void_p]
+        lib.mn_plane_sums_device.restype = ctypes.c_int
+        lib.mn_plane_coeffs_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                               ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        lib.mn_plane_coeffs_device.restype = ctypes.c_int
+        lib.mn_plane_grad_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_void_p,
+                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        lib.mn_plane_grad_device.restype = ctypes.c_int
     if hasattr(lib, "mn_tile_class_maps_device"):        # (absent from older variant builds: MN_LIB)
         lib.mn_tile_class_maps_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int,
@@ -1248,6 +1266,131 @@ class Merger:
         if rc != 0:
             raise MergeNetError(rc)
         return {"sums": sums, "grad_class": grads[0], "grad_same": grads[1]}
+
+    def _check_planes(self, logits, part, offsets, truth, truth_classes):
+        """One part of the network's output for :meth:`plane_sums` and :meth:`plane_grad`: returns (part code, dtype
+        code, P, H, W, the offsets as an int32 array or None, G)."""
+        code_of = {"class": MN_PART_CLASS, "offset": MN_PART_OFFSET, MN_PART_CLASS: MN_PART_CLASS,
+                   MN_PART_OFFSET: MN_PART_OFFSET}
+        if part not in code_of:
+            raise ValueError("part: 'class' or 'offset'")
+        part = code_of[part]
+        if not (logits.is_cuda and logits.is_contiguous() and logits.dim() == 3):
+            raise ValueError("expected a contiguous %s [P,H,W] tensor on the GPU" % self.DTYPE_NAMES)
+        if logits.device.index != self.device:
+            raise ValueError("tensor lives on another device than the Merger")
+        code = self._dtype(logits)
+        P, H, W = (int(v) for v in logits.shape)
+        off = None
+        if part == MN_PART_OFFSET:
+            off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int32).reshape(-1, 2))
+            if off.shape[0] != P:
+                raise ValueError("%d offsets for %d offset planes" % (off.shape[0], P))
+        G = self._check_truth(truth, truth_classes if part == MN_PART_CLASS else None, H, W, logits.device)
+        return part, code, P, H, W, off, G
+
+    def plane_sums(self, logits, part, offsets, truth, truth_classes, complement: bool = False, terms: bool = False,
+                   into=None, out=None):
+        """Step 1 of the criteria whose gradient needs totals over a plane (the reference's ``SoftDiceLoss`` and
+        ``MultiBCEWithLogitsLoss``, utils/loss.py:38-76), from the label mask: the sums of one image.  ``logits``
+        [P,H,W]: contiguous float32, float16 or bfloat16 LOGITS of ONE part of the output (a view of the prediction
+        is fine); ``part``: ``'class'`` -- targets and ignore class of :meth:`mask_bce`'s class planes -- or
+        ``'offset'`` with ``offsets`` (P pairs); ``truth``, ``truth_classes``: as for :meth:`mask_bce`
+        (``truth_classes`` is not used by the offset part).  Returns float64 [5*P + 1] on the maps' device: per plane
+        ``Q = sum q``, ``I = sum of q where z``, ``Z = number of z``, ``L1`` / ``L0 = sum of the BCE term where the
+        target is 1 / 0`` (computed only with ``terms``, else 0), then the number of pixels that took part; ``q =
+        sigmoid(x)``, ``z = y``, or with ``complement`` ``q = sigmoid(-x)``, ``z = !y`` (``labels.plane_sums`` is the
+        numpy statement).  ``into``: a previous result, to which this image's sums are added with one IEEE addition
+        each; ``out``: a caller's buffer in which they are stored (a row of a batch's table).  The sums are
+        bit-identical from run to run and do not depend on where the tensor lies.  Any image size; nothing is
+        synchronised or copied.  Keep the calls of one Merger on ONE stream."""
+        torch = self.torch
+        fn = self._entry("mn_plane_sums_device")
+        part, code, P, H, W, off, G = self._check_planes(logits, part, offsets, truth, truth_classes)
+        if into is not None and out is not None:
+            raise ValueError("into (add) or out (store), not both")
+        sums = into if into is not None else out
+        if sums is None:
+            sums = torch.empty((5 * P + 1,), dtype=torch.float64, device=logits.device)
+        elif not (sums.is_cuda and sums.dtype == torch.float64 and sums.is_contiguous()
+                  and tuple(sums.shape) == (5 * P + 1,) and sums.device == logits.device):
+            raise ValueError("into / out: a contiguous float64 [%d] tensor on the maps' GPU" % (5 * P + 1))
+        flags = (MN_PLANE_COMPLEMENT if complement else 0) | (MN_PLANE_TERMS if terms else 0)
+        stream = torch.cuda.current_stream(logits.device).cuda_stream
+        rc = fn(self.handle, logits.data_ptr(), code, W, H, part, P, off.ctypes.data_as(_i32p) if off is not None else None,
+                truth.data_ptr(), G, truth_classes.data_ptr() if G else None, flags, sums.data_ptr(),
+                1 if into is not None else 0, ctypes.c_void_p(stream))
+        if rc != 0:
+            raise MergeNetError(rc)
+        return sums
+
+    def plane_coeffs(self, criterion, sums, pixels: float = 0.0, smooth: float = 1.0, scale: float = 1.0,
+                     complement: bool = False, into=None, out=None):
+        """Step 2: per plane the value of the criterion and the four float32 coefficients of :meth:`plane_grad`, from
+        the ``sums`` of :meth:`plane_sums` (one image's, or a batch's added up), in one small launch in float64.
+        ``criterion``: ``'dice'`` (``smooth`` > 0; ``complement`` as the sums were taken) or ``'mbce'`` (``pixels`` =
+        H*W; sums taken with ``terms=True``).  Returns ``{"coeffs": float32 [4,P], "loss": float64 []}``: the loss is
+        ``scale`` times the planes' values added in ascending order (``labels.plane_coeffs`` is the numpy statement
+        and gives the formulas).  ``out``: a caller's [4,P] buffer for the coefficients; ``into``: a previous loss
+        tensor (or result) to which this loss is ADDED with one IEEE addition."""
+        torch = self.torch
+        fn = self._entry("mn_plane_coeffs_device")
+        crit = {"dice": MN_CRIT_DICE, "mbce": MN_CRIT_MBCE, MN_CRIT_DICE: MN_CRIT_DICE, MN_CRIT_MBCE: MN_CRIT_MBCE}.get(criterion)
+        if crit is None:
+            raise ValueError("criterion: 'dice' or 'mbce'")
+        if not (sums.is_cuda and sums.dtype == torch.float64 and sums.is_contiguous() and sums.dim() == 1
+                and sums.numel() % 5 == 1 and sums.numel() > 1 and sums.device.index == self.device):
+            raise ValueError("sums: a result of plane_sums on the Merger's GPU")
+        P = sums.numel() // 5
+        dev = sums.device
+        coeffs = torch.empty((4, P), dtype=torch.float32, device=dev) if out is None else out
+        if not (coeffs.is_cuda and coeffs.dtype == torch.float32 and coeffs.is_contiguous()
+                and tuple(coeffs.shape) == (4, P) and coeffs.device == dev):
+            raise ValueError("out: a contiguous float32 [4,%d] tensor on the sums' GPU" % P)
+        loss = into["loss"] if isinstance(into, dict) else into
+        if loss is None:
+            loss = torch.empty((), dtype=torch.float64, device=dev)
+        elif not (loss.is_cuda and loss.dtype == torch.float64 and loss.numel() == 1 and loss.device == dev):
+            raise ValueError("into: a float64 scalar on the sums' GPU")
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = fn(self.handle, crit, MN_PLANE_COMPLEMENT if complement else 0, sums.data_ptr(), P, float(pixels),
+                float(smooth), float(scale), coeffs.data_ptr(), loss.data_ptr(), 1 if into is not None else 0,
+                ctypes.c_void_p(stream))
+        if rc != 0:
+            raise MergeNetError(rc)
+        return {"coeffs": coeffs, "loss": loss}
+
+    def plane_grad(self, logits, part, offsets, truth, truth_classes, coeffs, factor=None, complement: bool = False,
+                   out=None):
+        """Step 3: the gradient of one image from its logits, the label mask and the coefficients of
+        :meth:`plane_coeffs` (arguments as for :meth:`plane_sums`): ``factor * (q*(1-q)*(c0 where z else c1) +
+        (s - y)*(c2 where y else c3))`` in float32, rounded into the maps' dtype; 0 at an ignored pixel
+        (``labels.plane_grad`` is the numpy statement).  ``factor``: None for 1, or a float32 scalar tensor on the
+        device that the kernel reads -- the incoming gradient of a backward pass: no synchronisation and no multiply
+        pass.  ``out``: a caller's buffer of the maps' shape and dtype (may be a view; must not overlap the maps).
+        Each logit is read once, each gradient element written once."""
+        torch = self.torch
+        fn = self._entry("mn_plane_grad_device")
+        part, code, P, H, W, off, G = self._check_planes(logits, part, offsets, truth, truth_classes)
+        dev = logits.device
+        if not (coeffs.is_cuda and coeffs.dtype == torch.float32 and coeffs.is_contiguous()
+                and tuple(coeffs.shape) == (4, P) and coeffs.device == dev):
+            raise ValueError("coeffs: a contiguous float32 [4,%d] tensor on the maps' GPU" % P)
+        if factor is not None and not (factor.is_cuda and factor.dtype == torch.float32 and factor.numel() == 1
+                                       and factor.device == dev):
+            raise ValueError("factor: a float32 scalar tensor on the maps' GPU, or None")
+        grad = torch.empty_like(logits) if out is None else out
+        if not (grad.is_cuda and grad.is_contiguous() and grad.dtype == logits.dtype and grad.shape == logits.shape
+                and grad.device == dev):
+            raise ValueError("out: a contiguous buffer of the maps' shape and dtype on the maps' GPU")
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = fn(self.handle, logits.data_ptr(), code, W, H, part, P, off.ctypes.data_as(_i32p) if off is not None else None,
+                truth.data_ptr(), G, truth_classes.data_ptr() if G else None, MN_PLANE_COMPLEMENT if complement else 0,
+                coeffs.data_ptr(), factor.data_ptr() if factor is not None else None, grad.data_ptr(),
+                ctypes.c_void_p(stream))
+        if rc != 0:
+            raise MergeNetError(rc)
+        return grad
 
     def tile_class_maps(self, tiles, flip_tiles, row_starts, col_starts, height: int, width: int, num_classes: int,
                         out_dtype=None, clip: bool = False):
