@@ -16,6 +16,19 @@ import torch
 from torch import nn
 
 
+def _batch_truth(truth, truth_classes, B, H, W):
+    """The ground truth of a batch: ``truth`` a contiguous int32 [B, H, W] tensor on the GPU, ``truth_classes`` a list
+    of B entries or None (no image has instances).  Returns the list."""
+    if not (truth.is_cuda and truth.dtype == torch.int32 and truth.is_contiguous()
+            and tuple(truth.shape) == (B, H, W)):
+        raise ValueError("truth: a contiguous int32 [B, H, W] tensor on the GPU")
+    if truth_classes is None:
+        truth_classes = [None] * B
+    if len(truth_classes) != B:
+        raise ValueError("truth_classes: one int32 tensor (or None) per image")
+    return truth_classes
+
+
 class _MaskBCE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, prediction, module, truth, truth_classes, want_grad):
@@ -83,13 +96,7 @@ class MaskBCELoss(nn.Module):
         B, K, H, W = prediction.shape
         if K != C + O:
             raise ValueError("prediction has %d channels, the criterion %d classes and %d offsets" % (K, C, O))
-        if not (truth.is_cuda and truth.dtype == torch.int32 and truth.is_contiguous()
-                and tuple(truth.shape) == (B, H, W)):
-            raise ValueError("truth: a contiguous int32 [B, H, W] tensor on the GPU")
-        if truth_classes is None:
-            truth_classes = [None] * B
-        if len(truth_classes) != B:
-            raise ValueError("truth_classes: one int32 tensor (or None) per image")
+        truth_classes = _batch_truth(truth, truth_classes, B, H, W)
         scale_class = 1.0 / (B * C * H * W) if C else 0.0
         scale_same = self.alpha / (B * O * H * W) if O else 0.0
         grad = torch.empty_like(prediction) if want_grad else None
@@ -131,7 +138,11 @@ class _PlaneLoss(torch.autograd.Function):
 
 
 class _MaskPlaneLoss(nn.Module):
-    """What :class:`MaskDiceLoss` and :class:`MaskMultiBCELoss` share: one part of the output, three steps."""
+    """What :class:`MaskDiceLoss` and :class:`MaskMultiBCELoss` share: one part of the output, three steps.  A subclass
+    supplies ``_sums_and_coeffs`` and says how the gradient pass takes its coefficients:"""
+
+    complement = False            # with q = sigmoid(-x), z = !y, as the sums were taken (MaskDiceLoss(mode='0'))
+    coeffs_per_image = False      # as [B, 4, P], one set per image, not one [4, P] for the batch
 
     def __init__(self, merger, part, offsets=None):
         super().__init__()
@@ -151,14 +162,16 @@ class _MaskPlaneLoss(nn.Module):
         B, P, H, W = prediction.shape
         if self.part == "offset" and P != len(self.offsets):
             raise ValueError("prediction has %d planes, the criterion %d offsets" % (P, len(self.offsets)))
-        if not (truth.is_cuda and truth.dtype == torch.int32 and truth.is_contiguous()
-                and tuple(truth.shape) == (B, H, W)):
-            raise ValueError("truth: a contiguous int32 [B, H, W] tensor on the GPU")
-        if truth_classes is None:
-            truth_classes = [None] * B
-        if len(truth_classes) != B:
-            raise ValueError("truth_classes: one int32 tensor (or None) per image")
-        return B, P, H, W, truth_classes
+        return B, P, H, W, _batch_truth(truth, truth_classes, B, H, W)
+
+    def _gradient(self, prediction, truth, truth_classes, coeffs, factor):
+        B, P, H, W, tcs = self._check(prediction, truth, truth_classes)
+        grad = torch.empty((B, P, H, W), dtype=prediction.dtype, device=prediction.device)
+        for b in range(B):
+            self.merger.plane_grad(prediction[b], self.part, self.offsets, truth[b], tcs[b],
+                                   coeffs[b] if self.coeffs_per_image else coeffs, factor=factor,
+                                   complement=self.complement, out=grad[b])
+        return grad
 
     def forward(self, prediction, truth, truth_classes=None):
         return _PlaneLoss.apply(prediction, self, truth, truth_classes)
@@ -192,25 +205,17 @@ class MaskDiceLoss(_MaskPlaneLoss):
             raise ValueError("mode: '0' or '1'")
         if not (smooth > 0 and smooth < float("inf")):
             raise ValueError("smooth must be finite and > 0")
-        self.mode, self.smooth = mode, float(smooth)
+        self.mode, self.smooth, self.complement = mode, float(smooth), mode == "0"
 
     def _sums_and_coeffs(self, prediction, truth, truth_classes):
         B, P, H, W, tcs = self._check(prediction, truth, truth_classes)
-        comp = self.mode == "0"
+        comp = self.complement
         sums = None
         for b in range(B):
             sums = self.merger.plane_sums(prediction[b], self.part, self.offsets, truth[b], tcs[b], complement=comp,
                                           terms=False, into=sums)
         res = self.merger.plane_coeffs("dice", sums, pixels=H * W, smooth=self.smooth, scale=1.0, complement=comp)
         return res["loss"].to(torch.float32), sums, res["coeffs"]
-
-    def _gradient(self, prediction, truth, truth_classes, coeffs, factor):
-        B, P, H, W, tcs = self._check(prediction, truth, truth_classes)
-        grad = torch.empty((B, P, H, W), dtype=prediction.dtype, device=prediction.device)
-        for b in range(B):
-            self.merger.plane_grad(prediction[b], self.part, self.offsets, truth[b], tcs[b], coeffs, factor=factor,
-                                   complement=self.mode == "0", out=grad[b])
-        return grad
 
 
 class MaskMultiBCELoss(_MaskPlaneLoss):
@@ -232,6 +237,8 @@ class MaskMultiBCELoss(_MaskPlaneLoss):
     rescales it behind the caller's back.  Train in bfloat16 or float32, or scale the loss before ``backward`` (the
     factor reaches the kernel before the rounding to float16)."""
 
+    coeffs_per_image = True
+
     def _sums_and_coeffs(self, prediction, truth, truth_classes):
         B, P, H, W, tcs = self._check(prediction, truth, truth_classes)
         dev = prediction.device
@@ -243,11 +250,3 @@ class MaskMultiBCELoss(_MaskPlaneLoss):
             loss = self.merger.plane_coeffs("mbce", sums[b], pixels=H * W, scale=1.0 / (B * P * H * W), into=loss,
                                             out=coeffs[b])["loss"]
         return loss.to(torch.float32), sums, coeffs
-
-    def _gradient(self, prediction, truth, truth_classes, coeffs, factor):
-        B, P, H, W, tcs = self._check(prediction, truth, truth_classes)
-        grad = torch.empty((B, P, H, W), dtype=prediction.dtype, device=prediction.device)
-        for b in range(B):
-            self.merger.plane_grad(prediction[b], self.part, self.offsets, truth[b], tcs[b], coeffs[b], factor=factor,
-                                   out=grad[b])
-        return grad

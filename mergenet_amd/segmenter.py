@@ -25,87 +25,17 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import rle as rle_mod
+from .abi import *  # noqa: F401,F403 -- the MN_* constants, MnOptions, MnStats, _f32p, _i32p, SIGNATURES, EXPORTS
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MN_LIB") or os.path.join(_HERE, "libmergenet_hip.so")   # MN_LIB: a variant build (tuning only)
-
-MN_VARIANT_CSEGMENT = 0
-MN_VARIANT_PYSEGMENTER = 1
-MN_MODE_AUTO, MN_MODE_EXACT, MN_MODE_ROUNDS, MN_MODE_COMPONENTS = 0, 1, 2, 3
-MN_ERR_NO_BACKGROUND = -10
-MN_ERR_UNPROVEN = -30
-MN_DEBUG_GENERIC_EDGE_PASS, MN_DEBUG_NO_EVENTS, MN_DEBUG_NO_CORES = 1, 2, 4
-MN_DEBUG_LEAN_EVENTS, MN_DEBUG_REPLAY = 16, 32
-MN_DEBUG_SWEEP_EVENT_PACKETS = 128   # the sweep is timed by an event packet before and behind it
-MN_DEBUG_SWEEP16_4PX = 256    # a 16-bit map's sweep takes 4 pixels per lane (8-byte loads) where it would take 8
-MN_DEBUG_SWEEP_FULL_FORM = 512   # the sweep of components mode leaves the full form of its outputs, not the lean one
-MN_DEBUG_TILES_1PX = 1024   # the labelling's tile stage takes one pixel per lane (mn_cc_tiles) where it would take four
-MN_DTYPE_F32, MN_DTYPE_F16, MN_DTYPE_BF16 = 0, 1, 2   # enum mn_dtype: element type of the maps (*_t entry points)
-MN_MAPS_LOGITS = 0x100   # or-ed into that dtype: both maps hold logits, the kernels take the sigmoid on load
-MN_PART_CLASS, MN_PART_OFFSET = 0, 1          # the part of the output a plane-loss call takes (Merger.plane_sums)
-MN_PLANE_COMPLEMENT, MN_PLANE_TERMS = 1, 2    # its flags
-MN_CRIT_DICE, MN_CRIT_MBCE = 0, 1             # the criteria of Merger.plane_coeffs
-MN_ERR_ARGUMENT = -1
-MN_ERR_CAPACITY = -4
-MN_MATCH_MAX_INSTANCES = 4096   # most prediction / truth instances of Merger.match_instances
-MN_EVAL_RECORD_BYTES = 32        # a record of the evaluation log (DatasetEval)
-MN_EVAL_MAX_AREAS, MN_EVAL_MAX_DETS = 4, 4
-MN_EVAL_CHUNK = 256              # records the accumulate pass scans per step
-MN_PROVE_ALWAYS, MN_PROVE_BY_MODE, MN_PROVE_NEVER = 1, 0, -1   # mn_options.require_proof
-MN_TIES_DEFAULT, MN_TIES_REFERENCE, MN_TIES_LOWEST_ID = 0, 1, 2   # mn_options.tie_order
-MN_PROOF_NONE, MN_PROOF_CERTIFICATE, MN_PROOF_SEQUENTIAL, MN_PROOF_SEQUENTIAL_TIES = 0, 1, 2, 3   # mn_stats.proof
 
 SegmenterOptions = namedtuple("SegmenterOptions",
                               ["same_different_bias", "object_merge_factor", "merge_logprob_bias"])
 
 
-class MnOptions(ctypes.Structure):
-    _fields_ = [("same_different_bias", ctypes.c_float), ("object_merge_factor", ctypes.c_float),
-                ("merge_logprob_bias", ctypes.c_float), ("variant", ctypes.c_int),
-                ("mode", ctypes.c_int), ("clip_inputs", ctypes.c_int),
-                ("exact_limit", ctypes.c_int), ("finish_limit", ctypes.c_int),
-                ("subrounds", ctypes.c_int), ("prune_threshold", ctypes.c_float),
-                ("compute_logprob", ctypes.c_int), ("no_handover_refresh", ctypes.c_int),
-                ("band_permille", ctypes.c_int), ("debug_flags", ctypes.c_int),
-                ("require_proof", ctypes.c_int), ("core_radius", ctypes.c_int),
-                ("tie_order", ctypes.c_int)]
-
-
-class MnStats(ctypes.Structure):
-    _fields_ = [("status", ctypes.c_int), ("mode_used", ctypes.c_int), ("certified", ctypes.c_int),
-                ("num_instances", ctypes.c_int), ("num_objects", ctypes.c_int),
-                ("rounds", ctypes.c_int), ("finisher_steps", ctypes.c_int),
-                ("cert_edge_violations", ctypes.c_int),
-                ("cert_class_violations", ctypes.c_int), ("cert_record_violations", ctypes.c_int),
-                ("initial_records", ctypes.c_longlong),
-                ("merges", ctypes.c_longlong), ("total_logprob", ctypes.c_double),
-                ("ms_score", ctypes.c_float), ("ms_class_pass", ctypes.c_float),
-                ("ms_edge_pass", ctypes.c_float), ("ms_merge", ctypes.c_float),
-                ("ms_output", ctypes.c_float), ("ms_total", ctypes.c_float),
-                ("ms_cc_label", ctypes.c_float), ("ms_cc_sums", ctypes.c_float),
-                ("ms_cc_edges", ctypes.c_float), ("ms_cc_cross", ctypes.c_float),
-                ("proof", ctypes.c_int), ("cores_condemned", ctypes.c_int), ("tied_steps", ctypes.c_int), ("tied_merges", ctypes.c_int),
-                ("tie_order_used", ctypes.c_int), ("tied_conflicts", ctypes.c_int)]
-
-    def as_dict(self) -> dict:
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_i"}
-
-
-_f32p = ctypes.POINTER(ctypes.c_float)
-_i32p = ctypes.POINTER(ctypes.c_int)
 _lib_handle = None
 
-EXPORTS = ["mn_default_options", "mn_create", "mn_destroy", "mn_workspace_bytes",
-           "mn_segment_device", "mn_segment_launch", "mn_segment_finish", "mn_segment_exact_batch", "mn_score_device", "mn_exact_phase_a_device", "mn_sweep_device", "mn_sweep_time_device", "mn_segment_host", "c_run_segmentation",
-           "mn_prepare_device", "mn_upsample_mask_device", "mn_rle_points_device", "mn_rle_encode_host", "mn_rle_counts_host", "mn_rle_decode_device", "mn_sameness_targets_device", "mn_instance_scores_device",
-           "mn_instance_table_device", "mn_filter_instances_device",
-           "mn_overlap_table_device", "mn_match_overlaps_device", "mn_map_scores_device", "mn_mask_bce_device", "mn_plane_sums_device", "mn_plane_coeffs_device", "mn_plane_grad_device", "mn_tile_class_maps_device",
-           "mn_eval_append_device", "mn_eval_keys_device", "mn_eval_accumulate_device",
-           "mn_pack_wire_device", "mn_runs_wire_words", "mn_pack_runs_device", "mn_unpack_runs_device",
-           "mn_unpack_runs_batch_device",
-           "mn_segment_device_t", "mn_segment_launch_t", "mn_segment_exact_batch_t", "mn_score_device_t",
-           "mn_exact_phase_a_device_t", "mn_sweep_device_t", "mn_sweep_time_device_t", "mn_prepare_device_t",
-           "mn_last_status", "mn_status_string", "mn_version"]
 
 def load_library() -> ctypes.CDLL:
     """Load libmergenet_hip.so (built in-tree by ``__graft_entry__.build``); fail loudly."""
@@ -123,194 +53,10 @@ def load_library() -> ctypes.CDLL:
     except ImportError:
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    lib.mn_default_options.argtypes = [ctypes.POINTER(MnOptions)]
-    lib.mn_default_options.restype = None
-    lib.mn_create.argtypes = [ctypes.c_int] * 5
-    lib.mn_create.restype = ctypes.c_void_p
-    lib.mn_destroy.argtypes = [ctypes.c_void_p]
-    lib.mn_destroy.restype = None
-    lib.mn_workspace_bytes.argtypes = [ctypes.c_void_p]
-    lib.mn_workspace_bytes.restype = ctypes.c_size_t
-    lib.mn_segment_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                      ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                      ctypes.c_int, _i32p, ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.POINTER(MnOptions), ctypes.c_void_p,
-                                      ctypes.POINTER(MnStats)]
-    lib.mn_segment_device.restype = ctypes.c_int
-    lib.mn_segment_launch.argtypes = lib.mn_segment_device.argtypes[:-1]
-    lib.mn_segment_launch.restype = ctypes.c_int
-    lib.mn_segment_finish.argtypes = [ctypes.c_void_p, ctypes.POINTER(MnStats)]
-    lib.mn_segment_finish.restype = ctypes.c_int
-    _vpp = ctypes.POINTER(ctypes.c_void_p)
-    lib.mn_segment_exact_batch.argtypes = [_vpp, ctypes.c_int, _vpp, ctypes.c_int, _vpp, ctypes.c_int, ctypes.c_int,
-                                           ctypes.c_int, ctypes.c_int, _i32p, _vpp, _vpp, _vpp,
-                                           ctypes.POINTER(MnOptions), ctypes.c_void_p, ctypes.POINTER(MnStats)]
-    lib.mn_segment_exact_batch.restype = ctypes.c_int
-    if hasattr(lib, "mn_sweep_time_device"):             # (absent from older variant builds: MN_LIB)
-        lib.mn_sweep_time_device.argtypes = [ctypes.c_void_p, _vpp, _vpp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p,
-                                             ctypes.POINTER(MnOptions), ctypes.c_void_p, ctypes.c_int, _f32p]
-        lib.mn_sweep_time_device.restype = ctypes.c_int
-    lib.mn_score_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p,
-                                    ctypes.POINTER(MnOptions), ctypes.c_void_p, ctypes.c_void_p,
-                                    ctypes.c_void_p, _f32p, _f32p]
-    lib.mn_score_device.restype = ctypes.c_int
-    lib.mn_exact_phase_a_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p,
-                                            ctypes.POINTER(MnOptions), ctypes.c_void_p, ctypes.c_void_p,
-                                            ctypes.c_void_p, ctypes.c_void_p]
-    lib.mn_exact_phase_a_device.restype = ctypes.c_int
-    lib.mn_sweep_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
-                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, ctypes.POINTER(MnOptions),
-                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                    ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _i32p]
-    lib.mn_sweep_device.restype = ctypes.c_int
-    lib.mn_segment_host.argtypes = [ctypes.c_void_p, _f32p, ctypes.c_int, _f32p, ctypes.c_int,
-                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _i32p, _i32p,
-                                    _i32p, ctypes.POINTER(MnOptions), ctypes.POINTER(MnStats)]
-    lib.mn_segment_host.restype = ctypes.c_int
-    lib.c_run_segmentation.argtypes = [_f32p, ctypes.c_int, _f32p, ctypes.c_int, ctypes.c_int,
-                                       ctypes.c_int, ctypes.c_int, _i32p, _i32p, _i32p,
-                                       ctypes.c_float, ctypes.c_float, ctypes.c_float]
-    lib.c_run_segmentation.restype = None
-    lib.mn_prepare_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                      ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                      ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-    lib.mn_prepare_device.restype = ctypes.c_int
-    if hasattr(lib, "mn_segment_device_t"):              # (absent from older variant builds: MN_LIB)
-        # the typed forms: `int dtype` right after the group of the two map pointers
-        def typed(argtypes, at=5):
-            return list(argtypes[:at]) + [ctypes.c_int] + list(argtypes[at:])
-        lib.mn_segment_device_t.argtypes = typed(lib.mn_segment_device.argtypes)
-        lib.mn_segment_launch_t.argtypes = typed(lib.mn_segment_launch.argtypes)
-        lib.mn_segment_exact_batch_t.argtypes = typed(lib.mn_segment_exact_batch.argtypes, 6)
-        lib.mn_score_device_t.argtypes = typed(lib.mn_score_device.argtypes)
-        lib.mn_exact_phase_a_device_t.argtypes = typed(lib.mn_exact_phase_a_device.argtypes)
-        lib.mn_sweep_device_t.argtypes = typed(lib.mn_sweep_device.argtypes)
-        lib.mn_sweep_time_device_t.argtypes = typed(lib.mn_sweep_time_device.argtypes, 3)
-        lib.mn_prepare_device_t.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                            ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-        for name in ("mn_segment_device_t", "mn_segment_launch_t", "mn_segment_exact_batch_t", "mn_score_device_t",
-                     "mn_exact_phase_a_device_t", "mn_sweep_device_t", "mn_sweep_time_device_t",
-                     "mn_prepare_device_t"):
-            getattr(lib, name).restype = ctypes.c_int
-    lib.mn_upsample_mask_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                            ctypes.c_void_p]
-    lib.mn_upsample_mask_device.restype = ctypes.c_int
-    lib.mn_rle_points_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                         ctypes.c_void_p, ctypes.c_int, _i32p, ctypes.c_void_p]
-    lib.mn_rle_points_device.restype = ctypes.c_int
-    lib.mn_rle_encode_host.argtypes = [_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                       ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong,
-                                       ctypes.POINTER(ctypes.c_longlong), _i32p]
-    lib.mn_rle_encode_host.restype = ctypes.c_longlong
-    if hasattr(lib, "mn_rle_counts_host"):               # (absent from older variant builds: MN_LIB)
-        lib.mn_rle_counts_host.argtypes = [ctypes.c_char_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong,
-                                           ctypes.POINTER(ctypes.c_longlong)]
-        lib.mn_rle_counts_host.restype = ctypes.c_longlong
-        lib.mn_rle_decode_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                             ctypes.c_void_p]
-        lib.mn_rle_decode_device.restype = ctypes.c_int
-    lib.mn_sameness_targets_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                               ctypes.c_int, _i32p, ctypes.c_int, ctypes.c_void_p,
-                                               ctypes.c_void_p]
-    lib.mn_sameness_targets_device.restype = ctypes.c_int
-    lib.mn_instance_scores_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.mn_instance_scores_device.restype = ctypes.c_int
-    if hasattr(lib, "mn_instance_table_device"):         # (absent from older variant builds: MN_LIB)
-        lib.mn_instance_table_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                                 ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-        lib.mn_instance_table_device.restype = ctypes.c_int
-    if hasattr(lib, "mn_filter_instances_device"):
-        lib.mn_filter_instances_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                                   ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_void_p]
-        lib.mn_filter_instances_device.restype = ctypes.c_int
-    if hasattr(lib, "mn_overlap_table_device"):          # (absent from older variant builds: MN_LIB)
-        lib.mn_overlap_table_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                                ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                                                ctypes.c_void_p]
-        lib.mn_overlap_table_device.restype = ctypes.c_int
-    if hasattr(lib, "mn_match_overlaps_device"):
-        lib.mn_match_overlaps_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_double,
-                                                  ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        lib.mn_match_overlaps_device.restype = ctypes.c_int
-    if hasattr(lib, "mn_eval_append_device"):            # (absent from older variant builds: MN_LIB)
-        _f64p = ctypes.POINTER(ctypes.c_double)
-        lib.mn_eval_append_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                              _f64p, ctypes.c_int, _f64p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                              ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        lib.mn_eval_append_device.restype = ctypes.c_int
-        lib.mn_eval_keys_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
-                                            ctypes.c_void_p, ctypes.c_void_p]
-        lib.mn_eval_keys_device.restype = ctypes.c_int
-        lib.mn_eval_accumulate_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
-                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                                  ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _i32p,
-                                                  ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_void_p]
-        lib.mn_eval_accumulate_device.restype = ctypes.c_int
-    if hasattr(lib, "mn_map_scores_device"):             # (absent from older variant builds: MN_LIB)
-        lib.mn_map_scores_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                             _i32p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                             ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-        lib.mn_map_scores_device.restype = ctypes.c_int
-    if hasattr(lib, "mn_mask_bce_device"):               # (absent from older variant builds: MN_LIB)
-        lib.mn_mask_bce_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p,
-                                           ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                           ctypes.c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_void_p,
-                                           ctypes.c_int, ctypes.c_void_p]
-        lib.mn_mask_bce_device.restype = ctypes.c_int
-    if hasattr(lib, "mn_plane_sums_device"):             # (absent from older variant builds: MN_LIB)
-        lib.mn_plane_sums_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_void_p,
-                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                                             ctypes.c_int, ctypes.c_void_p]
-        lib.mn_plane_sums_device.restype = ctypes.c_int
-        lib.mn_plane_coeffs_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                                               ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-        lib.mn_plane_coeffs_device.restype = ctypes.c_int
-        lib.mn_plane_grad_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_void_p,
-                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        lib.mn_plane_grad_device.restype = ctypes.c_int
-    if hasattr(lib, "mn_tile_class_maps_device"):        # (absent from older variant builds: MN_LIB)
-        lib.mn_tile_class_maps_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int,
-                                                  _i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                  ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-        lib.mn_tile_class_maps_device.restype = ctypes.c_int
-    lib.mn_pack_wire_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
-                                        ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-    lib.mn_pack_wire_device.restype = ctypes.c_int
-    lib.mn_runs_wire_words.argtypes = [ctypes.c_int, ctypes.c_int]
-    lib.mn_runs_wire_words.restype = ctypes.c_size_t
-    lib.mn_pack_runs_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                        ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                        ctypes.c_void_p, ctypes.c_void_p]
-    lib.mn_pack_runs_device.restype = ctypes.c_int
-    lib.mn_unpack_runs_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.mn_unpack_runs_device.restype = ctypes.c_int
-    lib.mn_last_status.restype = ctypes.c_int
-    lib.mn_status_string.argtypes = [ctypes.c_int]
-    lib.mn_status_string.restype = ctypes.c_char_p
-    lib.mn_version.restype = ctypes.c_char_p
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name, None)      # a variant build (MN_LIB) may lack a symbol: _typed / _entry say so at the call
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
     _lib_handle = lib
     return lib
 
@@ -320,6 +66,50 @@ class MergeNetError(RuntimeError):
         lib = load_library()
         super().__init__("mergenet_hip status %d: %s" % (status, lib.mn_status_string(status).decode()))
         self.status = status
+
+
+def _ok(rc: int) -> None:
+    if rc != 0:
+        raise MergeNetError(rc)
+
+
+def _stream(dev) -> ctypes.c_void_p:
+    """The current torch stream of `dev`, as the entry points take it."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _dev_tensor(t, what: str, dtype=None, shape=None, dim=None, at_least=None, numel=None, device=None,
+                contiguous=True):
+    """`t`, if it is a tensor on the GPU that meets every condition given: `dtype` (one, or a tuple of accepted
+    ones), `shape`, `dim`, `at_least` (a minimum numel), `numel` (an exact one), `device` (a torch.device, or a
+    device index) and, unless `contiguous` is False, contiguity.  ValueError(what) otherwise."""
+    if not (t.is_cuda and (not contiguous or t.is_contiguous())
+            and (dtype is None or (t.dtype in dtype if isinstance(dtype, tuple) else t.dtype == dtype))
+            and (dim is None or t.dim() == dim)
+            and (shape is None or tuple(t.shape) == tuple(shape))
+            and (at_least is None or t.numel() >= at_least)
+            and (numel is None or t.numel() == numel)
+            and (device is None or (t.device.index if isinstance(device, int) else t.device) == device)):
+        raise ValueError(what)
+    return t
+
+
+def _check_match_inputs(table, pred_classes, truth_classes, scores, crowd, device=None):
+    """What Merger.match_instances and DatasetEval.add take (the latter on its own `device`); returns (K, G)."""
+    import torch
+    _dev_tensor(table, "table: the contiguous int32 [K+1, G+1] tensor of overlap_table()%s"
+                % (", on the evaluator's GPU" if device is not None else ""), torch.int32, dim=2, at_least=1, device=device)
+    K, G = int(table.shape[0]) - 1, int(table.shape[1]) - 1
+    if pred_classes is None or truth_classes is None:
+        raise ValueError("pred_classes and truth_classes are needed")
+    for x, name, dtype, n in ((pred_classes, "pred_classes", torch.int32, K),
+                              (truth_classes, "truth_classes", torch.int32, G), (scores, "scores", torch.float32, K),
+                              (crowd, "crowd", (torch.uint8, torch.bool), G)):
+        if x is not None:
+            _dev_tensor(x, "%s: a contiguous %s tensor of at least %d entries on the table's GPU" % (name, dtype, n),
+                        dtype, at_least=n, device=table.device)
+    return K, G
 
 
 def default_options(**overrides) -> MnOptions:
@@ -382,9 +172,7 @@ def run_segmentation(class_pred, adj_pred, num_classes: int, offset_list,
                            mask_pred.ctypes.data_as(_i32p), object_class_pred.ctypes.data_as(_i32p),
                            float(same_different_bias), float(object_merge_factor),
                            float(merge_logprob_bias))
-    status = lib.mn_last_status()
-    if status != 0:
-        raise MergeNetError(status)      # the reference would exit(1) or crash
+    _ok(lib.mn_last_status())            # the reference would exit(1) or crash
     return mask_pred, _class_list(object_class_pred[0])
 
 
@@ -432,8 +220,7 @@ class HostContext:
                                       table.ctypes.data_as(_i32p),
                                       part.ctypes.data_as(_i32p) if part is not None else None,
                                       ctypes.byref(opts), ctypes.byref(stats))
-        if rc != 0:
-            raise MergeNetError(rc)
+        _ok(rc)
         return mask, _class_list(table), part, stats.as_dict()
 
 
@@ -530,6 +317,8 @@ class Merger:
     """
 
     DTYPE_NAMES = "float32, float16 or bfloat16"
+    MAPS_WANTED = "expected contiguous %s [K,H,W] tensors on the Merger's GPU" % DTYPE_NAMES
+    MASK_WANTED = "expected a contiguous int32 [H,W] tensor on the GPU"
 
     def __init__(self, H: int, W: int, C: int, O: int, device: Optional[int] = None):
         import torch
@@ -542,6 +331,7 @@ class Merger:
         if not self.handle:
             raise MergeNetError(self.lib.mn_last_status())
         self.H, self.W, self.C, self.O = H, W, C, O
+        self._dtype_codes = {torch.float32: MN_DTYPE_F32, torch.float16: MN_DTYPE_F16, torch.bfloat16: MN_DTYPE_BF16}
 
     def close(self):
         if getattr(self, "handle", None):
@@ -559,10 +349,15 @@ class Merger:
 
     def _dtype(self, t) -> int:
         """enum mn_dtype of a map tensor; ValueError for anything but the three accepted dtypes."""
-        torch = self.torch
-        code = {torch.float32: MN_DTYPE_F32, torch.float16: MN_DTYPE_F16, torch.bfloat16: MN_DTYPE_BF16}.get(t.dtype)
+        code = self._dtype_codes.get(t.dtype)
         if code is None:
             raise ValueError("expected %s tensors, got %s" % (self.DTYPE_NAMES, t.dtype))
+        return code
+
+    def _out_dtype(self, out_dtype) -> int:
+        code = self._dtype_codes.get(out_dtype)
+        if code is None:
+            raise ValueError("out_dtype: %s, got %s" % (self.DTYPE_NAMES, out_dtype))
         return code
 
     def _typed(self, name: str, dtype: int, logits: bool = False):
@@ -578,14 +373,11 @@ class Merger:
 
     def _check(self, class_probs, same_probs, offsets):
         for t in (class_probs, same_probs):
-            if not (t.is_cuda and t.is_contiguous() and t.dim() == 3):
-                raise ValueError("expected contiguous %s [K,H,W] tensors on the GPU" % self.DTYPE_NAMES)
+            _dev_tensor(t, self.MAPS_WANTED, dim=3, device=self.device)
             self._dtype(t)
             if t.dtype != class_probs.dtype:
                 raise ValueError("class and sameness maps must share one dtype (%s), got %s and %s"
                                  % (self.DTYPE_NAMES, class_probs.dtype, same_probs.dtype))
-            if t.device.index != self.device:
-                raise ValueError("tensor lives on another device than the Merger")
         C, H, W = class_probs.shape
         O = same_probs.shape[0]
         if same_probs.shape[1:] != (H, W) or len(offsets) != O:
@@ -604,14 +396,13 @@ class Merger:
         table = torch.empty((H * W,), dtype=torch.int32, device=dev)
         part = torch.empty((H, W), dtype=torch.int32, device=dev) if want_partition else None
         stats = MnStats()
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _stream(dev)
         fn, dt = self._typed("mn_segment_device", self._dtype(class_probs), logits)
         rc = fn(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(), O, *dt, W, H, C,
                 off.ctypes.data_as(_i32p), mask.data_ptr(), table.data_ptr(),
                 part.data_ptr() if part is not None else None,
-                ctypes.byref(opts), ctypes.c_void_p(stream), ctypes.byref(stats))
-        if rc != 0:
-            raise MergeNetError(rc)
+                ctypes.byref(opts), stream, ctypes.byref(stats))
+        _ok(rc)
         return mask, table, part, stats.as_dict()
 
     def segment_async(self, class_probs, same_probs, offsets, opts: Optional[MnOptions] = None,
@@ -631,22 +422,20 @@ class Merger:
         opts = opts if opts is not None else default_options()
         dev = class_probs.device
         if out is not None:
-            mask, table = out[0], out[1]
-            if not (mask.is_cuda and mask.dtype == torch.int32 and mask.is_contiguous() and mask.numel() == H * W
-                    and table.is_cuda and table.dtype == torch.int32 and table.numel() >= H * W):
-                raise ValueError("out=(mask int32 [H,W], table int32 [H*W]) on the GPU")
+            what = "out=(mask int32 [H,W], table int32 [H*W]) on the GPU"
+            mask = _dev_tensor(out[0], what, torch.int32, numel=H * W)
+            table = _dev_tensor(out[1], what, torch.int32, at_least=H * W, contiguous=False)
         else:
             mask = torch.empty((H, W), dtype=torch.int32, device=dev)
             table = torch.empty((H * W,), dtype=torch.int32, device=dev)
         part = torch.empty((H, W), dtype=torch.int32, device=dev) if want_partition else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _stream(dev)
         fn, dt = self._typed("mn_segment_launch", self._dtype(class_probs), logits)
         rc = fn(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(), O, *dt, W, H, C,
                 off.ctypes.data_as(_i32p), mask.data_ptr(), table.data_ptr(),
                 part.data_ptr() if part is not None else None,
-                ctypes.byref(opts), ctypes.c_void_p(stream))
-        if rc != 0:
-            raise MergeNetError(rc)
+                ctypes.byref(opts), stream)
+        _ok(rc)
         return PendingSegment(self, mask, table, part, (class_probs, same_probs, opts))
 
     def score(self, class_probs, same_probs, offsets, opts: Optional[MnOptions] = None,
@@ -659,16 +448,14 @@ class Merger:
         cls = torch.empty((H, W), dtype=torch.uint8, device=dev) if want_arrays else None
         best = torch.empty((H, W), dtype=torch.int64, device=dev) if want_arrays else None
         a, b = ctypes.c_float(0), ctypes.c_float(0)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _stream(dev)
         fn, dt = self._typed("mn_score_device", self._dtype(class_probs), logits)
         rc = fn(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(),
-                O, *dt, W, H, C, off.ctypes.data_as(_i32p), ctypes.byref(opts),
-                ctypes.c_void_p(stream),
+                O, *dt, W, H, C, off.ctypes.data_as(_i32p), ctypes.byref(opts), stream,
                 cls.data_ptr() if cls is not None else None,
                 best.data_ptr() if best is not None else None,
                 ctypes.byref(a), ctypes.byref(b))
-        if rc != 0:
-            raise MergeNetError(rc)
+        _ok(rc)
         if want_arrays:
             return a.value, b.value, cls, best
         return a.value, b.value
@@ -688,14 +475,13 @@ class Merger:
         gsum = torch.zeros((C, (H * W + 3) // 4), dtype=torch.int32, device=dev)
         logsum = ctypes.c_double(0.0)
         info = (ctypes.c_int * 3)()
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _stream(dev)
         fn, dt = self._typed("mn_sweep_device", self._dtype(class_probs), logits)
         rc = fn(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(), O, *dt, W, H, C,
-                off.ctypes.data_as(_i32p), ctypes.byref(opts), ctypes.c_void_p(stream),
+                off.ctypes.data_as(_i32p), ctypes.byref(opts), stream,
                 bits.data_ptr(), neg.data_ptr(), cls.data_ptr(), gsum.data_ptr(),
                 ctypes.byref(logsum), info)
-        if rc != 0:
-            raise MergeNetError(rc)
+        _ok(rc)
         fused = bool(info[1])
         return dict(bits=bits, neg=neg, cls=cls if fused else None, gsum=gsum if fused else None,
                     logsum=logsum.value, pixels_per_lane=int(info[0]), fused_class=fused, margin_edges=int(info[2]))
@@ -712,14 +498,13 @@ class Merger:
         n = len(inputs)
         vp = ctypes.c_void_p * n
         out = ctypes.c_float(0)
-        stream = self.torch.cuda.current_stream(inputs[0][0].device).cuda_stream
+        stream = _stream(inputs[0][0].device)
         fn, dt = self._typed("mn_sweep_time_device", self._dtype(inputs[0][0]), logits)
         rc = fn(self.handle, vp(*[a.data_ptr() for a, _ in inputs]),
                 vp(*[b.data_ptr() for _, b in inputs]), *dt, n, C, O, W, H, C,
-                off.ctypes.data_as(_i32p), ctypes.byref(opts), ctypes.c_void_p(stream),
+                off.ctypes.data_as(_i32p), ctypes.byref(opts), stream,
                 int(reps), ctypes.byref(out))
-        if rc != 0:
-            raise MergeNetError(rc)
+        _ok(rc)
         return out.value
 
     def exact_phase_a(self, class_probs, same_probs, offsets, opts: Optional[MnOptions] = None,
@@ -733,14 +518,13 @@ class Merger:
         cls = torch.empty((H, W), dtype=torch.uint8, device=dev)
         oml = torch.empty((O, H, W), dtype=torch.float32, device=dev)
         prio = torch.empty((O, H, W), dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _stream(dev)
         fn, dt = self._typed("mn_exact_phase_a_device", self._dtype(class_probs), logits)
         rc = fn(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(),
                 O, *dt, W, H, C, off.ctypes.data_as(_i32p), ctypes.byref(opts),
-                ctypes.c_void_p(stream), cls.data_ptr(), oml.data_ptr(),
+                stream, cls.data_ptr(), oml.data_ptr(),
                 prio.data_ptr())
-        if rc != 0:
-            raise MergeNetError(rc)
+        _ok(rc)
         return cls, oml, prio
 
     def prepare(self, maps, out_height: int, out_width: int, apply_sigmoid: bool = False,
@@ -751,42 +535,33 @@ class Merger:
         in float32, or in ``out_dtype`` (torch.float16 / torch.bfloat16): the float32 value the kernel computed,
         rounded to nearest even."""
         torch = self.torch
-        if not (maps.is_cuda and maps.is_contiguous() and maps.dim() == 3):
-            raise ValueError("expected a contiguous %s [K,H,W] tensor on the GPU" % self.DTYPE_NAMES)
+        _dev_tensor(maps, self.MAPS_WANTED, dim=3)
         in_code = self._dtype(maps)
         out_dtype = torch.float32 if out_dtype is None else out_dtype
-        out_code = {torch.float32: MN_DTYPE_F32, torch.float16: MN_DTYPE_F16, torch.bfloat16: MN_DTYPE_BF16}.get(out_dtype)
-        if out_code is None:
-            raise ValueError("out_dtype: %s, got %s" % (self.DTYPE_NAMES, out_dtype))
+        out_code = self._out_dtype(out_dtype)
         K, Hin, Win = maps.shape
         out = torch.empty((K, out_height, out_width), dtype=out_dtype, device=maps.device)
-        stream = torch.cuda.current_stream(maps.device).cuda_stream
+        stream = _stream(maps.device)
         if in_code == MN_DTYPE_F32 and out_code == MN_DTYPE_F32 and not hasattr(self.lib, "mn_prepare_device_t"):
             rc = self.lib.mn_prepare_device(self.handle, maps.data_ptr(), K, Hin, Win, out.data_ptr(),
                                             out_height, out_width, int(apply_sigmoid), int(clip),
-                                            ctypes.c_void_p(stream))      # (a variant build without the typed forms)
+                                            stream)      # (a variant build without the typed forms)
         else:
             rc = self.lib.mn_prepare_device_t(self.handle, maps.data_ptr(), in_code, K, Hin, Win, out.data_ptr(),
-                                              out_code, out_height, out_width, int(apply_sigmoid), int(clip),
-                                              ctypes.c_void_p(stream))
-        if rc != 0:
-            raise MergeNetError(rc)
+                                              out_code, out_height, out_width, int(apply_sigmoid), int(clip), stream)
+        _ok(rc)
         return out
 
     def upsample_mask(self, mask, out_height: int, out_width: int):
         """Instance mask back to the image size, cv2 INTER_NEAREST coordinates (segment.py:146-149)."""
         torch = self.torch
-        if not (mask.is_cuda and mask.dtype == torch.int32 and mask.is_contiguous() and mask.dim() == 2):
-            raise ValueError("expected a contiguous int32 [H,W] tensor on the GPU")
+        H, W = self._check_mask(mask)
         out = torch.empty((out_height, out_width), dtype=torch.int32, device=mask.device)
-        stream = torch.cuda.current_stream(mask.device).cuda_stream
-        rc = self.lib.mn_upsample_mask_device(self.handle, mask.data_ptr(), mask.shape[0],
-                                              mask.shape[1], out.data_ptr(), out_height, out_width,
-                                              ctypes.c_void_p(stream))
-        if rc != 0:
-            raise MergeNetError(rc)
+        stream = _stream(mask.device)
+        rc = self.lib.mn_upsample_mask_device(self.handle, mask.data_ptr(), H, W, out.data_ptr(), out_height, out_width,
+                                              stream)
+        _ok(rc)
         return out
-
 
     def encode_rle(self, mask, num_instances: int, drop_zero_area: bool = False):
         """COCO run-length encoding of every instance of an int32 [H,W] mask on this GPU.
@@ -800,9 +575,7 @@ class Merger:
         ``egs/cityscape/local/evaluate.py:52-54`` does before COCOeval.
         """
         torch = self.torch
-        if not (mask.is_cuda and mask.dtype == torch.int32 and mask.is_contiguous() and mask.dim() == 2):
-            raise ValueError("expected a contiguous int32 [H,W] tensor on the GPU")
-        H, W = mask.shape
+        H, W = self._check_mask(mask)
         cap = getattr(self, "_rle_cap", max(1024, H * W // 16))
         while True:
             if getattr(self, "_rle_pts", None) is None or self._rle_pts.shape[1] != cap:
@@ -810,14 +583,13 @@ class Merger:
                 self._rle_host = torch.empty((3, cap), dtype=torch.int32).pin_memory()
                 self._rle_cap = cap
             n = ctypes.c_int(0)
-            stream = torch.cuda.current_stream(mask.device).cuda_stream
+            stream = _stream(mask.device)
             rc = self.lib.mn_rle_points_device(self.handle, mask.data_ptr(), H, W, self._rle_pts.data_ptr(),
-                                               cap, ctypes.byref(n), ctypes.c_void_p(stream))
+                                               cap, ctypes.byref(n), stream)
             if rc == -4 and n.value > cap:
                 cap = n.value
                 continue
-            if rc != 0:
-                raise MergeNetError(rc)
+            _ok(rc)
             break
         nn = n.value
         for r in range(3):                                    # only the used part of each row travels
@@ -902,7 +674,7 @@ class Merger:
             starts[i + 1] = at
         dev = torch.device("cuda", self.device)
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
+            stream = _stream(dev)
             d_counts = torch.from_numpy(counts[:max(1, at)].view(np.int32)).to(dev, non_blocking=True)
             d_starts = torch.from_numpy(starts).to(dev, non_blocking=True)
             d_values = torch.from_numpy(vals).to(dev, non_blocking=True) if vals is not None and A else None
@@ -915,25 +687,21 @@ class Merger:
             rc = fn(self.handle, d_counts.data_ptr(), d_starts.data_ptr(), A, at,
                     d_values.data_ptr() if d_values is not None else None, H, W, self._rld_ends.data_ptr(),
                     self._rld_rec.data_ptr(), mask.data_ptr(), area.data_ptr() if area is not None and A else None,
-                    ctypes.c_void_p(stream))
-        if rc != 0:
-            raise MergeNetError(rc)
+                    stream)
+        _ok(rc)
         return (mask, area) if return_area else mask
 
     def sameness_targets(self, mask, offsets):
         """Instance mask int32 [H,W] -> float32 [O,H,W] sameness targets (utils/dataset.py:259-277)."""
         torch = self.torch
-        if not (mask.is_cuda and mask.dtype == torch.int32 and mask.is_contiguous() and mask.dim() == 2):
-            raise ValueError("expected a contiguous int32 [H,W] tensor on the GPU")
+        H, W = self._check_mask(mask)
         off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int32).reshape(-1, 2))
-        H, W = mask.shape
         out = torch.empty((off.shape[0], H, W), dtype=torch.float32, device=mask.device)
-        stream = torch.cuda.current_stream(mask.device).cuda_stream
+        stream = _stream(mask.device)
         rc = self.lib.mn_sameness_targets_device(self.handle, mask.data_ptr(), H, W,
                                                  off.ctypes.data_as(_i32p), off.shape[0],
-                                                 out.data_ptr(), ctypes.c_void_p(stream))
-        if rc != 0:
-            raise MergeNetError(rc)
+                                                 out.data_ptr(), stream)
+        _ok(rc)
         return out
 
     def instance_scores(self, num_instances: int, device=None):
@@ -941,16 +709,13 @@ class Merger:
         torch = self.torch
         dev = torch.device("cuda", self.device) if device is None else device
         out = torch.zeros((max(1, num_instances),), dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.mn_instance_scores_device(self.handle, out.data_ptr(), ctypes.c_void_p(stream))
-        if rc != 0:
-            raise MergeNetError(rc)
+        stream = _stream(dev)
+        rc = self.lib.mn_instance_scores_device(self.handle, out.data_ptr(), stream)
+        _ok(rc)
         return out[:num_instances]
 
     def _check_mask(self, mask):
-        torch = self.torch
-        if not (mask.is_cuda and mask.dtype == torch.int32 and mask.is_contiguous() and mask.dim() == 2):
-            raise ValueError("expected a contiguous int32 [H,W] tensor on the GPU")
+        _dev_tensor(mask, self.MASK_WANTED, self.torch.int32, dim=2)
         return int(mask.shape[0]), int(mask.shape[1])
 
     def _entry(self, name: str):
@@ -970,10 +735,9 @@ class Merger:
         if K < 0:
             raise ValueError("num_instances must not be negative")
         table = torch.empty((K, 5), dtype=torch.int32, device=mask.device)
-        stream = torch.cuda.current_stream(mask.device).cuda_stream
-        rc = fn(self.handle, mask.data_ptr(), H, W, K, table.data_ptr(), ctypes.c_void_p(stream))
-        if rc != 0:
-            raise MergeNetError(rc)
+        stream = _stream(mask.device)
+        rc = fn(self.handle, mask.data_ptr(), H, W, K, table.data_ptr(), stream)
+        _ok(rc)
         return table
 
     def filter_instances(self, mask, class_table, num_instances: int, min_area: int = 1, scores=None,
@@ -995,32 +759,29 @@ class Merger:
         if K < 0:
             raise ValueError("num_instances must not be negative")
         dev = mask.device
-        if not (class_table.is_cuda and class_table.dtype == torch.int32 and class_table.is_contiguous()
-                and class_table.numel() >= K and class_table.device == dev):
-            raise ValueError("class_table: a contiguous int32 tensor of at least num_instances entries on the mask's GPU")
-        if scores is not None and not (scores.is_cuda and scores.dtype == torch.float32 and scores.is_contiguous()
-                                       and scores.numel() >= K and scores.device == dev):
-            raise ValueError("scores: a contiguous float32 tensor of at least num_instances entries on the mask's GPU")
+        what = "%s: a contiguous %s tensor of at least num_instances entries on the mask's GPU"
+        _dev_tensor(class_table, what % ("class_table", "int32"), torch.int32, at_least=K, device=dev)
+        if scores is not None:
+            _dev_tensor(scores, what % ("scores", "float32"), torch.float32, at_least=K, device=dev)
         if table is None:
             table = self.instance_table(mask, K)
-        elif not (table.is_cuda and table.dtype == torch.int32 and table.is_contiguous() and table.device == dev
-                  and tuple(table.shape) == (K, 5)):
-            raise ValueError("table: the contiguous int32 [num_instances,5] tensor of instance_table()")
+        else:
+            _dev_tensor(table, "table: the contiguous int32 [num_instances,5] tensor of instance_table()",
+                        torch.int32, shape=(K, 5), device=dev)
         out_mask = mask if inplace else torch.empty_like(mask)
         remap = torch.empty((K + 1,), dtype=torch.int32, device=dev)
         table_out = torch.empty((K, 5), dtype=torch.int32, device=dev)
         classes_out = torch.empty((K,), dtype=torch.int32, device=dev)
         scores_out = torch.empty((K,), dtype=torch.float32, device=dev) if scores is not None else None
         count = torch.empty((1,), dtype=torch.int32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _stream(dev)
         threshold = float("-inf") if min_score is None else float(min_score)
         rc = fn(
             self.handle, mask.data_ptr(), H, W, K, table.data_ptr(), class_table.data_ptr(),
             scores.data_ptr() if scores is not None else None, int(min_area), threshold, out_mask.data_ptr(),
             remap.data_ptr(), table_out.data_ptr(), classes_out.data_ptr(),
-            scores_out.data_ptr() if scores_out is not None else None, count.data_ptr(), ctypes.c_void_p(stream))
-        if rc != 0:
-            raise MergeNetError(rc)
+            scores_out.data_ptr() if scores_out is not None else None, count.data_ptr(), stream)
+        _ok(rc)
         new_k = int(count.item())                             # the one synchronisation
         res = (out_mask, classes_out, scores_out[:new_k] if scores_out is not None else None, table_out[:new_k], new_k)
         return res + (remap,) if return_remap else res
@@ -1055,18 +816,17 @@ class Merger:
         torch = self.torch
         fn = self._entry("mn_overlap_table_device")
         H, W = self._check_mask(pred)
-        if self._check_mask(truth) != (H, W) or truth.device != pred.device:
-            raise ValueError("truth: a mask of the prediction's shape on the prediction's GPU")
+        _dev_tensor(truth, "truth: a contiguous int32 mask of the prediction's shape on the prediction's GPU",
+                    torch.int32, shape=(H, W), device=pred.device)
         K, G = int(num_pred), int(num_truth)
         if K < 0 or G < 0:
             raise ValueError("num_pred and num_truth must not be negative")
         if (K + 1) * (G + 1) > 2 ** 28:
             raise ValueError("(num_pred + 1) * (num_truth + 1) must not exceed 2^28")
         table = torch.empty((K + 1, G + 1), dtype=torch.int32, device=pred.device)
-        stream = torch.cuda.current_stream(pred.device).cuda_stream
-        rc = fn(self.handle, pred.data_ptr(), truth.data_ptr(), H, W, K, G, table.data_ptr(), ctypes.c_void_p(stream))
-        if rc != 0:
-            raise MergeNetError(rc)
+        stream = _stream(pred.device)
+        rc = fn(self.handle, pred.data_ptr(), truth.data_ptr(), H, W, K, G, table.data_ptr(), stream)
+        _ok(rc)
         return table
 
     def match_instances(self, table, pred_classes, truth_classes, scores=None, crowd=None, thresholds=None,
@@ -1083,26 +843,8 @@ class Merger:
         ``labels.match_instances`` is the numpy statement and gives the definitions.  Nothing is synchronised."""
         torch = self.torch
         fn = self._entry("mn_match_overlaps_device")
-        if not (table.is_cuda and table.dtype == torch.int32 and table.is_contiguous() and table.dim() == 2
-                and table.shape[0] >= 1 and table.shape[1] >= 1):
-            raise ValueError("table: the contiguous int32 [K+1, G+1] tensor of overlap_table()")
+        K, G = _check_match_inputs(table, pred_classes, truth_classes, scores, crowd)
         dev = table.device
-        K, G = int(table.shape[0]) - 1, int(table.shape[1]) - 1
-
-        def checked(x, name, dtypes, n):
-            if x is None:
-                return None
-            if not (x.is_cuda and x.dtype in dtypes and x.is_contiguous() and x.numel() >= n and x.device == dev):
-                raise ValueError("%s: a contiguous %s tensor of at least %d entries on the table's GPU"
-                                 % (name, " / ".join(str(d) for d in dtypes), n))
-            return x
-
-        checked(pred_classes, "pred_classes", (torch.int32,), K)
-        checked(truth_classes, "truth_classes", (torch.int32,), G)
-        if pred_classes is None or truth_classes is None:
-            raise ValueError("pred_classes and truth_classes are needed")
-        checked(scores, "scores", (torch.float32,), K)
-        checked(crowd, "crowd", (torch.uint8, torch.bool), G)
         th = np.ascontiguousarray(np.linspace(0.5, 0.95, 10) if thresholds is None else
                                   np.asarray(thresholds, np.float64).reshape(-1))
         T = int(th.size)
@@ -1113,15 +855,13 @@ class Merger:
         pred_ignore = torch.empty((T, K), dtype=torch.uint8, device=dev)
         truth_ignore = torch.empty((G,), dtype=torch.uint8, device=dev)
         iou = torch.empty((K, G), dtype=torch.float64, device=dev) if return_iou else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _stream(dev)
         rc = fn(self.handle, table.data_ptr(), K, G, pred_classes.data_ptr(),
                 scores.data_ptr() if scores is not None else None, truth_classes.data_ptr(),
                 crowd.data_ptr() if crowd is not None else None, th.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), T,
                 float(area_range[0]), float(area_range[1]), iou.data_ptr() if iou is not None else None,
-                pred_match.data_ptr(), truth_match.data_ptr(), pred_ignore.data_ptr(), truth_ignore.data_ptr(),
-                ctypes.c_void_p(stream))
-        if rc != 0:
-            raise MergeNetError(rc)
+                pred_match.data_ptr(), truth_match.data_ptr(), pred_ignore.data_ptr(), truth_ignore.data_ptr(), stream)
+        _ok(rc)
         res = {"pred_match": pred_match, "truth_match": truth_match, "pred_ignore": pred_ignore.view(torch.bool),
                "truth_ignore": truth_ignore.view(torch.bool)}
         if return_iou:
@@ -1142,13 +882,12 @@ class Merger:
         """The ground truth of :meth:`map_scores` and :meth:`mask_bce`: the label mask and the classes of its labels.
         Returns G, the number of truth labels."""
         torch = self.torch
-        if self._check_mask(truth) != (H, W) or truth.device != dev:
-            raise ValueError("truth: a mask of the maps' height and width on the maps' GPU")
+        _dev_tensor(truth, "truth: a contiguous int32 mask of the maps' height and width on the maps' GPU",
+                    torch.int32, shape=(H, W), device=dev)
         if truth_classes is None:
             return 0
-        if not (truth_classes.is_cuda and truth_classes.dtype == torch.int32 and truth_classes.is_contiguous()
-                and truth_classes.dim() == 1 and truth_classes.device == dev):
-            raise ValueError("truth_classes: a contiguous int32 [G] tensor on the maps' GPU, or None")
+        _dev_tensor(truth_classes, "truth_classes: a contiguous int32 [G] tensor on the maps' GPU, or None",
+                    torch.int32, dim=1, device=dev)
         return int(truth_classes.numel())
 
     def map_scores(self, class_probs, same_probs, offsets, truth, truth_classes, logits: bool = False, into=None):
@@ -1178,17 +917,15 @@ class Merger:
             sums = torch.empty((3, O), dtype=torch.float64, device=dev)
         else:
             confusion, sums = into["confusion"], into["sums"]
-            for t, dt, shape in ((confusion, torch.int64, (C, C)), (sums, torch.float64, (3, O))):
-                if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
-                    raise ValueError("into: a previous result of map_scores for %d classes and %d offsets on the maps' GPU"
-                                     % (C, O))
-        stream = torch.cuda.current_stream(dev).cuda_stream
+            what = "into: a previous result of map_scores for %d classes and %d offsets on the maps' GPU" % (C, O)
+            _dev_tensor(confusion, what, torch.int64, shape=(C, C), device=dev)
+            _dev_tensor(sums, what, torch.float64, shape=(3, O), device=dev)
+        stream = _stream(dev)
         rc = fn(self.handle, class_probs.data_ptr(), C, same_probs.data_ptr(), O,
                 self._dtype(class_probs) | (MN_MAPS_LOGITS if logits else 0), W, H, C, off.ctypes.data_as(_i32p),
                 truth.data_ptr(), G, truth_classes.data_ptr() if G else None, confusion.data_ptr(), sums.data_ptr(),
-                1 if into is not None else 0, ctypes.c_void_p(stream))
-        if rc != 0:
-            raise MergeNetError(rc)
+                1 if into is not None else 0, stream)
+        _ok(rc)
         return {"confusion": confusion, "sums": sums}
 
     def mask_bce(self, class_logits, same_logits, offsets, truth, truth_classes, scale_class: float = 1.0,
@@ -1220,12 +957,9 @@ class Merger:
         for t in maps:
             if t is None:
                 continue
-            if not (t.is_cuda and t.is_contiguous() and t.dim() == 3):
-                raise ValueError("expected contiguous %s [K,H,W] tensors on the GPU" % self.DTYPE_NAMES)
+            _dev_tensor(t, self.MAPS_WANTED, dim=3, device=self.device)
             if t.dtype != first.dtype:
                 raise ValueError("class and offset logits must share one dtype (%s)" % self.DTYPE_NAMES)
-            if t.device.index != self.device:
-                raise ValueError("tensor lives on another device than the Merger")
             if t.shape[1:] != first.shape[1:]:
                 raise ValueError("class and offset logits differ in height or width")
         code = self._dtype(first)
@@ -1241,30 +975,28 @@ class Merger:
             sums = torch.empty((2 + O,), dtype=torch.float64, device=dev)
         else:
             sums = into["sums"] if isinstance(into, dict) else into
-            if not (sums.is_cuda and sums.dtype == torch.float64 and sums.is_contiguous()
-                    and tuple(sums.shape) == (2 + O,) and sums.device == dev):
-                raise ValueError("into: a previous result of mask_bce for %d offsets on the maps' GPU" % O)
+            _dev_tensor(sums, "into: a previous result of mask_bce for %d offsets on the maps' GPU" % O,
+                        torch.float64, shape=(2 + O,), device=dev)
         grads = [None, None]
         if out is not None:
             if not grad or len(out) != 2:
                 raise ValueError("out: (grad_class, grad_same), with grad=True")
+            what = "out: contiguous buffers of the maps' shapes and dtype on the maps' GPU"
             for i, (g, t) in enumerate(zip(out, maps)):
                 if t is None:
                     continue
-                if g is None or not (g.is_cuda and g.is_contiguous() and g.dtype == t.dtype and g.shape == t.shape
-                                     and g.device == dev):
-                    raise ValueError("out: contiguous buffers of the maps' shapes and dtype on the maps' GPU")
-                grads[i] = g
+                if g is None:
+                    raise ValueError(what)
+                grads[i] = _dev_tensor(g, what, t.dtype, shape=t.shape, device=dev)
         elif grad:
             grads = [None if t is None else torch.empty_like(t) for t in maps]
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _stream(dev)
         rc = fn(self.handle, maps[0].data_ptr() if C else None, maps[1].data_ptr() if O else None, code, W, H, C, O,
                 off.ctypes.data_as(_i32p) if O else None, truth.data_ptr(), G,
                 truth_classes.data_ptr() if G else None, grads[0].data_ptr() if grads[0] is not None else None,
                 grads[1].data_ptr() if grads[1] is not None else None, float(scale_class), float(scale_same),
-                sums.data_ptr(), 1 if into is not None else 0, ctypes.c_void_p(stream))
-        if rc != 0:
-            raise MergeNetError(rc)
+                sums.data_ptr(), 1 if into is not None else 0, stream)
+        _ok(rc)
         return {"sums": sums, "grad_class": grads[0], "grad_same": grads[1]}
 
     def _check_planes(self, logits, part, offsets, truth, truth_classes):
@@ -1275,10 +1007,7 @@ class Merger:
         if part not in code_of:
             raise ValueError("part: 'class' or 'offset'")
         part = code_of[part]
-        if not (logits.is_cuda and logits.is_contiguous() and logits.dim() == 3):
-            raise ValueError("expected a contiguous %s [P,H,W] tensor on the GPU" % self.DTYPE_NAMES)
-        if logits.device.index != self.device:
-            raise ValueError("tensor lives on another device than the Merger")
+        _dev_tensor(logits, self.MAPS_WANTED, dim=3, device=self.device)
         code = self._dtype(logits)
         P, H, W = (int(v) for v in logits.shape)
         off = None
@@ -1312,16 +1041,15 @@ class Merger:
         sums = into if into is not None else out
         if sums is None:
             sums = torch.empty((5 * P + 1,), dtype=torch.float64, device=logits.device)
-        elif not (sums.is_cuda and sums.dtype == torch.float64 and sums.is_contiguous()
-                  and tuple(sums.shape) == (5 * P + 1,) and sums.device == logits.device):
-            raise ValueError("into / out: a contiguous float64 [%d] tensor on the maps' GPU" % (5 * P + 1))
+        else:
+            _dev_tensor(sums, "into / out: a contiguous float64 [%d] tensor on the maps' GPU" % (5 * P + 1),
+                        torch.float64, shape=(5 * P + 1,), device=logits.device)
         flags = (MN_PLANE_COMPLEMENT if complement else 0) | (MN_PLANE_TERMS if terms else 0)
-        stream = torch.cuda.current_stream(logits.device).cuda_stream
+        stream = _stream(logits.device)
         rc = fn(self.handle, logits.data_ptr(), code, W, H, part, P, off.ctypes.data_as(_i32p) if off is not None else None,
                 truth.data_ptr(), G, truth_classes.data_ptr() if G else None, flags, sums.data_ptr(),
-                1 if into is not None else 0, ctypes.c_void_p(stream))
-        if rc != 0:
-            raise MergeNetError(rc)
+                1 if into is not None else 0, stream)
+        _ok(rc)
         return sums
 
     def plane_coeffs(self, criterion, sums, pixels: float = 0.0, smooth: float = 1.0, scale: float = 1.0,
@@ -1338,26 +1066,24 @@ class Merger:
         crit = {"dice": MN_CRIT_DICE, "mbce": MN_CRIT_MBCE, MN_CRIT_DICE: MN_CRIT_DICE, MN_CRIT_MBCE: MN_CRIT_MBCE}.get(criterion)
         if crit is None:
             raise ValueError("criterion: 'dice' or 'mbce'")
-        if not (sums.is_cuda and sums.dtype == torch.float64 and sums.is_contiguous() and sums.dim() == 1
-                and sums.numel() % 5 == 1 and sums.numel() > 1 and sums.device.index == self.device):
-            raise ValueError("sums: a result of plane_sums on the Merger's GPU")
+        what = "sums: a result of plane_sums on the Merger's GPU"
+        if _dev_tensor(sums, what, torch.float64, dim=1, at_least=6, device=self.device).numel() % 5 != 1:
+            raise ValueError(what)
         P = sums.numel() // 5
         dev = sums.device
         coeffs = torch.empty((4, P), dtype=torch.float32, device=dev) if out is None else out
-        if not (coeffs.is_cuda and coeffs.dtype == torch.float32 and coeffs.is_contiguous()
-                and tuple(coeffs.shape) == (4, P) and coeffs.device == dev):
-            raise ValueError("out: a contiguous float32 [4,%d] tensor on the sums' GPU" % P)
+        _dev_tensor(coeffs, "out: a contiguous float32 [4,%d] tensor on the sums' GPU" % P, torch.float32, shape=(4, P),
+                    device=dev)
         loss = into["loss"] if isinstance(into, dict) else into
         if loss is None:
             loss = torch.empty((), dtype=torch.float64, device=dev)
-        elif not (loss.is_cuda and loss.dtype == torch.float64 and loss.numel() == 1 and loss.device == dev):
-            raise ValueError("into: a float64 scalar on the sums' GPU")
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        else:
+            _dev_tensor(loss, "into: a float64 scalar on the sums' GPU", torch.float64, numel=1, device=dev,
+                        contiguous=False)
+        stream = _stream(dev)
         rc = fn(self.handle, crit, MN_PLANE_COMPLEMENT if complement else 0, sums.data_ptr(), P, float(pixels),
-                float(smooth), float(scale), coeffs.data_ptr(), loss.data_ptr(), 1 if into is not None else 0,
-                ctypes.c_void_p(stream))
-        if rc != 0:
-            raise MergeNetError(rc)
+                float(smooth), float(scale), coeffs.data_ptr(), loss.data_ptr(), 1 if into is not None else 0, stream)
+        _ok(rc)
         return {"coeffs": coeffs, "loss": loss}
 
     def plane_grad(self, logits, part, offsets, truth, truth_classes, coeffs, factor=None, complement: bool = False,
@@ -1373,23 +1099,19 @@ class Merger:
         fn = self._entry("mn_plane_grad_device")
         part, code, P, H, W, off, G = self._check_planes(logits, part, offsets, truth, truth_classes)
         dev = logits.device
-        if not (coeffs.is_cuda and coeffs.dtype == torch.float32 and coeffs.is_contiguous()
-                and tuple(coeffs.shape) == (4, P) and coeffs.device == dev):
-            raise ValueError("coeffs: a contiguous float32 [4,%d] tensor on the maps' GPU" % P)
-        if factor is not None and not (factor.is_cuda and factor.dtype == torch.float32 and factor.numel() == 1
-                                       and factor.device == dev):
-            raise ValueError("factor: a float32 scalar tensor on the maps' GPU, or None")
+        _dev_tensor(coeffs, "coeffs: a contiguous float32 [4,%d] tensor on the maps' GPU" % P, torch.float32, shape=(4, P),
+                    device=dev)
+        if factor is not None:
+            _dev_tensor(factor, "factor: a float32 scalar tensor on the maps' GPU, or None", torch.float32, numel=1,
+                        device=dev, contiguous=False)
         grad = torch.empty_like(logits) if out is None else out
-        if not (grad.is_cuda and grad.is_contiguous() and grad.dtype == logits.dtype and grad.shape == logits.shape
-                and grad.device == dev):
-            raise ValueError("out: a contiguous buffer of the maps' shape and dtype on the maps' GPU")
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        _dev_tensor(grad, "out: a contiguous buffer of the maps' shape and dtype on the maps' GPU", logits.dtype,
+                    shape=logits.shape, device=dev)
+        stream = _stream(dev)
         rc = fn(self.handle, logits.data_ptr(), code, W, H, part, P, off.ctypes.data_as(_i32p) if off is not None else None,
                 truth.data_ptr(), G, truth_classes.data_ptr() if G else None, MN_PLANE_COMPLEMENT if complement else 0,
-                coeffs.data_ptr(), factor.data_ptr() if factor is not None else None, grad.data_ptr(),
-                ctypes.c_void_p(stream))
-        if rc != 0:
-            raise MergeNetError(rc)
+                coeffs.data_ptr(), factor.data_ptr() if factor is not None else None, grad.data_ptr(), stream)
+        _ok(rc)
         return grad
 
     def tile_class_maps(self, tiles, flip_tiles, row_starts, col_starts, height: int, width: int, num_classes: int,
@@ -1409,19 +1131,14 @@ class Merger:
         image or a pixel that no tile covers raises MergeNetError before anything is launched."""
         torch = self.torch
         fn = self._entry("mn_tile_class_maps_device")
-        if not (tiles.is_cuda and tiles.is_contiguous() and tiles.dim() == 4):
-            raise ValueError("tiles: a contiguous %s [T,Cn,th,tw] tensor on the GPU" % self.DTYPE_NAMES)
-        if tiles.device.index != self.device:
-            raise ValueError("tiles live on %s, this Merger on GPU %d" % (tiles.device, self.device))
+        _dev_tensor(tiles, "tiles: a contiguous %s [T,Cn,th,tw] tensor on the Merger's GPU" % self.DTYPE_NAMES, dim=4,
+                    device=self.device)
         code = self._dtype(tiles)
-        if flip_tiles is not None and not (flip_tiles.is_cuda and flip_tiles.is_contiguous() and
-                                           flip_tiles.shape == tiles.shape and flip_tiles.dtype == tiles.dtype and
-                                           flip_tiles.device == tiles.device):
-            raise ValueError("flip_tiles: a contiguous tensor of the shape, dtype and device of tiles, or None")
+        if flip_tiles is not None:
+            _dev_tensor(flip_tiles, "flip_tiles: a contiguous tensor of the shape, dtype and device of tiles, or None",
+                        tiles.dtype, shape=tiles.shape, device=tiles.device)
         out_dtype = tiles.dtype if out_dtype is None else out_dtype
-        out_code = {torch.float32: MN_DTYPE_F32, torch.float16: MN_DTYPE_F16, torch.bfloat16: MN_DTYPE_BF16}.get(out_dtype)
-        if out_code is None:
-            raise ValueError("out_dtype: %s, got %s" % (self.DTYPE_NAMES, out_dtype))
+        out_code = self._out_dtype(out_dtype)
         rows = np.ascontiguousarray(np.asarray(list(row_starts), dtype=np.int32).reshape(-1))
         cols = np.ascontiguousarray(np.asarray(list(col_starts), dtype=np.int32).reshape(-1))
         T, Cn, th, tw = (int(v) for v in tiles.shape)
@@ -1431,12 +1148,11 @@ class Merger:
         if H <= 0 or W <= 0 or C <= 0:
             raise MergeNetError(-1)
         out = torch.empty((C, H, W), dtype=out_dtype, device=tiles.device)
-        stream = torch.cuda.current_stream(tiles.device).cuda_stream
+        stream = _stream(tiles.device)
         rc = fn(self.handle, tiles.data_ptr(), flip_tiles.data_ptr() if flip_tiles is not None else None, code,
                 Cn, th, tw, rows.ctypes.data_as(_i32p), len(rows), cols.ctypes.data_as(_i32p), len(cols),
-                H, W, C, out.data_ptr(), out_code, int(bool(clip)), ctypes.c_void_p(stream))
-        if rc != 0:
-            raise MergeNetError(rc)
+                H, W, C, out.data_ptr(), out_code, int(bool(clip)), stream)
+        _ok(rc)
         return out
 
 
@@ -1501,28 +1217,9 @@ class DatasetEval:
         """One image: the arguments of :meth:`Merger.match_instances`.  Enqueues on the current stream; nothing is
         synchronised.  K, G <= 4096."""
         torch = self.torch
-        if not (table.is_cuda and table.dtype == torch.int32 and table.is_contiguous() and table.dim() == 2
-                and table.shape[0] >= 1 and table.shape[1] >= 1 and table.device == self.device):
-            raise ValueError("table: the contiguous int32 [K+1, G+1] tensor of overlap_table(), on the evaluator's GPU")
-        K, G = int(table.shape[0]) - 1, int(table.shape[1]) - 1
+        K, G = _check_match_inputs(table, pred_classes, truth_classes, scores, crowd, device=self.device)
         if K > MN_MATCH_MAX_INSTANCES or G > MN_MATCH_MAX_INSTANCES:
             raise ValueError("at most %d prediction and truth instances per image" % MN_MATCH_MAX_INSTANCES)
-
-        def checked(x, name, dtypes, n):
-            if x is None:
-                return None
-            if not (x.is_cuda and x.dtype in dtypes and x.is_contiguous() and x.numel() >= n
-                    and x.device == self.device):
-                raise ValueError("%s: a contiguous %s tensor of at least %d entries on the table's GPU"
-                                 % (name, " / ".join(str(d) for d in dtypes), n))
-            return x
-
-        if pred_classes is None or truth_classes is None:
-            raise ValueError("pred_classes and truth_classes are needed")
-        checked(pred_classes, "pred_classes", (torch.int32,), K)
-        checked(truth_classes, "truth_classes", (torch.int32,), G)
-        checked(scores, "scores", (torch.float32,), K)
-        checked(crowd, "crowd", (torch.uint8, torch.bool), G)
         if self.num_records + K > 2 ** 31 - 1:
             raise ValueError("the log holds at most 2^31 - 1 records")
         if self.num_records + K > self.capacity:                 # grow by doubling: a copy on the stream, no read-back
@@ -1531,16 +1228,14 @@ class DatasetEval:
             grown[:self.num_records].copy_(self._log[:self.num_records])
             self._log = grown
         _f64p = ctypes.POINTER(ctypes.c_double)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = _stream(self.device)
         rc = self._append(self.merger.handle, table.data_ptr(), K, G, pred_classes.data_ptr(),
                           scores.data_ptr() if scores is not None else None, truth_classes.data_ptr(),
                           crowd.data_ptr() if crowd is not None else None, self.thresholds.ctypes.data_as(_f64p),
                           len(self.thresholds), self.area_ranges.ctypes.data_as(_f64p), len(self.area_ranges),
                           self.max_dets[-1], self.num_classes, self.num_images,
-                          self._log.data_ptr() + self.num_records * MN_EVAL_RECORD_BYTES, self._npig.data_ptr(),
-                          ctypes.c_void_p(stream))
-        if rc != 0:
-            raise MergeNetError(rc)
+                          self._log.data_ptr() + self.num_records * MN_EVAL_RECORD_BYTES, self._npig.data_ptr(), stream)
+        _ok(rc)
         self.num_records += K
         self.num_images += 1
 
@@ -1552,13 +1247,12 @@ class DatasetEval:
         torch = self.torch
         T, R, C = len(self.thresholds), len(self.rec_thresholds), self.num_classes
         A, M, N = len(self.area_ranges), len(self.max_dets), self.num_records
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = _stream(self.device)
         keys = index = None
         if N:
             raw = torch.empty((N,), dtype=torch.int64, device=self.device)
             rc = self._keys(self.merger.handle, self._log.data_ptr(), N, C, raw.data_ptr(), stream)
-            if rc != 0:
-                raise MergeNetError(rc)
+            _ok(rc)
             keys, index = torch.sort(raw, stable=True)
         precision = torch.empty((T, R, C, A, M), dtype=torch.float64, device=self.device)
         recall = torch.empty((T, C, A, M), dtype=torch.float64, device=self.device)
@@ -1567,8 +1261,7 @@ class DatasetEval:
                               keys.data_ptr() if N else None, index.data_ptr() if N else None, self._npig.data_ptr(),
                               C, T, self._rec_dev.data_ptr() if R else None, R, A, self._max_dets_c, M,
                               precision.data_ptr(), recall.data_ptr(), scores.data_ptr(), stream)
-        if rc != 0:
-            raise MergeNetError(rc)
+        _ok(rc)
         return {"precision": precision, "recall": recall, "scores": scores, "npig": self._npig.clone()}
 
     def summarize(self, result=None, classes=None) -> dict:
@@ -1608,8 +1301,7 @@ class PendingSegment:
             stats = MnStats()
             rc = self._merger.lib.mn_segment_finish(self._merger.handle, ctypes.byref(stats))
             self._keepalive = None
-            if rc != 0:
-                raise MergeNetError(rc)
+            _ok(rc)
             self._done = self._out + (stats.as_dict(),)
         return self._done
 
@@ -1651,22 +1343,21 @@ class ExactBatch:
         parts = [torch.empty((H, W), dtype=torch.int32, device=dev) for _ in range(n)] if want_partition else None
         vp = ctypes.c_void_p * n
         stats = (MnStats * n)()
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _stream(dev)
         fn, dt = self.mergers[0]._typed("mn_segment_exact_batch", self.mergers[0]._dtype(class_probs[0]), logits)
         rc = fn(
             vp(*[m.handle for m in self.mergers[:n]]), n, vp(*[t.data_ptr() for t in class_probs]), C,
             vp(*[t.data_ptr() for t in same_probs]), O, *dt, W, H, C, off.ctypes.data_as(_i32p),
             vp(*[t.data_ptr() for t in masks]), vp(*[t.data_ptr() for t in tables]),
             vp(*[t.data_ptr() for t in parts]) if parts is not None else None,
-            ctypes.byref(opts), ctypes.c_void_p(stream), stats)
+            ctypes.byref(opts), stream, stats)
         results = [(masks[i], tables[i], parts[i] if parts is not None else None, stats[i].as_dict())
                    for i in range(n)]
         if rc == MN_ERR_UNPROVEN:
             err = MergeNetError(rc)
             err.results = results
             raise err
-        if rc != 0:
-            raise MergeNetError(rc)
+        _ok(rc)
         return results
 
     def close(self):
@@ -1778,12 +1469,10 @@ def pack_wire(mask, class_table, num_instances: int, wire, max_instances: int,
             or not mask.is_contiguous() or wire.numel() < n + 1 + max_instances + 4
             or class_table.numel() < num_instances):
         raise AssertionError("pack_wire: int32 mask/table, int16 wire of n + 1 + max_instances + 4")
-    stream = torch.cuda.current_stream(mask.device).cuda_stream
+    stream = _stream(mask.device)
     rc = lib.mn_pack_wire_device(mask.data_ptr(), class_table.data_ptr(), int(num_instances),
-                                 float(total_logprob), n, int(max_instances), wire.data_ptr(),
-                                 ctypes.c_void_p(stream))
-    if rc != 0:
-        raise MergeNetError(rc)
+                                 float(total_logprob), n, int(max_instances), wire.data_ptr(), stream)
+    _ok(rc)
 
 
 
@@ -1803,12 +1492,11 @@ def pack_runs(merger, mask, class_table, num_instances: int, wire, capacity: int
             or not mask.is_contiguous() or wire.numel() < runs_wire_words(capacity, max_instances)
             or class_table.numel() < num_instances):
         raise AssertionError("pack_runs: int32 mask/table, int32 wire of runs_wire_words(capacity, max_instances)")
-    stream = torch.cuda.current_stream(mask.device).cuda_stream
+    stream = _stream(mask.device)
     rc = merger.lib.mn_pack_runs_device(merger.handle, mask.data_ptr(), class_table.data_ptr(),
                                         int(num_instances), float(total_logprob), n, int(capacity),
-                                        int(max_instances), wire.data_ptr(), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise MergeNetError(rc)
+                                        int(max_instances), wire.data_ptr(), stream)
+    _ok(rc)
 
 
 def unpack_runs_batch(wires, height: int, width: int, capacity: int, max_instances: int):
@@ -1819,16 +1507,10 @@ def unpack_runs_batch(wires, height: int, width: int, capacity: int, max_instanc
     count = int(wires.shape[0])
     masks = torch.empty((count, height, width), dtype=torch.int32, device=wires.device)
     tables = torch.empty((count, max_instances), dtype=torch.int32, device=wires.device)
-    stream = torch.cuda.current_stream(wires.device).cuda_stream
-    lib.mn_unpack_runs_batch_device.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
-                                                ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_void_p]
-    lib.mn_unpack_runs_batch_device.restype = ctypes.c_int
+    stream = _stream(wires.device)
     rc = lib.mn_unpack_runs_batch_device(wires.data_ptr(), int(wires.stride(0)), count, height * width,
-                                         int(capacity), int(max_instances), masks.data_ptr(), tables.data_ptr(),
-                                         ctypes.c_void_p(stream))
-    if rc != 0:
-        raise MergeNetError(rc)
+                                         int(capacity), int(max_instances), masks.data_ptr(), tables.data_ptr(), stream)
+    _ok(rc)
     return masks, tables
 
 
@@ -1838,9 +1520,8 @@ def unpack_runs(wire, height: int, width: int, capacity: int, max_instances: int
     lib = load_library()
     mask = torch.empty((height, width), dtype=torch.int32, device=wire.device)
     table = torch.empty((max_instances,), dtype=torch.int32, device=wire.device)
-    stream = torch.cuda.current_stream(wire.device).cuda_stream
+    stream = _stream(wire.device)
     rc = lib.mn_unpack_runs_device(wire.data_ptr(), height * width, int(capacity), int(max_instances),
-                                   mask.data_ptr(), table.data_ptr(), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise MergeNetError(rc)
+                                   mask.data_ptr(), table.data_ptr(), stream)
+    _ok(rc)
     return mask, table
