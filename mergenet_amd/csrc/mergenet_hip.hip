@@ -30,16 +30,16 @@
 #include "mn_kernels_rle.h"
 #include "mn_kernels_tiles.h"
 #include "mn_sweep_form.h"
+#include "mn_memory.h"
 #include "mn_kernels_tail.h"
 #include "mn_kernels_exact.h"
 #include "mn_kernels_reforder.h"
 
-// Counters | 16 int scalars | 4 doubles, each part 16-byte aligned
+// The stat block (stat_layout): Counters | 16 int scalars | 4 doubles, each part 16-byte aligned
 // scalars: [0] edge violations [1] instances [2] objects [3] class violations [4] record violations
 //          [5] RLE change points [6] separability violations [7] table / list overflow
 //          [8] component roots [9] negative edges (unsigned)
 #define MN_NSCALARS 16
-#define MN_STAT_BYTES ((((sizeof(Counters) + 15) & ~(size_t)15)) + MN_NSCALARS * sizeof(int) + 4 * sizeof(double))
 
 #define MN_MAX_SUBROUNDS 64
 
@@ -88,10 +88,9 @@ struct mn_context {
   size_t N, Rmax, cap;    // cap: slots of the record table / entries of the record lists CURRENTLY allocated
   size_t cap_full;        // ... and what the general rounds need (allocated on their first use: ensure_general)
   int gen_ready;
-  size_t gen_bytes;
   size_t cc_cap;          // table capacity used by the last component contraction
   int debug_flags;        // mn_options.debug_flags of the call in progress
-  size_t bytes;
+  MnMemory mem;           // every buffer below, by group (mn_memory.h); mem.counted is mn_workspace_bytes
   // objects
   unsigned char *ocls, *cls0, *lpvalid, *matched, *pruned;
   int *osize, *parent, *mate, *root, *label, *mapbuf;
@@ -129,6 +128,7 @@ struct mn_context {
   // host block, so that the statistics of an image come back in a single copy
   unsigned char* statblk;
   unsigned char* h_statblk;
+  size_t stat_bytes;
   int *cc_tcount, *cc_lcount;   // pixel edges per record: parallel to the components-mode table / list
   unsigned* cc_bits;            // [N] positive out-edges of every pixel (mn_cc_sign)
   int* cc_roots;                // [N] component roots (mn_cc_finish)
@@ -171,13 +171,15 @@ struct mn_context {
   double* ms_partials;      // [MN_MS_VALUES][MN_MS_WORKGROUPS] partial sums of mn_map_scores_device: allocated on first use
   double* pl_partials;      // [MN_PL_VALUES][MN_MS_WORKGROUPS] partial sums of mn_plane_sums_device: allocated on first use
   // workspace of the exact engine (mn_kernels_exact.h): allocated on first use, for the largest
-  // image seen so far
+  // image seen so far (group MN_MEM_EXACT; x_free drops it and resets this struct)
   struct XWork {
     XState X;
     size_t n_pix, n_rec, n_cls_floats, hcap, arena_cap, leaf_cap;   // capacities of what is allocated
     void* block;                  // the ONE allocation all arrays live in
-    size_t bytes;
     XCtl* h_ctl;                  // pinned
+  } xw;
+  // ... and what outlives a regrow of it: the sizing rules, the batch arrays, the state of the run
+  struct XKeep {
     int lds_ready;
     int prerun;                   // set-up and loop of the image have run (as part of a batch)
     ImgParams* d_P;               // device copies of a batch's parameters (first context of the batch)
@@ -186,18 +188,20 @@ struct mn_context {
     int arena_extra;              // arena words per pixel beyond the initial arrays (doubled when a run fills it)
     int table_permille;           // pair table: load at the start, in thousandths (lowered when a run fills the table)
     int max_blocks;               // most queue blocks (0 = MN_X_MAXBLOCKS); smaller for the contexts of a large batch
-  } xw;
-  // the reference-order loop (mn_options.tie_order = MN_TIES_REFERENCE, mn_kernels_reforder.h)
+  } xk;
+  // the reference-order loop (mn_options.tie_order = MN_TIES_REFERENCE, mn_kernels_reforder.h): workspace
+  // (group MN_MEM_REFORDER; r_free drops it and resets this struct) and what outlives a regrow
   struct RWork {
     RoState S;
     void* block;                  // one allocation for all arrays
-    size_t bytes;
     int n_pix; long long n_rec; int n_cls; long long arena_cap, heap_cap;
-    int arena_per_pixel, heap_per_record;     // (doubled when a run fills them)
     long long* h_ctl;             // pinned
+  } rw;
+  struct RKeep {
+    int arena_per_pixel, heap_per_record;     // (doubled when a run fills them)
     RoState* d_S;                 // device copies of a batch's states (first context of the batch)
     int batch_cap;
-  } rw;
+  } rk;
   int tie_ref;                    // this attempt: MN_TIES_* as asked for
   int tie_used;                   // ... and what the last exact attempt ran in the end
   // staging for the host-pointer entry points
@@ -228,35 +232,29 @@ static size_t next_pow2(size_t x) {
   return p;
 }
 
+// ---- memory: every allocation is a registration with the context (mn_memory.h) --------------------------
+static int hip_failed(const char* what, size_t bytes, hipError_t e) {
+  if (e != hipSuccess) fprintf(stderr, "mergenet_hip: %s of %zu bytes failed: %s\n", what, bytes, hipGetErrorString(e));
+  return e != hipSuccess;
+}
+static int hip_dev_alloc(void** p, size_t b) { return hip_failed("hipMalloc", b, hipMalloc(p, b)); }
+static int hip_pin_alloc(void** p, size_t b) { return hip_failed("hipHostMalloc", b, hipHostMalloc(p, b)); }
+static void hip_dev_free(void* p) { (void)hipFree(p); }
+static void hip_pin_free(void* p) { (void)hipHostFree(p); }
+
+// How a step leaves on a status that is not MN_OK (an allocation: MN_ERR_NO_DEVICE).
+#define MN_TRY(expr) do { const int _rc = (expr); if (_rc != MN_OK) return done(_rc); } while (0)
+
+// n elements on the device, rounded up to 256 bytes and counted toward mn_workspace_bytes
 template <typename T>
-static hipError_t dev_alloc(mn_context* c, T** p, size_t n) {
-  const size_t b = (n * sizeof(T) + 255) & ~(size_t)255;
-  c->bytes += b;
-  return hipMalloc(reinterpret_cast<void**>(p), b);
-}
+static int dev_alloc(mn_context* c, int group, T** p, size_t n) { return c->mem.alloc(p, (n * sizeof(T) + 255) & ~(size_t)255, group, MN_MEM_DEVICE, true); }
+// ... one that an entry point allocates where it first needs it
+template <typename T>
+static int ensure_scratch(mn_context* c, T** p, size_t n) { return *p ? MN_OK : dev_alloc(c, MN_MEM_SCRATCH, p, n); }
 
-// ---- exact engine: workspace ------------------------------------------------------------------------
-static void x_free(mn_context* c) {
-  XState& X = c->xw.X;
-  if (c->xw.block) (void)hipFree(c->xw.block);     // (every array of the workspace lives in this ONE allocation)
-  if (X.mlog) (void)hipFree(X.mlog);
-  if (c->xw.h_ctl) (void)hipHostFree(c->xw.h_ctl);
-  c->bytes -= c->xw.bytes;
-  const mn_context::XWork keep = c->xw;
-  memset(&c->xw, 0, sizeof(c->xw));
-  c->xw.d_P = keep.d_P; c->xw.d_X = keep.d_X; c->xw.batch_cap = keep.batch_cap;
-  c->xw.arena_extra = keep.arena_extra; c->xw.table_permille = keep.table_permille; c->xw.max_blocks = keep.max_blocks;
-}
-
-static void r_free(mn_context* c) {
-  if (c->rw.block) (void)hipFree(c->rw.block);
-  if (c->rw.h_ctl) (void)hipHostFree(c->rw.h_ctl);
-  c->bytes -= c->rw.bytes;
-  const int ap = c->rw.arena_per_pixel, hp = c->rw.heap_per_record, bc = c->rw.batch_cap;
-  RoState* ds = c->rw.d_S;
-  memset(&c->rw, 0, sizeof(c->rw));
-  c->rw.arena_per_pixel = ap; c->rw.heap_per_record = hp; c->rw.d_S = ds; c->rw.batch_cap = bc;
-}
+// ---- exact engine and reference-order loop: workspaces (block, pinned mirror, merge log; the arrays are the block's) ----
+static void x_free(mn_context* c) { c->mem.free_group(MN_MEM_EXACT); c->xw = mn_context::XWork(); }
+static void r_free(mn_context* c) { c->mem.free_group(MN_MEM_REFORDER); c->rw = mn_context::RWork(); }
 
 // Sizes the workspace for an image of N pixels, O offsets, C classes.  Per pixel (C = 9, O = 10):
 // records 20 B x O, pair table 32-64 B x O (load <= 0.5 at the start, falling: pairs only disappear), class
@@ -265,27 +263,28 @@ static void r_free(mn_context* c) {
 // 1024 x 2048 (of 288 GB) -- the workspace bounds the images in flight (mn_segment_exact_batch).
 static int x_ensure(mn_context* c, int N, int O, int C) {
   mn_context::XWork& w = c->xw;
+  mn_context::XKeep& keep = c->xk;
   const size_t NL = (size_t)N * O;
   if (NL >= 0xFFFFFFF0ull) return MN_ERR_CAPACITY;
   size_t B = 256;
   // blocks of the queue: at most 16 K (128 KB of LDS: one image per compute unit); a context that is one of MORE
-  // images than the chip has compute units (xw.max_blocks, set by mn_segment_exact_batch) takes at most 6 K
+  // images than the chip has compute units (xk.max_blocks, set by mn_segment_exact_batch) takes at most 6 K
   // (72 KB with the rest of the loop's LDS: two images per compute unit, at the price of longer block scans)
-  const size_t max_blocks = w.max_blocks > 0 ? (size_t)w.max_blocks : (size_t)MN_X_MAXBLOCKS;
+  const size_t max_blocks = keep.max_blocks > 0 ? (size_t)keep.max_blocks : (size_t)MN_X_MAXBLOCKS;
   while ((NL + B - 1) / B > max_blocks) B <<= 1;
   const size_t NB = (NL + B - 1) / B;
   const size_t leaf_cap = NB * B + 1024;             // (a round of the block scan may read past a short block)
-  if (w.arena_extra <= 0) {
-    w.arena_extra = 8 * O + 8;                        // (measured use: 6.4 entries per pixel and offset at O = 10: doubling reallocation, exact-size free lists)
-    if (const char* e = getenv("MN_X_ARENA_EXTRA")) { const int v = atoi(e); if (v > 0) w.arena_extra = v; }   // (tests)
-    w.table_permille = 600;
-    if (const char* e = getenv("MN_X_TABLE_PERMILLE")) { const int v = atoi(e); if (v >= 50 && v <= 950) w.table_permille = v; }   // (tests)
+  if (keep.arena_extra <= 0) {
+    keep.arena_extra = 8 * O + 8;                        // (measured use: 6.4 entries per pixel and offset at O = 10: doubling reallocation, exact-size free lists)
+    if (const char* e = getenv("MN_X_ARENA_EXTRA")) { const int v = atoi(e); if (v > 0) keep.arena_extra = v; }   // (tests)
+    keep.table_permille = 600;
+    if (const char* e = getenv("MN_X_TABLE_PERMILLE")) { const int v = atoi(e); if (v >= 50 && v <= 950) keep.table_permille = v; }   // (tests)
   }
   // pair table: 4-slot buckets for a load of table_permille / 1000 (0.6) at the start (pairs only disappear: it falls)
-  const size_t nbuckets = (size_t)((double)NL * 1000.0 / (4.0 * (double)w.table_permille)) + 64;
+  const size_t nbuckets = (size_t)((double)NL * 1000.0 / (4.0 * (double)keep.table_permille)) + 64;
   if (nbuckets * 4 >= 0xFFFFFFF0ull) return MN_ERR_CAPACITY;
   // (single pixels keep no stored array: the arena only holds what merges allocate)
-  const size_t arena_cap = (size_t)N * (size_t)w.arena_extra + 65536;
+  const size_t arena_cap = (size_t)N * (size_t)keep.arena_extra + 65536;
   if (arena_cap >= 0xFFFFFFF0ull) return MN_ERR_CAPACITY;
   const size_t ovf_cap = NL / 256 + 4096;
   if (w.n_pix < (size_t)N || w.n_rec < NL || w.n_cls_floats < (size_t)N * C || w.hcap < nbuckets ||
@@ -293,30 +292,18 @@ static int x_ensure(mn_context* c, int N, int O, int C) {
     x_free(c);
     XState& X = w.X;
     // ONE allocation for the whole workspace, the arrays at 2 MB-aligned offsets (the loop walks them at random)
-    {
-      const size_t al = ((size_t)N * O > (1u << 20)) ? ((size_t)2 << 20) : 4096;
-      size_t off = 0;
-      auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + al - 1) / al * al; return o; };
-      const size_t o_hs = take(nbuckets * 4 * sizeof(XSlot)), o_rec = take(NL * sizeof(XRec)),
-                   o_arena = take(arena_cap * sizeof(unsigned)), o_leaf = take(leaf_cap * sizeof(unsigned)),
-                   o_lp = take(((size_t)N * C + 64) * sizeof(float)), o_obj = take((size_t)N * sizeof(XObj)),
-                   o_acap = take((size_t)N * sizeof(int)), o_ostamp = take((size_t)N * 2 * sizeof(unsigned)),
-                   o_ovf = take(ovf_cap * sizeof(unsigned)), o_l1g = take((size_t)MN_X_MAXBLOCKS * sizeof(u64)),
-                   o_tstack = take((size_t)MN_X_TSTACK * sizeof(u64)), o_free = take((size_t)MN_X_FREE_CLASSES * sizeof(unsigned)),
-                   o_ctl = take(sizeof(XCtl));
-      MN_HIP(hipMalloc(&w.block, off));
-      w.bytes = off;
-      c->bytes += off;
-      char* b = static_cast<char*>(w.block);
-      X.hs = reinterpret_cast<XSlot*>(b + o_hs); X.rec = reinterpret_cast<XRec*>(b + o_rec);
-      X.arena = reinterpret_cast<unsigned*>(b + o_arena); X.leaf = reinterpret_cast<unsigned*>(b + o_leaf);
-      X.lp = reinterpret_cast<float*>(b + o_lp); X.obj = reinterpret_cast<XObj*>(b + o_obj);
-      X.acap = reinterpret_cast<int*>(b + o_acap); X.ostamp = reinterpret_cast<unsigned*>(b + o_ostamp);
-      X.overflow = reinterpret_cast<unsigned*>(b + o_ovf); X.l1g = reinterpret_cast<u64*>(b + o_l1g);
-      X.tstack = reinterpret_cast<u64*>(b + o_tstack); X.ctl = reinterpret_cast<XCtl*>(b + o_ctl);
-      X.freeheads = reinterpret_cast<unsigned*>(b + o_free);
-    }
-    MN_HIP(hipHostMalloc(reinterpret_cast<void**>(&w.h_ctl), sizeof(XCtl)));
+    auto arrays = [&](void* block) {
+      MnCarver k(block, ((size_t)N * O > (1u << 20)) ? ((size_t)2 << 20) : 4096);
+      k.carve(X.hs, nbuckets * 4); k.carve(X.rec, NL); k.carve(X.arena, arena_cap); k.carve(X.leaf, leaf_cap);
+      k.carve(X.lp, (size_t)N * C + 64); k.carve(X.obj, (size_t)N); k.carve(X.acap, (size_t)N);
+      k.carve(X.ostamp, (size_t)N * 2); k.carve(X.overflow, ovf_cap); k.carve(X.l1g, (size_t)MN_X_MAXBLOCKS);
+      k.carve(X.tstack, (size_t)MN_X_TSTACK); k.carve(X.freeheads, (size_t)MN_X_FREE_CLASSES); k.carve(X.ctl, 1);
+      return k.off;
+    };
+    int rc = c->mem.alloc(&w.block, arrays(nullptr), MN_MEM_EXACT, MN_MEM_DEVICE, true);
+    if (rc == MN_OK) rc = c->mem.alloc(&w.h_ctl, sizeof(XCtl), MN_MEM_EXACT, MN_MEM_PINNED, false);
+    if (rc != MN_OK) { x_free(c); return done(rc); }
+    arrays(w.block);
     w.n_pix = N; w.n_rec = NL; w.n_cls_floats = (size_t)N * C; w.hcap = nbuckets; w.arena_cap = arena_cap;
     w.leaf_cap = leaf_cap;
     X.overflow_cap = (int)ovf_cap;
@@ -334,8 +321,7 @@ static int x_ensure(mn_context* c, int N, int O, int C) {
   X.dbg = getenv("MN_X_FORCE_RELOCATE") ? 1 : 0;                       // (tests)
   // diagnostic: MN_X_MERGELOG=<file> keeps the sequence of merges (survivor, absorbed, record, priority)
   if (getenv("MN_X_MERGELOG") && !X.mlog) {
-    if (hipMalloc(reinterpret_cast<void**>(&X.mlog), (size_t)N * 16) == hipSuccess) X.mlog_cap = N;
-    else X.mlog = nullptr;
+    if (c->mem.alloc(&X.mlog, (size_t)N * 16, MN_MEM_EXACT, MN_MEM_DEVICE, false) == MN_OK) X.mlog_cap = N;
   }
   return MN_OK;
 }
@@ -375,81 +361,75 @@ extern "C" const char* mn_version(void) { return "mergenet_hip 0.1 (gfx950)"; }
 
 // record lists A / B, the record table and the finisher's scratch list, `cap` entries each
 static int alloc_records(mn_context* c, size_t cap) {
-  const size_t before = c->bytes;
-  MN_HIP(dev_alloc(c, &c->LA.key, cap));
-  MN_HIP(dev_alloc(c, &c->LA.S, cap));
-  MN_HIP(dev_alloc(c, &c->LA.st, cap));
-  MN_HIP(dev_alloc(c, &c->LA.fr, cap));
-  MN_HIP(dev_alloc(c, &c->LA.aux, cap));
-  MN_HIP(dev_alloc(c, &c->LB.key, cap));
-  MN_HIP(dev_alloc(c, &c->LB.S, cap));
-  MN_HIP(dev_alloc(c, &c->LB.st, cap));
-  MN_HIP(dev_alloc(c, &c->LB.fr, cap));
-  MN_HIP(dev_alloc(c, &c->LB.aux, cap));
-  MN_HIP(dev_alloc(c, &c->touched_list, cap));
-  MN_HIP(dev_alloc(c, &c->T.key, cap));
-  MN_HIP(dev_alloc(c, &c->T.S, cap));
-  MN_HIP(dev_alloc(c, &c->T.st, cap));
-  MN_HIP(dev_alloc(c, &c->T.touched, cap));
-  c->gen_bytes = c->bytes - before;
+  for (RecList* L : {&c->LA, &c->LB}) {
+    MN_TRY(dev_alloc(c, MN_MEM_RECORDS, &L->key, cap));
+    MN_TRY(dev_alloc(c, MN_MEM_RECORDS, &L->S, cap));
+    MN_TRY(dev_alloc(c, MN_MEM_RECORDS, &L->st, cap));
+    MN_TRY(dev_alloc(c, MN_MEM_RECORDS, &L->fr, cap));
+    MN_TRY(dev_alloc(c, MN_MEM_RECORDS, &L->aux, cap));
+  }
+  MN_TRY(dev_alloc(c, MN_MEM_RECORDS, &c->touched_list, cap));
+  MN_TRY(dev_alloc(c, MN_MEM_RECORDS, &c->T.key, cap));
+  MN_TRY(dev_alloc(c, MN_MEM_RECORDS, &c->T.S, cap));
+  MN_TRY(dev_alloc(c, MN_MEM_RECORDS, &c->T.st, cap));
+  MN_TRY(dev_alloc(c, MN_MEM_RECORDS, &c->T.touched, cap));
   return MN_OK;
 }
 
-static void free_records(mn_context* c) {
-  void* dev[] = {c->LA.key, c->LA.S, c->LA.st, c->LA.fr, c->LA.aux, c->LB.key, c->LB.S, c->LB.st, c->LB.fr, c->LB.aux,
-                 c->touched_list, c->T.key, c->T.S, c->T.st, c->T.touched};
-  for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); i++)
-    if (dev[i]) (void)hipFree(dev[i]);
-  c->LA = RecList(); c->LB = RecList(); c->T = HashTab(); c->touched_list = nullptr;
-  c->bytes -= c->gen_bytes;
-  c->gen_bytes = 0;
+// The lists and the table at `cap` entries in place of what there was; c->cap says what is there (0 after a failure).
+static int set_records(mn_context* c, size_t cap) {
+  c->mem.free_group(MN_MEM_RECORDS);
+  c->cap = 0;
+  const int rc = alloc_records(c, cap);
+  if (rc != MN_OK) { c->mem.free_group(MN_MEM_RECORDS); return rc; }
+  c->cap = cap;
+  return MN_OK;
+}
+
+// Counters | MN_NSCALARS ints | 4 doubles of a stat block at `blk` (null: only its size, which is returned)
+static size_t stat_layout(void* blk, Counters*& cnt, int*& scalars, double*& lp) {
+  MnCarver k(blk, 16); k.carve(cnt, 1); k.carve(scalars, MN_NSCALARS); k.carve(lp, 4);
+  return k.off;
 }
 
 static int ctx_alloc(mn_context* c) {
   const size_t N = c->N;
-  MN_HIP(dev_alloc(c, &c->ocls, N));
-  MN_HIP(dev_alloc(c, &c->cls0, N));
-  MN_HIP(dev_alloc(c, &c->lpvalid, N));
-  MN_HIP(dev_alloc(c, &c->matched, N));
-  MN_HIP(dev_alloc(c, &c->pruned, N));
-  MN_HIP(dev_alloc(c, &c->osize, N));
-  MN_HIP(dev_alloc(c, &c->parent, N));
-  MN_HIP(dev_alloc(c, &c->mate, N));
-  MN_HIP(dev_alloc(c, &c->root, N));
-  MN_HIP(dev_alloc(c, &c->label, N));
-  MN_HIP(dev_alloc(c, &c->mapbuf, N));
-  MN_HIP(dev_alloc(c, &c->lpsum, N * (size_t)c->maxC));
-  MN_HIP(dev_alloc(c, &c->fin_lists, 3 * (size_t)MN_FIN2_MAXR));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->ocls, N));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->cls0, N));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->lpvalid, N));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->matched, N));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->pruned, N));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->osize, N));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->parent, N));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->mate, N));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->root, N));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->label, N));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->mapbuf, N));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->lpsum, N * (size_t)c->maxC));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->fin_lists, 3 * (size_t)MN_FIN2_MAXR));
   c->cc_cap_max = next_pow2(N / 8 + 8192);
   if (c->cc_cap_max > c->cap_full) c->cc_cap_max = c->cap_full;
-  MN_HIP(dev_alloc(c, &c->cc_tcount, c->cc_cap_max));
-  MN_HIP(dev_alloc(c, &c->cc_lcount, c->cc_cap_max));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->cc_tcount, c->cc_cap_max));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->cc_lcount, c->cc_cap_max));
   // record lists and record table: sized for what the speculative components attempt can use (records
   // BETWEEN components: at most cc_cap_max); the general rounds, which hold a record per pixel edge,
   // get theirs at first use (ensure_general) -- 0.3 instead of 2.1 GB per 1024x2048 context, and a ring
   // of eight of them is what a throughput loop keeps
-  c->cap = c->cc_cap_max;
-  if (alloc_records(c, c->cap) != MN_OK) return MN_ERR_NO_DEVICE;
-  MN_HIP(dev_alloc(c, &c->block_count, N / MN_SCAN_ITEMS + 2));
-  MN_HIP(dev_alloc(c, &c->wire_counts, N / MN_RLE_ITEMS + 4));
-  MN_HIP(dev_alloc(c, &c->partial, 3 * (N / 256 + 2) > 2 * (N / 64 + 8) ? 3 * (N / 256 + 2) : 2 * (N / 64 + 8)));   // (verify: 3 per block; sweep: 2 per wave)
-  {
-    const size_t o_sc = (sizeof(Counters) + 15) & ~(size_t)15, o_lp = o_sc + MN_NSCALARS * sizeof(int);
-    MN_HIP(dev_alloc(c, &c->statblk, MN_STAT_BYTES));
-    c->cnt = reinterpret_cast<Counters*>(c->statblk);
-    c->scalars = reinterpret_cast<int*>(c->statblk + o_sc);
-    c->lp_out = reinterpret_cast<double*>(c->statblk + o_lp);
-    MN_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_statblk), MN_STAT_BYTES));
-    c->h_cnt = reinterpret_cast<Counters*>(c->h_statblk);
-    c->h_scalars = reinterpret_cast<int*>(c->h_statblk + o_sc);
-    c->h_lp = reinterpret_cast<double*>(c->h_statblk + o_lp);
-  }
-  MN_HIP(dev_alloc(c, &c->gmax, 64));
-  MN_HIP(dev_alloc(c, &c->touch, 64));
-  MN_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_touch), (64 + MN_MAX_SUBROUNDS) * sizeof(unsigned)));
-  MN_HIP(dev_alloc(c, &c->theta, 4));
-  MN_HIP(dev_alloc(c, &c->progress, MN_MAX_SUBROUNDS));
-  MN_HIP(dev_alloc(c, &c->bg_key, 1));
+  MN_TRY(set_records(c, c->cc_cap_max));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->block_count, N / MN_SCAN_ITEMS + 2));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->wire_counts, N / MN_RLE_ITEMS + 4));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->partial, 3 * (N / 256 + 2) > 2 * (N / 64 + 8) ? 3 * (N / 256 + 2) : 2 * (N / 64 + 8)));   // (verify: 3 per block; sweep: 2 per wave)
+  c->stat_bytes = stat_layout(nullptr, c->cnt, c->scalars, c->lp_out);
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->statblk, c->stat_bytes));
+  stat_layout(c->statblk, c->cnt, c->scalars, c->lp_out);
+  MN_TRY(c->mem.alloc(&c->h_statblk, c->stat_bytes, MN_MEM_BASE, MN_MEM_PINNED, false));
+  stat_layout(c->h_statblk, c->h_cnt, c->h_scalars, c->h_lp);
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->gmax, 64));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->touch, 64));
+  MN_TRY(c->mem.alloc(&c->h_touch, (64 + MN_MAX_SUBROUNDS) * sizeof(unsigned), MN_MEM_BASE, MN_MEM_PINNED, false));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->theta, 4));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->progress, MN_MAX_SUBROUNDS));
+  MN_TRY(dev_alloc(c, MN_MEM_BASE, &c->bg_key, 1));
   for (int i = 0; i < 12; i++) MN_HIP(hipEventCreate(&c->ev[i]));
   MN_HIP(hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming));
   MN_HIP(hipEventCreate(&c->ev_fork));            // (timing enabled: it can be the stop event of a dispatch)
@@ -490,6 +470,7 @@ extern "C" mn_context* mn_create(int device, int max_height, int max_width, int 
   mn_context* c = static_cast<mn_context*>(calloc(1, sizeof(mn_context)));
   if (!c) { g_last_status = MN_ERR_INTERNAL; return NULL; }
   c->device = device;
+  c->mem = MnMemory{{hip_dev_alloc, hip_pin_alloc}, {hip_dev_free, hip_pin_free}};      // (by MnMemKind)
   c->maxH = max_height; c->maxW = max_width; c->maxC = max_classes; c->maxO = max_offsets;
   c->N = (size_t)max_height * max_width;
   c->Rmax = c->N * (size_t)max_offsets;
@@ -508,21 +489,7 @@ extern "C" void mn_destroy(mn_context* c) {
     g_host_n[0] = g_host_n[1] = 0; g_host_us[0] = g_host_us[1] = g_host_us[2] = 0.0;
   }
   (void)hipSetDevice(c->device);
-  void* dev[] = {c->ocls, c->cls0, c->lpvalid, c->matched, c->pruned, c->osize, c->parent, c->mate, c->root,
-                 c->label, c->mapbuf, c->lpsum, c->lp_acc, c->ball, c->bsub, c->fin_lists, c->cc_tcount, c->cc_lcount, c->cc_bits, c->cc_roots, c->cc_negbits,
-                 c->block_count, c->wire_counts, c->partial, c->statblk,
-                 c->bg_key, c->gmax, c->touch, c->theta, c->progress, c->d_class, c->d_same, c->d_mask, c->d_objcls, c->d_part,
-                 c->match_work, c->eval_work, c->ms_partials, c->pl_partials};
-  for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); i++)
-    if (dev[i]) (void)hipFree(dev[i]);
-  x_free(c);
-  r_free(c);
-  if (c->xw.d_P) (void)hipFree(c->xw.d_P);
-  if (c->xw.d_X) (void)hipFree(c->xw.d_X);
-  if (c->rw.d_S) (void)hipFree(c->rw.d_S);
-  free_records(c);
-  if (c->h_statblk) (void)hipHostFree(c->h_statblk);
-  if (c->h_touch) (void)hipHostFree(c->h_touch);
+  c->mem.free_all();
   for (int i = 0; i < 12; i++)
     if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
   if (c->ev_done) (void)hipEventDestroy(c->ev_done);
@@ -536,20 +503,21 @@ extern "C" void mn_destroy(mn_context* c) {
   free(c);
 }
 
-extern "C" size_t mn_workspace_bytes(const mn_context* c) { return c ? c->bytes : 0; }
+extern "C" size_t mn_workspace_bytes(const mn_context* c) { return c ? c->mem.counted : 0; }
 
 // What only the fast paths use (fixed-point class sums, best-record slots, edge masks: 100 B per pixel at C = 9) is
 // allocated at their first use: a context that only ever serves the exact engine -- the contexts of a batch
 // (mn_segment_exact_batch), where memory per image bounds the images in flight -- never pays for it.
 static int ensure_fast(mn_context* c) {
-  if (c->lp_acc) return MN_OK;
+  if (c->cc_negbits) return MN_OK;         // (the last one allocated: the group is whole)
+  c->mem.free_group(MN_MEM_FAST);          // (what an attempt that failed half-way left)
   const size_t N = c->N;
-  MN_HIP(dev_alloc(c, &c->lp_acc, N * (size_t)c->maxC));
-  MN_HIP(dev_alloc(c, &c->ball, N));
-  MN_HIP(dev_alloc(c, &c->bsub, N));
-  MN_HIP(dev_alloc(c, &c->cc_bits, N));
-  MN_HIP(dev_alloc(c, &c->cc_roots, N));
-  MN_HIP(dev_alloc(c, &c->cc_negbits, N + 16));
+  MN_TRY(dev_alloc(c, MN_MEM_FAST, &c->lp_acc, N * (size_t)c->maxC));
+  MN_TRY(dev_alloc(c, MN_MEM_FAST, &c->ball, N));
+  MN_TRY(dev_alloc(c, MN_MEM_FAST, &c->bsub, N));
+  MN_TRY(dev_alloc(c, MN_MEM_FAST, &c->cc_bits, N));
+  MN_TRY(dev_alloc(c, MN_MEM_FAST, &c->cc_roots, N));
+  MN_TRY(dev_alloc(c, MN_MEM_FAST, &c->cc_negbits, N + 16));
   return MN_OK;
 }
 
@@ -562,16 +530,18 @@ static void drop_replay_graphs(mn_context::Replay& rp) {
 }
 
 // The general rounds (and the small-list exact mode) hold a record per pixel edge: their lists and table
-// are allocated when first needed.  Recorded replay graphs hold the old pointers and are dropped.
+// are allocated when first needed.  Recorded replay graphs hold the old pointers and are dropped.  (The small lists
+// go first, to make room.  Should the large ones fail, the small ones come back; a context left without any, c->cap
+// = 0, takes no further image: check_args answers MN_ERR_CAPACITY to every size.)
 static int ensure_general(mn_context* c) {
   if (c->gen_ready) return MN_OK;
   MN_HIP(hipDeviceSynchronize());
-  free_records(c);
-  if (alloc_records(c, c->cap_full) != MN_OK) return MN_ERR_NO_DEVICE;
-  c->cap = c->cap_full;
-  c->gen_ready = 1;
   c->cc_clean = 0;
   drop_replay_graphs(c->replay);
+  const int rc = set_records(c, c->cap_full);
+  if (rc != MN_OK && set_records(c, c->cc_cap_max) != MN_OK) c->N = 0;
+  if (rc != MN_OK) return done(rc);
+  c->gen_ready = 1;
   return MN_OK;
 }
 
@@ -1159,13 +1129,14 @@ static int exact_setup(mn_context* c, const ImgParams& P, hipStream_t st) {
 // device copies of the images' parameters live in the first context given.  `full[i]` is set for an image that ran
 // out of arena or pair table (its workspace grows and exact_run repeats it; the others finish).
 static int exact_loop(mn_context** cs, int n, const ImgParams* Ps, hipStream_t st, unsigned char* full) {
-  mn_context::XWork& w0 = cs[0]->xw;
+  mn_context::XKeep& w0 = cs[0]->xk;
   if (w0.batch_cap < n) {
-    if (w0.d_P) (void)hipFree(w0.d_P);
-    if (w0.d_X) (void)hipFree(w0.d_X);
-    w0.d_P = nullptr; w0.d_X = nullptr;
-    MN_HIP(hipMalloc(reinterpret_cast<void**>(&w0.d_P), (size_t)n * sizeof(ImgParams)));
-    MN_HIP(hipMalloc(reinterpret_cast<void**>(&w0.d_X), (size_t)n * sizeof(XState)));
+    MnMemory& mem = cs[0]->mem;
+    mem.free_group(MN_MEM_EXACT_BATCH);
+    w0.batch_cap = 0;
+    int rc = mem.alloc(&w0.d_P, (size_t)n * sizeof(ImgParams), MN_MEM_EXACT_BATCH, MN_MEM_DEVICE, false);
+    if (rc == MN_OK) rc = mem.alloc(&w0.d_X, (size_t)n * sizeof(XState), MN_MEM_EXACT_BATCH, MN_MEM_DEVICE, false);
+    if (rc != MN_OK) { mem.free_group(MN_MEM_EXACT_BATCH); return done(rc); }
     w0.batch_cap = n;
   }
   size_t lds = 0;
@@ -1256,7 +1227,7 @@ static int exact_run(mn_context** cs, int n, const ImgParams* Ps, hipStream_t st
     int k = 0;
     for (int i = 0; i < m; i++) {
       if (!full[i]) continue;
-      mn_context::XWork& w = sub[i]->xw;
+      mn_context::XKeep& w = sub[i]->xk;
       if (full[i] == MN_X_ARENA_FULL) w.arena_extra *= 2;
       else if (w.table_permille > 100) w.table_permille = w.table_permille * 2 / 3;
       else { rc = MN_ERR_CAPACITY; break; }
@@ -1326,40 +1297,32 @@ static int exact_export(mn_context* c, const ImgParams& P, hipStream_t st) {
 // header, bucket arrays (13 + 29 + ... entries as the maps grow: 95-200 per pixel measured).
 static int r_ensure(mn_context* c, int N, int O, int C) {
   mn_context::RWork& w = c->rw;
-  if (w.arena_per_pixel <= 0) {
-    w.arena_per_pixel = 16 * O + 64; w.heap_per_record = 3;
-    if (const char* e = getenv("MN_RO_ARENA_PER_PIXEL")) { const int v = atoi(e); if (v > 0) w.arena_per_pixel = v; }   // (tests)
-    if (const char* e = getenv("MN_RO_HEAP_PER_RECORD")) { const int v = atoi(e); if (v > 0) w.heap_per_record = v; }
+  mn_context::RKeep& keep = c->rk;
+  if (keep.arena_per_pixel <= 0) {
+    keep.arena_per_pixel = 16 * O + 64; keep.heap_per_record = 3;
+    if (const char* e = getenv("MN_RO_ARENA_PER_PIXEL")) { const int v = atoi(e); if (v > 0) keep.arena_per_pixel = v; }   // (tests)
+    if (const char* e = getenv("MN_RO_HEAP_PER_RECORD")) { const int v = atoi(e); if (v > 0) keep.heap_per_record = v; }
   }
   const long long NL = (long long)N * O;
-  const long long arena_cap = (long long)N * w.arena_per_pixel + 65536;
-  const long long heap_cap = NL * w.heap_per_record + 65536;
+  const long long arena_cap = (long long)N * keep.arena_per_pixel + 65536;
+  const long long heap_cap = NL * keep.heap_per_record + 65536;
   if (NL > (1LL << 28)) return MN_ERR_CAPACITY;          // (node ids 2 * record + side are ints)
   if (!(w.block && w.n_pix >= N && w.n_rec >= NL && w.arena_cap >= arena_cap && w.heap_cap >= heap_cap)) {
     r_free(c);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_osize = take((size_t)N * 4), o_ocls = take((size_t)N * 4), o_bcount = take((size_t)N * 4),
-                 o_nelem = take((size_t)N * 4), o_head = take((size_t)N * 4), o_boff = take((size_t)N * 8),
-                 o_single = take((size_t)N * 4), o_barena = take((size_t)arena_cap * 4),
-                 o_nnext = take((size_t)NL * 2 * 4), o_nkey = take((size_t)NL * 2 * 8), o_r1 = take((size_t)NL * 4),
-                 o_r2 = take((size_t)NL * 4), o_oml = take((size_t)NL * 4), o_prio = take((size_t)NL * 4),
-                 o_heap = take((size_t)heap_cap * 8), o_ctl = take(128);
-    MN_HIP(hipMalloc(&w.block, off));
-    MN_HIP(hipHostMalloc(reinterpret_cast<void**>(&w.h_ctl), 128));
-    w.bytes = off;
-    c->bytes += off;
-    char* b = static_cast<char*>(w.block);
     RoState& S = w.S;
-    S.osize = reinterpret_cast<int*>(b + o_osize); S.ocls = reinterpret_cast<int*>(b + o_ocls);
-    S.bcount = reinterpret_cast<int*>(b + o_bcount); S.nelem = reinterpret_cast<int*>(b + o_nelem);
-    S.head = reinterpret_cast<int*>(b + o_head); S.boff = reinterpret_cast<long long*>(b + o_boff);
-    S.single = reinterpret_cast<int*>(b + o_single); S.barena = reinterpret_cast<int*>(b + o_barena);
-    S.nnext = reinterpret_cast<int*>(b + o_nnext); S.nkey = reinterpret_cast<unsigned long long*>(b + o_nkey);
-    S.r1 = reinterpret_cast<int*>(b + o_r1); S.r2 = reinterpret_cast<int*>(b + o_r2);
-    S.oml = reinterpret_cast<float*>(b + o_oml); S.prio = reinterpret_cast<float*>(b + o_prio);
-    S.heap = reinterpret_cast<unsigned long long*>(b + o_heap);
-    S.ctl = reinterpret_cast<long long*>(b + o_ctl);
+    auto arrays = [&](void* block) {
+      MnCarver k(block, 256);
+      k.carve(S.osize, (size_t)N); k.carve(S.ocls, (size_t)N); k.carve(S.bcount, (size_t)N); k.carve(S.nelem, (size_t)N);
+      k.carve(S.head, (size_t)N); k.carve(S.boff, (size_t)N); k.carve(S.single, (size_t)N);
+      k.carve(S.barena, (size_t)arena_cap); k.carve(S.nnext, (size_t)NL * 2); k.carve(S.nkey, (size_t)NL * 2);
+      k.carve(S.r1, (size_t)NL); k.carve(S.r2, (size_t)NL); k.carve(S.oml, (size_t)NL); k.carve(S.prio, (size_t)NL);
+      k.carve(S.heap, (size_t)heap_cap); k.carve(S.ctl, 16);
+      return k.off;
+    };
+    int rc = c->mem.alloc(&w.block, arrays(nullptr), MN_MEM_REFORDER, MN_MEM_DEVICE, true);
+    if (rc == MN_OK) rc = c->mem.alloc(&w.h_ctl, 128, MN_MEM_REFORDER, MN_MEM_PINNED, false);
+    if (rc != MN_OK) { r_free(c); return done(rc); }
+    arrays(w.block);
     w.n_pix = N; w.n_rec = NL; w.n_cls = C; w.arena_cap = arena_cap; w.heap_cap = heap_cap;
   }
   w.S.N = N; w.S.C = C; w.S.NL = NL;
@@ -1397,11 +1360,11 @@ static int ro_setup(mn_context* c, const ImgParams& P, hipStream_t st) {
 // device copies of the images' states live in the first context given.  full[i]: MN_RO_ARENA_FULL / MN_RO_HEAP_FULL
 // for an image whose workspace was too small (it grows and the caller repeats that image).
 static int ro_loop(mn_context** cs, int n, const ImgParams* Ps, hipStream_t st, unsigned char* full) {
-  mn_context::RWork& w0 = cs[0]->rw;
+  mn_context::RKeep& w0 = cs[0]->rk;
   if (w0.batch_cap < n) {
-    if (w0.d_S) (void)hipFree(w0.d_S);
-    w0.d_S = nullptr;
-    MN_HIP(hipMalloc(reinterpret_cast<void**>(&w0.d_S), (size_t)n * sizeof(RoState)));
+    cs[0]->mem.free_group(MN_MEM_REFORDER_BATCH);
+    w0.batch_cap = 0;
+    MN_TRY(cs[0]->mem.alloc(&w0.d_S, (size_t)n * sizeof(RoState), MN_MEM_REFORDER_BATCH, MN_MEM_DEVICE, false));
     w0.batch_cap = n;
   }
   HostBuf<RoState> hs((size_t)n);
@@ -1498,7 +1461,7 @@ static int run_reforder_batch(mn_context** cs, int n, const ImgParams* Ps, hipSt
     int k = 0;
     for (int i = 0; i < m; i++) {
       if (!full[i]) continue;
-      mn_context::RWork& w = sub[i]->rw;
+      mn_context::RKeep& w = sub[i]->rk;
       if (full[i] == MN_RO_ARENA_FULL) w.arena_per_pixel *= 2; else w.heap_per_record *= 2;
       sub[k] = sub[i]; subP[k] = subP[i]; k++;
     }
@@ -1530,19 +1493,19 @@ static int redo_in_reference_order(mn_context** cs, int n, const ImgParams* Ps, 
 }
 
 // set-up, loop and hand-over of ONE image; in a batch (mn_segment_exact_batch) set-up and loop have run for
-// all images together and only the hand-over is left (xw.prerun)
+// all images together and only the hand-over is left (xk.prerun)
 static int run_exact_engine(mn_context* c, const ImgParams& P, hipStream_t st) {
   int rc = MN_OK;
   mn_context* one[1] = {c};
   c->tie_used = MN_TIES_LOWEST_ID;
   const bool ref_possible = P.variant == MN_VARIANT_CSEGMENT;       // (the Python variant's heapq / dict order is not restated)
-  if (c->tie_ref == MN_TIES_REFERENCE && !c->xw.prerun) {
+  if (c->tie_ref == MN_TIES_REFERENCE && !c->xk.prerun) {
     if (!ref_possible) return MN_ERR_ARGUMENT;
     if ((rc = redo_in_reference_order(one, 1, &P, st, false)) != MN_OK) return rc;
     c->tie_used = MN_TIES_REFERENCE;
     MN_HIP(hipEventRecord(c->ev[1], st));
     MN_HIP(hipEventRecord(c->ev[2], st));
-  } else if (!c->xw.prerun) {
+  } else if (!c->xk.prerun) {
     if ((rc = exact_run(one, 1, &P, st)) != MN_OK) return rc;
     // MN_TIES_DEFAULT: tied pops are the only place where the engine's order and the reference's can part; a
     // small image that had some is redone the reference's way
@@ -1555,7 +1518,7 @@ static int run_exact_engine(mn_context* c, const ImgParams& P, hipStream_t st) {
     }
   } else {
     // (set-up and loop have run as part of a batch; prerun == 2: the reference-order loop too)
-    if (c->xw.prerun == 2) c->tie_used = MN_TIES_REFERENCE;
+    if (c->xk.prerun == 2) c->tie_used = MN_TIES_REFERENCE;
     MN_HIP(hipEventRecord(c->ev[1], st));
     MN_HIP(hipEventRecord(c->ev[2], st));
   }
@@ -1999,7 +1962,7 @@ static int launch_certificate(mn_context* c, const ImgParams& P, const Plan& pl,
 static int close_attempt(mn_context* c, const ImageCall& call, const Plan& pl, Attempt& A, mn_stats* stats, bool defer) {
   hipStream_t st = A.st;
   const Queued q = {A.mode, A.rounds, pl.finish_limit, call.W * call.H, pl.R0, pl.speculate, pl.want_cert};
-  MN_HIP(hipMemcpyAsync(c->h_statblk, c->statblk, MN_STAT_BYTES, hipMemcpyDeviceToHost, st));
+  MN_HIP(hipMemcpyAsync(c->h_statblk, c->statblk, c->stat_bytes, hipMemcpyDeviceToHost, st));
   if (pl.fused_tail) {             // (st is the side stream here)
     A.post.launch(st);
     c->cc_clean = 1;
@@ -2271,13 +2234,13 @@ extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, ctxs[0]->device) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
     (void)hipGetLastError();
-    for (int i = 0; i < count; i++) ctxs[i]->xw.max_blocks = count > ncu ? 6144 : 0;
+    for (int i = 0; i < count; i++) ctxs[i]->xk.max_blocks = count > ncu ? 6144 : 0;
   }
   const bool ref_possible = o.variant == MN_VARIANT_CSEGMENT;
   // (MN_TIES_REFERENCE: straight to the reference-order loop, as a single call goes)
   const bool ref_only = ref_possible && o.tie_order == MN_TIES_REFERENCE;
   if (!ref_only) rc = exact_run(ctxs, count, Ps, st);
-  for (int i = 0; i < count; i++) ctxs[i]->xw.max_blocks = 0;
+  for (int i = 0; i < count; i++) ctxs[i]->xk.max_blocks = 0;
   if (rc != MN_OK) return done(rc);
   // The tie policy, as a single call applies it: images whose tied choices conflict (or all, with
   // MN_TIES_REFERENCE) are redone in the reference's order among equals -- TOGETHER, one workgroup per image in one
@@ -2296,9 +2259,9 @@ extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void
   if (rc != MN_OK) return done(rc);
   // hand-over and output stage of every image (labels, mask, class table, certificate, log-likelihood)
   for (int i = 0; i < count; i++) {
-    ctxs[i]->xw.prerun = redo[i] ? 2 : 1;
+    ctxs[i]->xk.prerun = redo[i] ? 2 : 1;
     const int r = segment_attempt(ctxs[i], calls[i], out ? &out[i] : nullptr, MN_MODE_EXACT, false);
-    ctxs[i]->xw.prerun = 0;
+    ctxs[i]->xk.prerun = 0;
     if (r != MN_OK && rc == MN_OK) rc = r;
   }
   // require_proof = 1, as mn_segment_finish applies it to a single call: a result that chose among bit-equal
@@ -2326,9 +2289,9 @@ extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void
     }
     for (int j = 0; j < n2 && r2 == MN_OK; j++) {
       const int i = rc_idx[j];
-      ctxs[i]->xw.prerun = 2;
+      ctxs[i]->xk.prerun = 2;
       const int r = segment_attempt(ctxs[i], calls[i], &out[i], MN_MODE_EXACT, false);
-      ctxs[i]->xw.prerun = 0;
+      ctxs[i]->xk.prerun = 0;
       if (r != MN_OK && rc == MN_OK) rc = r;
     }
   }
@@ -2513,12 +2476,13 @@ extern "C" int mn_exact_phase_a_device(mn_context* c, const float* d_class_pred,
 }
 
 static int ensure_staging(mn_context* c) {
-  if (c->d_class) return MN_OK;
-  MN_HIP(dev_alloc(c, &c->d_class, c->N * (size_t)c->maxC));
-  MN_HIP(dev_alloc(c, &c->d_same, c->N * (size_t)c->maxO));
-  MN_HIP(dev_alloc(c, &c->d_mask, c->N));
-  MN_HIP(dev_alloc(c, &c->d_objcls, c->N));
-  MN_HIP(dev_alloc(c, &c->d_part, c->N));
+  if (c->d_part) return MN_OK;             // (the last one allocated: the group is whole)
+  c->mem.free_group(MN_MEM_STAGING);       // (what an attempt that failed half-way left)
+  MN_TRY(dev_alloc(c, MN_MEM_STAGING, &c->d_class, c->N * (size_t)c->maxC));
+  MN_TRY(dev_alloc(c, MN_MEM_STAGING, &c->d_same, c->N * (size_t)c->maxO));
+  MN_TRY(dev_alloc(c, MN_MEM_STAGING, &c->d_mask, c->N));
+  MN_TRY(dev_alloc(c, MN_MEM_STAGING, &c->d_objcls, c->N));
+  MN_TRY(dev_alloc(c, MN_MEM_STAGING, &c->d_part, c->N));
   return MN_OK;
 }
 
@@ -2814,7 +2778,7 @@ extern "C" int mn_match_overlaps_device(mn_context* c, const int* d_table, int n
     }
     return done(MN_OK);
   }
-  if (!c->match_work) MN_HIP(dev_alloc(c, &c->match_work, 1));
+  MN_TRY(ensure_scratch(c, &c->match_work, 1));
   match_launch(c, st, d_table, K, G, d_pred_class, d_pred_score, d_truth_class, d_truth_crowd,
                match_thresholds(thresholds, T), T, area_lo, area_hi, d_iou, d_pred_match, d_truth_match, d_pred_ignore,
                d_truth_ignore, /* ordered */ false);
@@ -2838,8 +2802,8 @@ extern "C" int mn_eval_append_device(mn_context* c, const int* d_table, int num_
   if (K == 0 && G == 0) return done(MN_OK);                      // an image without anything: no record, no count
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (!c->match_work) MN_HIP(dev_alloc(c, &c->match_work, 1));
-  if (!c->eval_work) MN_HIP(dev_alloc(c, &c->eval_work, 1));
+  MN_TRY(ensure_scratch(c, &c->match_work, 1));
+  MN_TRY(ensure_scratch(c, &c->eval_work, 1));
   MnEvalWork* e = c->eval_work;
   MnAreaRanges ar;
   for (int a = 0; a < MN_EVAL_MAX_AREAS; a++) {
@@ -2929,7 +2893,7 @@ extern "C" int mn_map_scores_device(mn_context* c, const void* d_class_pred, int
   const int dt = dtype & 0xFF, logits = (dtype & MN_MAPS_LOGITS) ? 1 : 0;
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (!c->ms_partials) MN_HIP(dev_alloc(c, &c->ms_partials, (size_t)MN_MS_VALUES * MN_MS_WORKGROUPS));
+  MN_TRY(ensure_scratch(c, &c->ms_partials, (size_t)MN_MS_VALUES * MN_MS_WORKGROUPS));
   if (!accumulate) MN_HIP(hipMemsetAsync(d_confusion, 0, (size_t)C * C * sizeof(long long), st));
 
   MnMapScoreArgs A;
@@ -2973,7 +2937,7 @@ extern "C" int mn_mask_bce_device(mn_context* c, const void* d_class_logits, con
     return done(MN_ERR_ARGUMENT);
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (!c->ms_partials) MN_HIP(dev_alloc(c, &c->ms_partials, (size_t)MN_MS_VALUES * MN_MS_WORKGROUPS));
+  MN_TRY(ensure_scratch(c, &c->ms_partials, (size_t)MN_MS_VALUES * MN_MS_WORKGROUPS));
 
   MnMaskBceArgs A;
   memset(&A, 0, sizeof(A));
@@ -3041,7 +3005,7 @@ extern "C" int mn_plane_sums_device(mn_context* c, const void* d_logits, int dty
     return done(MN_ERR_ARGUMENT);
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (!c->pl_partials) MN_HIP(dev_alloc(c, &c->pl_partials, (size_t)MN_PL_VALUES * MN_MS_WORKGROUPS));
+  MN_TRY(ensure_scratch(c, &c->pl_partials, (size_t)MN_PL_VALUES * MN_MS_WORKGROUPS));
   A.partials = c->pl_partials;
   const int slots = A.walk.blocks;
   const dim3 g((unsigned)slots), b(MN_PL_THREADS);
