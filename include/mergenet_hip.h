@@ -838,6 +838,55 @@ int mn_plane_grad_device(mn_context* ctx, const void* d_logits, int dtype /* MN_
                          int num_truth, const int* d_truth_classes, int flags, const float* d_coeffs /* [4*P] */,
                          const float* d_factor, void* d_grad, void* stream);
 
+/* The cross-entropy criterion from the label mask: the reference's CrossEntropyLossOneHot (utils/loss.py:24-35,
+ * F.cross_entropy(input, target.max(1)[1]); --loss ce of egs/coco/local/train.py:145-154 on the class planes and of
+ * egs/cityscape/local/train.py:193-204 on the offset planes) on ONE part of the network's output, as a sum, and its
+ * gradient, in ONE pass over one image: no target plane and no argmax plane is written or read.
+ *   d_logits [num_planes][height * width]: float32, float16 or bfloat16 LOGITS (`dtype`: MN_DTYPE_*; MN_MAPS_LOGITS
+ *   is not accepted).  x_q: the element of plane q widened exactly to float32.
+ *   Target plane of a pixel -- what target.max(1)[1] elects on the reference's one-hot planes, the FIRST plane whose
+ *   target is 1, plane 0 where none is:
+ *     part == MN_PART_CLASS: the pixel's truth class (as for mn_mask_bce_device).  A truth class outside
+ *     0..num_planes-1 is an ignore class: the pixel has no term, gets gradient 0 on every plane (the store is made)
+ *     and is not counted.  (The reference has no ignore class: its one-hot planes would be all zero there and elect
+ *     class 0.  With every class in range the two agree.)
+ *     part == MN_PART_OFFSET: offset_list a HOST array of num_planes (di, dj) pairs, any values; the least k whose
+ *     target is 1 -- (r + di_k, c + dj_k) is outside the image or carries the pixel's own truth label -- or plane 0 if
+ *     every plane's target is 0; every pixel takes part; num_truth and d_truth_classes are not used (num_truth >= 0).
+ *   Term of a pixel: logsumexp_q(x_q) - x_target, and its gradient softmax(x)_q - [q == target], in float32 as
+ *     m    = max_q x_q                      a = the first q with x_q == m
+ *     e_q  = expf(x_q - m) for q != a       (e_a is 1)
+ *     r    = sum of e_q, q != a, in ascending q
+ *     term = log1pf(r) + (m - x_target)     (both summands >= 0)
+ *     p_q  = e_q * (1.0f / (1.0f + r));     g_q = (p_q - [q == target]) * scale
+ *   each operation rounded (no fused multiply-add).  An x_q more than about 87 below the maximum has an e_q below
+ *   2^-126: 0 or a subnormal.  num_planes == 1: term 0 and gradient 0.
+ *   d_sums float64 [2]: d_sums[0] = the sum of the terms over the kept pixels, each term widened to float64 before it
+ *   is added; d_sums[1] = the number of kept pixels, an exact integer (height * width in the offset part).
+ *   Gradient: d_grad has the element type and layout of d_logits, or is NULL (the validation loss: nothing but the
+ *   sums is written); element = g_q rounded to nearest even into the element type.  It must not overlap d_logits.  A
+ *   float16 gradient scaled by 1 / (number of pixels) underflows: scale it up (loss scaling) or use bfloat16.
+ * The sums of a call are bit-identical from run to run, the same whether or not a gradient is written and wherever
+ * the map and the gradient lie in memory: no floating-point atomic is used, which pixels a lane adds up follows
+ * (height, width, element type) only and the kernel's form num_planes only (up to 20 planes a lane keeps all planes
+ * of its pixels in registers and reads every logit once; above that it reads them three times, twice without a
+ * gradient, the repeats through the cache), every workgroup writes its partial sums to its own slot of a buffer of the
+ * context and a second launch adds the slots in a fixed order.  accumulate != 0: the two totals are ADDED to what d_sums
+ * holds (one IEEE addition each) -- the totals of a batch, with no synchronisation between images; accumulate == 0:
+ * they are stored.
+ * Accesses: as for mn_mask_bce_device (16-byte accesses where the width is a multiple of 4 float32 / 8 16-bit elements
+ * and both bases are aligned, 8-byte ones for 16-bit maps of width % 8 == 4 aligned to 8, single elements otherwise).
+ * Any image size (not held to the context's capacity).  1 <= num_planes <= MN_MAX_CLASSES (class part) or
+ * MN_MAX_OFFSETS (offset part).  MN_ERR_ARGUMENT: a null pointer that is needed (d_truth_classes when num_truth > 0 in
+ * the class part, offset_list in the offset part), a non-positive size, height * width > INT_MAX, img_width > 2^30, a
+ * count out of range, an unknown part, an unknown dtype or one with MN_MAPS_LOGITS, a scale that is not finite; nothing
+ * is launched then.  The partials buffer is the one of mn_map_scores_device (allocated by the first call of either):
+ * keep the calls of one context on one stream.  Enqueues on `stream` only: no host synchronisation. */
+int mn_mask_ce_device(mn_context* ctx, const void* d_logits, int dtype /* MN_DTYPE_* */, int img_width,
+                      int img_height, int part /* MN_PART_* */, int num_planes, const int* offset_list,
+                      const int* d_truth, int num_truth, const int* d_truth_classes, void* d_grad /* or null */,
+                      float scale, double* d_sums /* [2] */, int accumulate, void* stream);
+
 /* Wire format of the multi-GPU mask exchange (the all-gather of final instance masks the north
  * star asks for; the reference has no exchange, its jobs write files: segment.py:59-61).  d_wire is
  * int16 [n_pixels + 1 + max_instances + 4]: the labels (0..K), K, the classes of labels 1..K

@@ -104,6 +104,7 @@ def _signatures() -> dict:
         "mn_plane_sums_device": (I, [P, P, I, I, I, I, I, IP, P, I, P, I, P, I, P]),
         "mn_plane_coeffs_device": (I, [P, I, I, P, I, D, D, D, P, P, I, P]),
         "mn_plane_grad_device": (I, [P, P, I, I, I, I, I, IP, P, I, P, I, P, P, P, P]),
+        "mn_mask_ce_device": (I, [P, P, I, I, I, I, I, IP, P, I, P, P, F, P, I, P]),
         "mn_tile_class_maps_device": (I, [P, P, P, I, I, I, I, IP, I, IP, I, I, I, I, P, I, I, P]),
         "mn_eval_append_device": (I, [P, P, I, I, P, P, P, P, DP, I, DP, I, I, I, I, P, P, P]),
         "mn_eval_keys_device": (I, [P, P, L, I, P, P]),

@@ -27,6 +27,7 @@
 #include "mn_kernels_mapscore.h"
 #include "mn_kernels_loss.h"
 #include "mn_kernels_planeloss.h"
+#include "mn_kernels_celoss.h"
 #include "mn_kernels_rle.h"
 #include "mn_kernels_tiles.h"
 #include "mn_sweep_form.h"
@@ -3056,6 +3057,48 @@ extern "C" int mn_plane_grad_device(mn_context* c, const void* d_logits, int dty
                          static_cast<hipStream_t>(stream), A);
     });
   });
+  MN_HIP(hipGetLastError());
+  return done(MN_OK);
+}
+
+// ---- cross-entropy over the planes of one part, from the label mask (mn_kernels_celoss.h) ---------------
+// Enqueues only: no host synchronisation, no copy.  Nothing of the segmentation path runs here.
+extern "C" int mn_mask_ce_device(mn_context* c, const void* d_logits, int dtype, int img_width, int img_height,
+                                 int part, int num_planes, const int* offset_list, const int* d_truth, int num_truth,
+                                 const int* d_truth_classes, void* d_grad, float scale, double* d_sums, int accumulate,
+                                 void* stream) {
+  MnPlaneArgs Q;                  // what plane_call refuses is refused here; its grid and walk are this pass's too
+  static_assert(MN_CE_WAVES == MN_PL_WAVES, "mn_mask_ce_device takes the walk that plane_call lays out");
+  if (!d_sums || !std::isfinite(scale) || !plane_call(&Q, c, d_logits, dtype, img_width, img_height, part, num_planes,
+                                                      offset_list, d_truth, num_truth, d_truth_classes, 0, d_grad))
+    return done(MN_ERR_ARGUMENT);
+  MN_HIP(hipSetDevice(c->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  MN_TRY(ensure_scratch(c, &c->ms_partials, (size_t)MN_MS_VALUES * MN_MS_WORKGROUPS));
+
+  MnMaskCeArgs A;
+  memset(&A, 0, sizeof(A));
+  A.maps = Q.maps; A.grad = Q.grad; A.truth = Q.truth; A.truth_classes = Q.truth_classes;
+  A.H = Q.H; A.W = Q.W; A.NP = Q.NP; A.G = Q.G; A.part = Q.part; A.wide = Q.wide;
+  A.scale = scale;
+  A.walk = Q.walk;
+  A.partials = c->ms_partials;
+  memcpy(A.di, Q.di, sizeof(A.di));
+  memcpy(A.dj, Q.dj, sizeof(A.dj));
+  // The form by the plane count alone: resident up to MN_CE_RESIDENT_MAX planes, in the smallest bucket, else streaming.
+  const int bucket = mn_ce_bucket(A.NP);
+  const dim3 g((unsigned)A.walk.blocks), b(MN_CE_THREADS);
+  by_dtype(dtype & 0xFF, [&](auto t) {
+    by_pixels(t, A.walk.v, [&](auto px) {
+      constexpr int DT = decltype(t)::value, V = decltype(px)::value;
+      if (bucket == 4) hipLaunchKernelGGL((mn_mask_ce_pass<DT, V, 4>), g, b, 0, st, A);
+      else if (bucket == 10) hipLaunchKernelGGL((mn_mask_ce_pass<DT, V, 10>), g, b, 0, st, A);
+      else if (bucket == MN_CE_RESIDENT_MAX) hipLaunchKernelGGL((mn_mask_ce_pass<DT, V, MN_CE_RESIDENT_MAX>), g, b, 0, st, A);
+      else hipLaunchKernelGGL((mn_mask_ce_pass<DT, V, 0>), g, b, 0, st, A);
+    });
+  });
+  hipLaunchKernelGGL(mn_map_scores_finish, dim3(MN_CE_VALUES), dim3(64), 0, st, (const double*)c->ms_partials,
+                     A.walk.blocks, d_sums, accumulate);
   MN_HIP(hipGetLastError());
   return done(MN_OK);
 }

@@ -820,3 +820,46 @@ def multi_bce_loss(prediction, part, offsets, truth, truth_classes=None):
             grad[b, p] = scale * ((sp - y[b, p]) * np.where(y[b, p], w, 1.0)
                                   + L1 * (-(n + 2.0) / ((S + 1.0) * (S + 1.0))) * sp * (1.0 - sp))
     return math.fsum(values) * scale, np.where(keep, grad, 0.0)
+
+
+# ---- cross-entropy over the planes of one part, from the label mask: the numpy statement of Merger.mask_ce and of
+# losses.MaskCELoss (CrossEntropyLossOneHot of utils/loss.py:24-35, F.cross_entropy(input, target.max(1)[1]), on the
+# targets of utils/dataset.py:259-277 and :419-429, looked up in the label mask) ---------------------------------------
+
+def ce_targets(part, num_planes: int, offsets, truth, truth_classes, num_truth: int):
+    """(target int64 [H,W], keep bool [H,W]): the target plane of every pixel and the pixels that take part -- what
+    ``target.max(1)[1]`` elects on the one-hot planes of :func:`plane_targets`: the FIRST plane whose target is 1,
+    plane 0 where none is.  Class part: the truth class; a pixel whose truth class lies outside 0..P-1 is ignored
+    (its target is given as 0).  Offset part: the least k whose offset target is 1, else 0; every pixel takes part."""
+    y, keep = plane_targets(part, num_planes, offsets, truth, truth_classes, num_truth)
+    return np.argmax(y, axis=0).astype(np.int64), keep          # (argmax: the first maximal index, 0 when all are 0)
+
+
+def mask_ce(logits, part, offsets, truth, truth_classes, num_truth: int, scale: float = 1.0):
+    """(sums float64 [2], grad float64 [P,H,W]) of one image: the cross-entropy of the softmax over the P planes of
+    one part of the output against the pixel's target plane, and its gradient.
+
+    x is the element widened exactly to float64 (float64 logits are taken as they are), and so is all else.  Target plane: :func:`ce_targets`.
+    Term of a pixel: ``logsumexp_q(x_q) - x_target``; gradient: ``(softmax(x)_q - [q == target]) * scale``.  A pixel
+    whose truth class lies outside 0..P-1 (class part) is an ignore class: term 0, gradient 0, not counted.  That is
+    one difference from the reference, whose one-hot planes would be all zero at such a pixel and would elect class
+    0; with every class in range the two agree.  ``sums[0]``: the correctly rounded sum (``math.fsum``) of the kept
+    pixels' terms, ``sums[1]``: the number of kept pixels."""
+    x = np.asarray(logits).astype(np.float64)
+    P = x.shape[0]
+    target, keep = ce_targets(part, P, offsets, truth, truth_classes, num_truth)
+    if x.shape != (P,) + target.shape:
+        raise ValueError("the logits and the truth mask differ in size")
+    planes = np.arange(P)[:, None, None]
+    m = x.max(axis=0)
+    first = planes == np.argmax(x, axis=0)[None]                # the first maximal plane: its exponential is 1
+    onehot = planes == target[None]
+    e = np.exp(x - m[None])
+    r = np.where(first, 0.0, e).sum(axis=0)                     # sum(exp) - 1, without forming 1 + r
+    x_target = np.take_along_axis(x, target[None], axis=0)[0]
+    term = np.log1p(r) + (m - x_target)                         # (log(1 + r) would lose a term that is about r)
+    rest = np.where(onehot, 0.0, e).sum(axis=0)                 # 1 - softmax_target = rest / (1 + r): nothing cancels
+    grad = np.where(onehot, -rest[None], e) / (1.0 + r)[None] * float(scale)
+    grad = np.where(keep[None], grad, 0.0) + 0.0                # (+ 0.0: no negative zero at P = 1)
+    sums = np.array([math.fsum(term[keep].tolist()), float(keep.sum())], np.float64)
+    return sums, grad

@@ -9,6 +9,13 @@ are looked up in the int32 label mask, and the loss and its gradient come out of
 ``MaskDiceLoss`` and ``MaskMultiBCELoss`` are the recipes' ``--loss dice`` and ``--loss mbce`` (``SoftDiceLoss`` and
 ``MultiBCEWithLogitsLoss`` of utils/loss.py) on one part of the output.  Their gradient depends on totals over a whole
 plane, so they take three steps: ``Merger.plane_sums``, ``Merger.plane_coeffs``, ``Merger.plane_grad``.
+
+``MaskCELoss`` is the recipes' ``--loss ce`` (``CrossEntropyLossOneHot`` of utils/loss.py) on one part of the output:
+a softmax over the part's planes per pixel, loss and gradient in ONE pass per image (``Merger.mask_ce``).
+
+Out of scope for ``MaskCELoss``: a per-class ``weight`` (its mean divides by the sum of the targets' weights, which is
+not known before the pass), a divisor of the kept pixels only (``last_sums[1]`` holds their number for a caller who
+wants it), ``WeightedBCEWithLogitsLoss`` (no recipe uses it) and polygon targets.
 """
 from __future__ import annotations
 
@@ -250,3 +257,69 @@ class MaskMultiBCELoss(_MaskPlaneLoss):
             loss = self.merger.plane_coeffs("mbce", sums[b], pixels=H * W, scale=1.0 / (B * P * H * W), into=loss,
                                             out=coeffs[b])["loss"]
         return loss.to(torch.float32), sums, coeffs
+
+
+# ---- cross-entropy over the planes of one part --------------------------------------------------------------------
+
+class _MaskCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, prediction, module, truth, truth_classes, want_grad):
+        loss, sums, grad = module._run(prediction.detach(), truth, truth_classes, want_grad)
+        module.last_sums = sums
+        ctx.grad = grad
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        grad, ctx.grad = ctx.grad, None
+        if grad is None:
+            raise RuntimeError("MaskCELoss: backward was already run, or forward ran without a gradient")
+        return grad.mul_(grad_output), None, None, None, None      # (no test for 1.0: that would synchronise)
+
+
+class MaskCELoss(_MaskPlaneLoss):
+    """``CrossEntropyLossOneHot()`` of the reference (utils/loss.py:24-35: ``F.cross_entropy(input,
+    target.max(1)[1])`` with mean reduction; ``--loss ce`` of egs/coco/local/train.py:145-154 on the class planes and of
+    egs/cityscape/local/train.py:193-204 on the offset planes) on ONE part of the network's output, from the label
+    mask: neither the one-hot target planes nor their argmax are materialised.
+
+    ``merger``, ``part``, ``offsets`` and the arguments of ``forward(prediction [B, P, H, W], truth [B, H, W] int32,
+    truth_classes=None)`` as for :class:`MaskDiceLoss`: every ``prediction[b]`` a contiguous [P, H, W] block of
+    float32, float16 or bfloat16 LOGITS.  The target plane of a pixel is its truth class (class part) or the first
+    offset plane whose target is 1, plane 0 if none is (offset part): what ``max(1)[1]`` elects.  Returns the loss as a
+    float32 device scalar
+
+        sums[0] / (B*H*W)
+
+    where ``sums`` are the totals of ``Merger.mask_ce`` over the batch (``labels.mask_ce`` is the numpy statement):
+    with no ignore class exactly ``CrossEntropyLossOneHot()(prediction, targets)``.  A pixel whose truth class lies
+    outside 0..P-1 (class part) is an ignore class: it contributes 0 and gets gradient 0, but it still COUNTS in the
+    divisor B*H*W -- the reference has no ignore class and would elect class 0 there; ``last_sums[1]`` holds the
+    number of kept pixels for a caller who wants another normalisation.
+
+    One kernel pass per image, all added into one ``sums`` buffer (``last_sums``, float64 [2]); nothing is
+    synchronised with the host and no plane is copied.  When ``prediction`` requires a gradient (and gradients are
+    enabled) the same pass writes it, already scaled by 1 / (B*H*W), into one buffer of the prediction's shape and
+    dtype; ``backward`` multiplies that buffer by the incoming gradient in place and returns it, so a forward result
+    can be back-propagated once.  Otherwise (``torch.no_grad()``, validation) no gradient buffer is allocated and the
+    loss is the same bits.
+
+    float16: a gradient scaled by 1 / (B*H*W) underflows binary16 at any real image size, and nothing here rescales
+    it behind the caller's back.  Train in bfloat16 or float32, or call ``Merger.mask_ce`` with a ``scale`` of a loss
+    scaler's choosing.
+
+    Not offered: a per-class ``weight``, a divisor of the kept pixels only (see the module's documentation)."""
+
+    def _run(self, prediction, truth, truth_classes, want_grad: bool):
+        B, P, H, W, tcs = self._check(prediction, truth, truth_classes)
+        scale = 1.0 / (B * H * W)
+        grad = torch.empty((B, P, H, W), dtype=prediction.dtype, device=prediction.device) if want_grad else None
+        sums = None
+        for b in range(B):
+            sums = self.merger.mask_ce(prediction[b], self.part, self.offsets, truth[b], tcs[b], scale,
+                                       grad=want_grad, into=sums, out=grad[b] if want_grad else None)["sums"]
+        return (sums[0] * scale).to(torch.float32), sums, grad
+
+    def forward(self, prediction, truth, truth_classes=None):
+        want_grad = prediction.requires_grad and torch.is_grad_enabled()     # (grad mode is off inside the Function)
+        return _MaskCE.apply(prediction, self, truth, truth_classes, want_grad)

@@ -1114,6 +1114,54 @@ class Merger:
         _ok(rc)
         return grad
 
+    def mask_ce(self, logits, part, offsets, truth, truth_classes, scale: float = 1.0, grad: bool = True, into=None,
+                out=None):
+        """The reference's ``CrossEntropyLossOneHot`` (utils/loss.py:24-35: ``F.cross_entropy(input,
+        target.max(1)[1])``, ``--loss ce`` of the recipes) on ONE part of the output, from the label mask: the sum of
+        the pixels' terms and the gradient in one pass on the device -- no target plane and no argmax plane exists,
+        each gradient element is written once.  ``logits`` [P,H,W]: contiguous float32, float16 or bfloat16 LOGITS (a
+        view of the prediction is fine); ``part``: ``'class'`` or ``'offset'`` with ``offsets`` (P pairs); ``truth``,
+        ``truth_classes``: as for :meth:`mask_bce` (``truth_classes`` is not used by the offset part).  Target plane of
+        a pixel: its truth class (class part), or the first offset plane whose target is 1, plane 0 if none is (offset
+        part) -- what ``max(1)[1]`` elects on the one-hot planes.  A pixel whose truth class is outside 0..P-1 is an
+        ignore class: no term, gradient 0, not counted (the reference has none: it would elect class 0 there).
+        Returns ``{"sums": float64 [2], "grad": [P,H,W] or None}`` on the maps' device: ``sums[0]`` the sum of
+        ``logsumexp(x) - x_target`` over the kept pixels, ``sums[1]`` their number (``labels.mask_ce`` is the numpy
+        statement and gives the definitions).  The gradient is ``(softmax(x) - onehot(target)) * scale`` in the maps'
+        dtype; ``grad=False``: the sums alone (the validation loss), bit-equal to those of a call with a gradient.
+        ``out``: the caller's buffer of the maps' shape and dtype, which may be a view.  ``into``: a previous result
+        (or its ``sums`` tensor), to which this image's sums are added with one IEEE addition each.  A float16
+        gradient scaled by 1 / (number of pixels) underflows: pass a larger scale (loss scaling) or use bfloat16.
+        The sums of a call are bit-identical from run to run and do not depend on where the tensors lie in memory.
+        Up to 20 planes every logit is read once; above that the planes are read three times (twice without a
+        gradient), the repeats through the cache.  Any image size; nothing is synchronised or copied.  The calls of
+        one Merger share a buffer of partial sums with :meth:`map_scores`: keep them on ONE stream."""
+        torch = self.torch
+        fn = self._entry("mn_mask_ce_device")
+        part, code, P, H, W, off, G = self._check_planes(logits, part, offsets, truth, truth_classes)
+        dev = logits.device
+        if into is None:
+            sums = torch.empty((2,), dtype=torch.float64, device=dev)
+        else:
+            sums = into["sums"] if isinstance(into, dict) else into
+            _dev_tensor(sums, "into: a previous result of mask_ce on the maps' GPU", torch.float64, shape=(2,),
+                        device=dev)
+        g = None
+        if out is not None:
+            if not grad:
+                raise ValueError("out: the gradient's buffer, with grad=True")
+            g = _dev_tensor(out, "out: a contiguous buffer of the maps' shape and dtype on the maps' GPU", logits.dtype,
+                            shape=logits.shape, device=dev)
+        elif grad:
+            g = torch.empty_like(logits)
+        stream = _stream(dev)
+        rc = fn(self.handle, logits.data_ptr(), code, W, H, part, P,
+                off.ctypes.data_as(_i32p) if off is not None else None, truth.data_ptr(), G,
+                truth_classes.data_ptr() if G else None, g.data_ptr() if g is not None else None, float(scale),
+                sums.data_ptr(), 1 if into is not None else 0, stream)
+        _ok(rc)
+        return {"sums": sums, "grad": g}
+
     def tile_class_maps(self, tiles, flip_tiles, row_starts, col_starts, height: int, width: int, num_classes: int,
                         out_dtype=None, clip: bool = False):
         """The image's class planes from the LOGITS of a semantic network run on overlapping tiles: what the
