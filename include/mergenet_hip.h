@@ -452,7 +452,11 @@ int mn_tile_class_maps_device(mn_context* ctx, const void* d_tiles, const void* 
                               void* d_out, int out_dtype, int clip, void* stream);
 
 /* Nearest-neighbour resize of the instance mask back to the image size, cv2 INTER_NEAREST
- * coordinates (egs/cityscape/local/segment.py:146-149). */
+ * coordinates (egs/cityscape/local/segment.py:146-149), as OpenCV's portable resizeNN forms them, in double:
+ * source index = min(floor(dst * (1. / ((double)dst_size / src_size))), src_size - 1), per axis.  That is neither
+ * the float32 index of torch's mode="nearest" nor the rational floor (dst * src_size) / dst_size: 8 -> 82 differs
+ * from the first at dst 41, 8 -> 98 from the second at dst 49.  mergenet_amd/labels.py::nearest_index is the numpy
+ * statement.  Any sizes, growing or shrinking; out_height <= 65535. */
 int mn_upsample_mask_device(mn_context* ctx, const int* d_mask, int in_height, int in_width,
                             int* d_out, int out_height, int out_width, void* stream);
 
@@ -469,8 +473,9 @@ int mn_rle_points_device(mn_context* ctx, const int* d_mask, int height, int wid
  * instances).  points = [positions | label before | label at] with stride `capacity` (host copy of
  * d_points), n of them.  Strings are concatenated into `out` (string k-1 = out[offsets[k-1] ..
  * offsets[k]) ), areas[k-1] = pixels of instance k (0 => the caller may drop it, as
- * egs/cityscape/local/evaluate.py:52-54 does).  Returns the bytes needed; nothing is written past
- * out_capacity.  Needs no GPU. */
+ * egs/cityscape/local/evaluate.py:52-54 does).  A label outside 1..num_instances in the mask (a negative
+ * ignore label, a label above the count) is ignored: it gets no string and counts as zeros in the strings of
+ * the others, as `mask == k` does.  Returns the bytes needed; nothing is written past out_capacity.  Needs no GPU. */
 long long mn_rle_encode_host(const int* points, int capacity, int n, int height, int width,
                              int num_instances, unsigned char* out, long long out_capacity,
                              long long* offsets, int* areas);
@@ -891,7 +896,9 @@ int mn_mask_ce_device(mn_context* ctx, const void* d_logits, int dtype /* MN_DTY
  * star asks for; the reference has no exchange, its jobs write files: segment.py:59-61).  d_wire is
  * int16 [n_pixels + 1 + max_instances + 4]: the labels (0..K), K, the classes of labels 1..K
  * padded with -1, then the float64 total log-likelihood as four 16-bit words, low word first
- * (the scalars ride the same gather).  Needs no context; max_instances <= 32767. */
+ * (the scalars ride the same gather).  Needs no context; max_instances <= 32767.  d_wire may start
+ * at any int16 element and d_mask at any int32 element (a wire inside a batch buffer, a plane of a larger tensor):
+ * the vector accesses are taken only where both bases have their natural alignment. */
 int mn_pack_wire_device(const int* d_mask, const int* d_object_class, int num_instances,
                         double total_logprob, int n_pixels, int max_instances, short* d_wire,
                         void* stream);

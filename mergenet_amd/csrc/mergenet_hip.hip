@@ -2587,7 +2587,8 @@ extern "C" int mn_upsample_mask_device(mn_context* c, const int* d_mask, int in_
   MN_HIP(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(mn_upsample_mask, dim3(grid_for(out_width, 256), out_height), dim3(256), 0, st,
-                     d_mask, in_height, in_width, d_out, out_height, out_width);
+                     d_mask, in_height, in_width, d_out, out_height, out_width,
+                     mn_nearest_scale(in_width, out_width), mn_nearest_scale(in_height, out_height));
   MN_HIP(hipGetLastError());
   return done(MN_OK);
 }

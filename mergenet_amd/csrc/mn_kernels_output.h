@@ -401,11 +401,20 @@ __global__ __launch_bounds__(256) void mn_pack_wire(int n_pixels, int max_instan
                                                     short* __restrict__ wire) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int n4 = n_pixels >> 2;
+  // The 16-byte load and the 8-byte store need their natural alignment.  A wire that is one of several in a
+  // buffer (MaskExchange with batch > 1: wire b starts b * (n_pixels + 1 + max_instances + 4) int16 elements in,
+  // an odd count for an even n_pixels) or a mask that is a plane of a larger tensor need not have it: those go
+  // element by element, which any base serves.  Uniform over the launch.
+  const bool vec = ((reinterpret_cast<size_t>(mask) & 15) | (reinterpret_cast<size_t>(wire) & 7)) == 0;
   if (i < n4) {
-    const int4 m = *reinterpret_cast<const int4*>(mask + 4 * (size_t)i);
-    short4 o;
-    o.x = (short)m.x; o.y = (short)m.y; o.z = (short)m.z; o.w = (short)m.w;
-    *reinterpret_cast<short4*>(wire + 4 * (size_t)i) = o;
+    if (vec) {
+      const int4 m = *reinterpret_cast<const int4*>(mask + 4 * (size_t)i);
+      short4 o;
+      o.x = (short)m.x; o.y = (short)m.y; o.z = (short)m.z; o.w = (short)m.w;
+      *reinterpret_cast<short4*>(wire + 4 * (size_t)i) = o;
+    } else {
+      for (int j = 0; j < 4; j++) wire[4 * (size_t)i + j] = (short)mask[4 * (size_t)i + j];
+    }
   }
   if (i < n_pixels - (n4 << 2)) wire[(n4 << 2) + i] = (short)mask[(n4 << 2) + i];
   if (i <= max_instances) {

@@ -11,8 +11,12 @@
 //     -> mn_upsample_mask
 // Interpolation follows cv2's INTER_LINEAR for float images: source coordinate
 // (dst + 0.5) * scale - 0.5, clamped at both borders, horizontal then vertical blend in float32.
-// torch.nn.functional.interpolate(mode="bilinear", align_corners=False) uses the same mapping and
-// serves as the float reference in the tests (cv2 itself is not installed in this image).
+// The coordinate is formed in float32 where cv2 forms it in double and casts: a few ulp of its magnitude apart,
+// times the local slope of the map in the result (the blend is continuous in the coordinate).
+// cv2 itself is not installed: mergenet_amd/resize.py states both resizes in numpy float64 from OpenCV's published
+// source, and tests/test_gpu_edges.py holds the kernels to it (the bilinear one within a bound derived per element);
+// torch.nn.functional.interpolate(mode="bilinear", align_corners=False) uses the same mapping and is the float32
+// reference of tests/test_gpu_prepare.py.
 #pragma once
 
 #include "mn_device.h"
@@ -67,14 +71,26 @@ __global__ __launch_bounds__(256) void mn_prepare_maps(const void* __restrict__ 
   else static_cast<mn_u16*>(out)[o] = out_dtype == MN_DTYPE_F16 ? mn_narrow_f16(v) : mn_narrow_bf16(v);
 }
 
-// cv2 INTER_NEAREST: source index = min(floor(dst * src/dst_size), src - 1)
+// cv2 INTER_NEAREST, as OpenCV's portable resizeNN forms the index, all in double:
+//   fx = (double)dst_size / src_size;  ifx = 1. / fx;  source index = min(cvFloor(dst * ifx), src_size - 1)
+// mn_nearest_scale is the first two steps (two roundings: not src_size / dst_size, and not the rational floor
+// (dst * src_size) / dst_size either -- 8 -> 98 takes source 3 at dst 49 where the exact quotient is 4); the
+// entry point takes them once on the host, each lane the product and the floor, in double.  In float32
+// (torch's mode="nearest") whole rows and columns come from the neighbouring source pixel at many size pairs
+// (8 -> 82, 24 -> 34, 1000 -> 1040, ...); labels.nearest_index is the numpy statement.
+static inline double mn_nearest_scale(int src_size, int dst_size) {
+  const double fx = (double)dst_size / (double)src_size;
+  return 1.0 / fx;
+}
+
 __global__ __launch_bounds__(256) void mn_upsample_mask(const int* __restrict__ in, int Hin, int Win,
-                                                        int* __restrict__ out, int Hout, int Wout) {
+                                                        int* __restrict__ out, int Hout, int Wout,
+                                                        double ifx, double ify) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   const int y = blockIdx.y;
   if (x >= Wout) return;
-  const int sx = min((int)floorf((float)x * ((float)Win / (float)Wout)), Win - 1);
-  const int sy = min((int)floorf((float)y * ((float)Hin / (float)Hout)), Hin - 1);
+  const int sx = min((int)floor((double)x * ifx), Win - 1);
+  const int sy = min((int)floor((double)y * ify), Hin - 1);
   out[(size_t)y * Wout + x] = in[(size_t)sy * Win + sx];
 }
 

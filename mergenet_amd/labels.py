@@ -10,7 +10,8 @@ comparison with the ground truth (``overlap_table``, ``instance_iou``, ``match_i
 ``Merger.overlap_table`` / ``Merger.match_instances``, of the dataset-level evaluation (``eval_records``,
 ``coco_accumulate``, ``coco_summarize``: the checkers of ``Merger.dataset_eval``), and of the scores of the network's maps themselves
 (``map_scores``, the checker of ``Merger.map_scores``, with the reference's summaries ``class_scores`` and
-``offset_iou``).
+``offset_iou``), and of the sameness targets of a label mask (``sameness_targets``, the checker of
+``Merger.sameness_targets``).
 """
 
 from __future__ import annotations
@@ -573,6 +574,29 @@ def _truth_class_of(truth, truth_classes, num_truth: int):
     if G:
         by_label[1:] = np.asarray(truth_classes).astype(np.int64).reshape(-1)[:G]
     return by_label[np.where((t < 0) | (t > G), 0, t)]
+
+
+def sameness_targets(mask, offsets) -> np.ndarray:
+    """float32 [O,H,W]: the sameness targets of an instance mask as utils/dataset.py:259-277 defines them, the
+    statement of ``Merger.sameness_targets``: for offset (i, j) the mask rolled by (-i, -j) compared with itself --
+    as plain integers, negative (ignore) labels included -- and the rows and columns whose neighbour the roll
+    wrapped round forced to 1; an offset that reaches past the image gives all ones."""
+    m = np.asarray(mask)
+    out = np.zeros((len(offsets),) + m.shape, np.float32)
+    for n, (i, j) in enumerate(offsets):
+        i, j = int(i), int(j)
+        rolled = np.roll(np.roll(m, -i, axis=0), -j, axis=1)
+        t = (rolled == m)
+        if i < 0:
+            t[:-i, :] = 1
+        elif i > 0:
+            t[-i:, :] = 1
+        if j < 0:
+            t[:, :-j] = 1
+        elif j > 0:
+            t[:, -j:] = 1
+        out[n] = t
+    return out
 
 
 def _different(t, di: int, dj: int):

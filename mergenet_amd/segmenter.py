@@ -553,7 +553,13 @@ class Merger:
         return out
 
     def upsample_mask(self, mask, out_height: int, out_width: int):
-        """Instance mask back to the image size, cv2 INTER_NEAREST coordinates (segment.py:146-149)."""
+        """Instance mask int32 [H,W] on this GPU -> int32 [out_height, out_width], growing or shrinking: what
+        ``cv2.resize(mask, (out_width, out_height), interpolation=cv2.INTER_NEAREST)`` gives (segment.py:146-149).
+        The source index of each axis is cv2's, formed in double: ``min(floor(dst * (1. / (dst_size / src_size))),
+        src_size - 1)`` -- not the float32 index of ``torch.nn.functional.interpolate(mode="nearest")``, which takes
+        the neighbouring source row or column at many size pairs (8 -> 82 at index 41, 1000 -> 1040 at 30 indices),
+        and not the rational floor either (8 -> 98 at index 49).  ``resize.upsample_mask`` is the numpy statement,
+        written from OpenCV's published source."""
         torch = self.torch
         H, W = self._check_mask(mask)
         out = torch.empty((out_height, out_width), dtype=torch.int32, device=mask.device)
@@ -572,7 +578,10 @@ class Merger:
         pycocotools' compressed counts strings.  Returns a list of ``{"size": [H, W], "counts": bytes,
         "area": pixels, "label": k}``, one per instance in label order; ``drop_zero_area`` leaves out
         instances without pixels (e.g. lost in the nearest-neighbour resize), as
-        ``egs/cityscape/local/evaluate.py:52-54`` does before COCOeval.
+        ``egs/cityscape/local/evaluate.py:52-54`` does before COCOeval.  A label outside ``1..num_instances`` in
+        the mask -- a negative ignore label, a label above the count -- is ignored: it gets no entry and counts as
+        zeros in the strings of the others, as ``mask == i`` does.  A mask with more label changes than the
+        Merger's buffer holds (at first ``max(1024, H * W / 16)``) is counted, the buffer grown, and encoded again.
         """
         torch = self.torch
         H, W = self._check_mask(mask)

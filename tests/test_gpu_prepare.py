@@ -1,8 +1,10 @@
 """Producer hand-off and mask post-processing kernels against a plain PyTorch fp32 reference.
 
 Float kernel => torch reference (cv2 is not installed here): F.interpolate(mode="bilinear",
-align_corners=False) uses cv2.resize/INTER_LINEAR's coordinate mapping, mode="nearest" is cv2's
-INTER_NEAREST.  Tolerance: 2e-6 absolute on probabilities (float32 blend order differs).
+align_corners=False) uses cv2.resize/INTER_LINEAR's coordinate mapping; mode="nearest" computes INTER_NEAREST's
+index in float32 where cv2 computes it in double, and agrees with it only at some size pairs (those used here).
+Tolerance: 2e-6 absolute on probabilities (float32 blend order differs).  The same kernels against the float64
+statements of mergenet_amd/resize.py, at the sizes where the formulas part: tests/test_gpu_edges.py.
 """
 import numpy as np
 import pytest
@@ -34,6 +36,10 @@ def test_prepare_matches_torch_bilinear(shape, sigmoid):
 
 @pytest.mark.parametrize("shape", [((32, 48), (64, 96)), ((25, 35), (50, 70)), ((40, 56), (37, 129))])
 def test_upsample_mask_matches_torch_nearest(shape):
+    # torch's mode="nearest" takes the source index in float32, the kernel takes cv2's, in double
+    # (resize.nearest_index).  At these size pairs the two agree at every index (test_resize.py checks that on the
+    # CPU), so torch can stand in for cv2 here; at 8 -> 82, 24 -> 34, 1000 -> 1040 and many others it cannot:
+    # test_gpu_edges.py::test_upsample_mask_is_cv2_nearest holds the kernel to the statement there.
     import torch
     import torch.nn.functional as F
     from mergenet_amd import segmenter as seg
@@ -76,24 +82,12 @@ def test_prepare_then_segment_equals_host_pipeline(oracle):
 def test_sameness_targets_match_numpy_roll_definition():
     """np.roll compare with the border forced to 1, as utils/dataset.py:259-277 defines it."""
     import torch
-    from mergenet_amd import segmenter as seg, synth
+    from mergenet_amd import labels, segmenter as seg, synth
     rng = np.random.default_rng(5)
     H, W = 37, 53
     mask = rng.integers(0, 4, (H, W)).astype(np.int32)
     offs = synth.generate_offsets(10, 6)
-    expect = np.zeros((len(offs), H, W), np.float32)
-    for n, (i, j) in enumerate(offs):
-        rolled = np.roll(np.roll(mask, -i, axis=0), -j, axis=1)
-        t = (rolled == mask)
-        if i < 0:
-            t[:-i, :] = 1
-        elif i > 0:
-            t[-i:, :] = 1
-        if j < 0:
-            t[:, :-j] = 1
-        elif j > 0:
-            t[:, -j:] = 1
-        expect[n] = t
+    expect = labels.sameness_targets(mask, offs)      # (the np.roll definition, shared with test_gpu_edges.py)
     m = seg.Merger(H, W, 4, len(offs))
     got = m.sameness_targets(torch.from_numpy(mask).cuda(), offs).cpu().numpy()
     assert np.array_equal(got, expect)
