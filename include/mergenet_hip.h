@@ -522,8 +522,19 @@ int mn_rle_decode_device(mn_context* ctx, const unsigned* d_counts, const int* d
 int mn_sameness_targets_device(mn_context* ctx, const int* d_mask, int height, int width,
                                const int* offset_list, int offset_dim, float* d_out, void* stream);
 
-/* Confidence of the instances of the last mn_segment_device call: d_scores[k-1] = lp[cls] - lp[0]
- * of label k (segment.h:109); the reference's COCO results carry a constant score 1. */
+/* Confidence of the instances of the last segmentation on this context (mn_segment_device, mn_segment_finish, the
+ * context's image of mn_segment_exact_batch): d_scores[k-1] = lp[cls] - lp[0] of label k (segment.h:109), for the
+ * labels 1..num_instances of that call; words of d_scores behind them, and all of them when it found no instance,
+ * are not written.  The reference's COCO results carry a constant score 1.
+ *
+ * Contract: the call gives the scores of the last segmentation on this context, or it refuses -- never a third
+ * thing.  It computes nothing from the maps: it reads what that segmentation left in the context (the sums of the
+ * objects; for a single-pixel instance the caller's class maps, which must still be alive and unchanged).  It
+ * refuses with MN_ERR_ARGUMENT, launching nothing, on a context that has not segmented yet, whose last
+ * segmentation failed after its first launch, that has an unfinished mn_segment_launch, or on which one of
+ * mn_score_device, mn_sweep_device, mn_sweep_time_device or mn_exact_phase_a_device ran since: those overwrite the
+ * state.  A call that is rejected for its arguments before anything ran, and every other entry point (resize, RLE,
+ * tables, matching, evaluation, map scores, criteria, wires, tiles), leaves the scores available. */
 int mn_instance_scores_device(mn_context* ctx, float* d_scores, void* stream);
 
 /* Instance table of a label mask (labels 0..num_instances, 0 = background): what a detection result needs per

@@ -165,7 +165,11 @@ struct mn_context {
   } replay;
   hipStream_t side;       // the single-workgroup tail of an image runs here, beside the next image's sweeps
   hipEvent_t ev_fork;
-  ImgParams last_params;  // of the most recent mn_segment_device call (for mn_instance_scores_device)
+  // What mn_instance_scores_device reads: parent, label, ocls, lpvalid and lpsum as the last segmentation left them,
+  // and through last_params the caller's class planes (element type, logits flag and clip with them).  last_valid
+  // says that all of it is still that segmentation's: set where an attempt has queued everything (and kept only
+  // if its read-back succeeds), cleared by scores_stale() in every entry that overwrites one of those arrays.
+  ImgParams last_params;
   int last_valid;
   MnMatchWork* match_work;  // scratch of mn_match_overlaps_device (mn_kernels_match.h): allocated on first use
   MnEvalWork* eval_work;    // scratch of mn_eval_append_device (mn_kernels_eval.h): allocated on first use
@@ -521,6 +525,10 @@ static int ensure_fast(mn_context* c) {
   MN_TRY(dev_alloc(c, MN_MEM_FAST, &c->cc_negbits, N + 16));
   return MN_OK;
 }
+
+// The entry in progress overwrites an array the score kernel reads (or may, depending on the form of its sweep):
+// until the next segmentation has finished, mn_instance_scores_device refuses.
+static inline void scores_stale(mn_context* c) { c->last_valid = 0; }
 
 static void drop_replay_graphs(mn_context::Replay& rp) {
   if (rp.eA) { (void)hipGraphExecDestroy(rp.eA); rp.eA = nullptr; }
@@ -1993,7 +2001,8 @@ static int close_attempt(mn_context* c, const ImageCall& call, const Plan& pl, A
 static int segment_attempt(mn_context* c, const ImageCall& call, mn_stats* stats, int force_mode, bool speculate, bool defer = false) {
   ImgParams P;
   int rc = begin_call(c, call, call.d_mask && call.d_objcls, stats, &P);
-  if (rc != MN_OK) return rc;
+  if (rc != MN_OK) return rc;           // (refused before anything ran: the scores of the image before stay available)
+  scores_stale(c);                      // an attempt that fails half-way leaves the context refusing
   // (development aid: MN_DEBUG_FLAGS_OR in the environment is OR-ed into debug_flags, so that a whole
   //  test run can be put through an opt-in code path)
   static const int env_flags = getenv("MN_DEBUG_FLAGS_OR") ? atoi(getenv("MN_DEBUG_FLAGS_OR")) : 0;
@@ -2014,8 +2023,11 @@ static int segment_attempt(mn_context* c, const ImageCall& call, mn_stats* stats
   if ((rc = launch_finisher(c, P, pl, A, call)) != MN_OK) return rc;
   if ((rc = launch_output(c, P, pl, A, call)) != MN_OK) return rc;
   if ((rc = launch_certificate(c, P, pl, A)) != MN_OK) return rc;
-  c->last_params = P; c->last_valid = 1;
-  return close_attempt(c, call, pl, A, stats, defer);
+  c->last_params = P;
+  rc = close_attempt(c, call, pl, A, stats, defer);
+  // (MN_PENDING: mn_segment_finish reads the verdict, and clears the flag again if it is not MN_OK)
+  if (rc == MN_OK || rc == MN_PENDING) c->last_valid = 1;
+  return rc;
 }
 
 // The image of last time again, through the same buffers: the sweep between its events, then the two graphs.
@@ -2023,6 +2035,7 @@ static int replay_launch(mn_context* c, const ImageCall& call) {
   ImgParams P;
   const int rc = begin_call(c, call, true, nullptr, &P);
   if (rc != MN_OK) return rc;
+  scores_stale(c);
   const hipStream_t st = call.stream;
   c->debug_flags = call.opts.debug_flags;      // (deliberate carry-over: without MN_DEBUG_FLAGS_OR, unlike segment_attempt)
   c->ext_events = !(call.opts.debug_flags & (MN_DEBUG_NO_EVENTS | MN_DEBUG_SWEEP_EVENT_PACKETS));
@@ -2132,6 +2145,7 @@ extern "C" int mn_segment_finish(mn_context* c, mn_stats* stats) {
     t_synced = host_now_us();
     memset(&q.stats, 0, sizeof(q.stats));
     rc = segment_read_back(c, &o, q.queued, &q.stats);
+    if (rc != MN_OK) scores_stale(c);     // (a verdict: the attempts below set it again; an error: the context refuses)
     // a speculative attempt that does not hold is redone: by the sequential order itself when the
     // caller wants a proven result and the input is not sign-separable (the rounds would only
     // approximate it), else on the ordinary path
@@ -2215,6 +2229,9 @@ extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void
   }
   MN_HIP(hipSetDevice(ctxs[0]->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
+  // (the set-up below writes `parent` long before the hand-over sets the flag again: a batch that fails in between
+  //  must not leave a context answering for the image it segmented before)
+  for (int i = 0; i < count; i++) scores_stale(ctxs[i]);
   // (require_proof reads every image's verdict after the hand-over: statistics are kept also when the caller wants none)
   HostBuf<mn_stats> own_stats((!stats && o.require_proof > 0) ? (size_t)count : 0);
   mn_stats* out = stats ? stats : (o.require_proof > 0 ? (mn_stats*)own_stats : nullptr);
@@ -2280,6 +2297,9 @@ extern "C" int mn_segment_exact_batch_t(mn_context** ctxs, int count, const void
         continue;
       }
       rc_ctx[n2] = ctxs[i]; rc_P[n2] = Ps[i]; rc_idx[n2] = i; n2++;
+      // (the redo's set-up resets `parent` under the labels of the hand-over above: should it fail, or be given up for
+      //  MN_ERR_UNPROVEN, the context refuses; the second hand-over below sets the flag again)
+      scores_stale(ctxs[i]);
     }
     const int r2 = n2 > 0 ? redo_in_reference_order(rc_ctx, n2, rc_P, st, true) : MN_OK;
     if (r2 == MN_ERR_CAPACITY) {
@@ -2320,6 +2340,7 @@ extern "C" int mn_score_device_t(mn_context* c, const void* d_class_pred, int cl
   ImgParams P;
   int rc = begin_call(c, call, true, nullptr, &P);
   if (rc != MN_OK) return rc;
+  scores_stale(c);                 // (run_phase_a: parent, ocls, lpvalid)
   const hipStream_t st = call.stream;
   // (deliberate carry-over: the flags as given, without MN_DEBUG_FLAGS_OR; ext_events and core_radius as the last call left them)
   c->debug_flags = call.opts.debug_flags;
@@ -2364,6 +2385,7 @@ extern "C" int mn_sweep_device_t(mn_context* c, const void* d_class_pred, int cl
   c->debug_flags = call.opts.debug_flags | MN_DEBUG_NO_EVENTS;
   c->ext_events = 0;
   c->cc_clean = 0;
+  scores_stale(c);                 // (the sweep: lpsum as its group sums; ocls and lpvalid in the forms that carry classes)
   const SweepForm F = sweep_form_of(c, P, SWEEP_EXPORT);
   const size_t sign_waves = (size_t)F.waves;
   MN_HIP(hipMemsetAsync(c->scalars, 0, MN_NSCALARS * sizeof(int), st));
@@ -2417,6 +2439,7 @@ extern "C" int mn_sweep_time_device_t(mn_context* c, const void* const* d_class_
   c->debug_flags = call.opts.debug_flags | MN_DEBUG_NO_EVENTS;
   c->ext_events = 0;
   c->cc_clean = 0;
+  scores_stale(c);                 // (the sweep: lpsum as its group sums; ocls and lpvalid in the forms that carry classes)
   MN_HIP(hipMemsetAsync(c->scalars, 0, MN_NSCALARS * sizeof(int), st));
   for (int phase = 0; phase < 2; phase++) {          // a tenth of the launches untimed first
     const int n = phase == 0 ? (reps + 9) / 10 : reps;
@@ -2457,6 +2480,7 @@ extern "C" int mn_exact_phase_a_device_t(mn_context* c, const void* d_class_pred
   ImgParams P;
   int rc = begin_call(c, call, d_oml_out && d_prio_out, nullptr, &P);
   if (rc != MN_OK) return rc;
+  scores_stale(c);                 // (exact_setup: parent)
   hipStream_t st = static_cast<hipStream_t>(stream);
   // (deliberate carry-over: debug_flags is not set here -- nothing below reads it)
   if ((rc = exact_setup(c, P, st)) != MN_OK) return done(rc);
@@ -2644,7 +2668,8 @@ extern "C" int mn_sameness_targets_device(mn_context* c, const int* d_mask, int 
 // d_scores[k-1] = lp[cls] - lp[0] of label k (float32, at least num_instances entries).  The class
 // planes passed to that call must still be alive (objects that never merged read them).
 extern "C" int mn_instance_scores_device(mn_context* c, float* d_scores, void* stream) {
-  if (!c || !d_scores || !c->last_valid) return done(MN_ERR_ARGUMENT);
+  // (a context with an unfinished launch is busy: its tail may still be running on the side stream)
+  if (!c || !d_scores || !c->last_valid || c->pend.active) return done(MN_ERR_ARGUMENT);
   MN_HIP(hipSetDevice(c->device));
   hipLaunchKernelGGL(mn_instance_scores, dim3(grid_for(c->last_params.N, 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), c->last_params, obj_state(c),

@@ -5,7 +5,8 @@ order (``utils/csegment/segment.cc:503``), this library in ascending surviving p
 are therefore compared as partitions plus per-instance class.
 
 Also the numpy statements of the instance table and the small-instance filter (``instance_table``,
-``filter_instances``), the checkers of ``Merger.instance_table`` / ``Merger.filter_instances``, and those of the
+``filter_instances``), the checkers of ``Merger.instance_table`` / ``Merger.filter_instances``, of the per-instance
+confidence (``instance_scores``, the checker of ``Merger.instance_scores``), and those of the
 comparison with the ground truth (``overlap_table``, ``instance_iou``, ``match_instances``), the checkers of
 ``Merger.overlap_table`` / ``Merger.match_instances``, of the dataset-level evaluation (``eval_records``,
 ``coco_accumulate``, ``coco_summarize``: the checkers of ``Merger.dataset_eval``), and of the scores of the network's maps themselves
@@ -141,6 +142,60 @@ def filter_instances(mask: np.ndarray, class_table, num_instances: int, table: n
     if scores is not None:
         new_scores = np.asarray([scores[k - 1] for k in kept], np.float32)
     return out, new_classes, new_scores, new_table, len(kept), remap
+
+
+# ---- per-instance confidence: the numpy statement of Merger.instance_scores --------------------------------------
+# (Object::GetNoBackLogprob, segment.h:109, summed over the pixels the result mask gives the instance)
+
+EPS32 = float(np.finfo(np.float32).eps)          # MN_EPS32: the clip of the loaders is [eps, 1 - eps] in float32
+
+
+def loaded_class_probs(class_maps, logits: bool = False, clip: bool = False) -> np.ndarray:
+    """float32 [C,H,W]: the probability every kernel sees when it loads an element of the class maps (``mn_ld_class``).
+
+    The element is widened exactly to float32.  With ``logits`` it is a logit and the loader takes
+    ``1 / (1 + exp(-x))``: here each operation in float64 and ONE rounding to float32 (the device takes it in
+    float32, within a few units in the last place of this value).  The clip to ``[eps32, 1 - eps32]`` (float32
+    min / max, ``mn_clip``) applies where the loader applies it: always for logits and for 16-bit maps, for float32
+    probabilities only when the caller asks (``clip_inputs``).  numpy has no bfloat16: such maps come as their float32
+    widening, with ``clip=True``; a ``numpy.float16`` array is clipped by its dtype."""
+    x = np.asarray(class_maps)
+    lowp = x.dtype == np.float16
+    p = x.astype(np.float32)
+    if logits:
+        with np.errstate(over="ignore"):
+            p = (1.0 / (1.0 + np.exp(-p.astype(np.float64)))).astype(np.float32)
+    if clip or logits or lowp:
+        one = np.float32(1.0)
+        p = np.minimum(np.maximum(p, np.float32(EPS32)), one - np.float32(EPS32)).astype(np.float32)
+    return p
+
+
+def instance_scores(class_maps, mask, class_table, num_instances: int, logits: bool = False,
+                    clip: bool = False) -> np.ndarray:
+    """float64 [K]: ``score[k-1]`` = the sum over the pixels with ``mask == k`` of ``log p[class_table[k-1]] - log p[0]``,
+    with p = :func:`loaded_class_probs` ``(class_maps, logits, clip)`` and the logarithms in float64 (each class's sum
+    is the correctly rounded sum of its terms, ``math.fsum``, then ONE subtraction).  A label without pixels scores 0; labels outside
+    1..K are ignored; K = 0 gives an empty array.  The class of instance k is the table's word, whatever the maps say."""
+    p = loaded_class_probs(class_maps, logits, clip)
+    C, H, W = p.shape
+    m = np.asarray(mask).astype(np.int64)
+    if m.shape != (H, W):
+        raise ValueError("the class maps and the mask differ in size")
+    K = int(num_instances)
+    table = np.asarray(class_table).astype(np.int64).reshape(-1)[:K]
+    if table.size != K or (K and (table.min() < 0 or table.max() >= C)):
+        raise ValueError("class_table: K classes in 0..C-1 are needed")
+    out = np.zeros(K, np.float64)
+
+    def log_sum(values):         # (math.log: the C library's, one and the same on every host; log 0 = -inf)
+        return math.fsum(math.log(v) if v > 0.0 else -math.inf for v in values.astype(np.float64).tolist())
+
+    for k in range(1, K + 1):
+        sel = m == k
+        if sel.any():
+            out[k - 1] = log_sum(p[table[k - 1]][sel]) - log_sum(p[0][sel])
+    return out
 
 
 # ---- overlap table, IoU and matching against the ground truth: the numpy statements of the device path ------

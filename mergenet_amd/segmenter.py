@@ -714,7 +714,12 @@ class Merger:
         return out
 
     def instance_scores(self, num_instances: int, device=None):
-        """lp[cls] - lp[0] of each instance of the last segment() call (float32 [K])."""
+        """lp[cls] - lp[0] of each instance of the last segmentation on this Merger (float32 [K];
+        ``labels.instance_scores`` is the float64 statement).  The scores of that segmentation, or MergeNetError
+        (``MN_ERR_ARGUMENT``, nothing launched): before the first segmentation, between ``segment_async`` and its
+        ``result()``, after a segmentation that failed half-way, and after ``score``, ``sweep``, ``sweep_time`` or
+        ``exact_phase_a``, which overwrite what the call reads.  Every other call may come in between.  The class
+        maps of that segmentation must still be alive and unchanged (single-pixel instances read them)."""
         torch = self.torch
         dev = torch.device("cuda", self.device) if device is None else device
         out = torch.zeros((max(1, num_instances),), dtype=torch.float32, device=dev)
